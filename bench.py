@@ -8,10 +8,13 @@ BASELINE.json configs[1]: DEGREE_FE=4, DIMENSION=3, uniform cube, n = 54 cells p
 n(N) = round(54 N^(1/3)) cells per direction (configs[3]: N = 8 -> 108^3 cells, 81 182 737 DoFs) and is
 sharded by z-slabs, one process per GPU, interface-plane sums over RCCL (weak scaling).
 
-Prints ONE JSON line on rank 0.  Inputs are resident in HBM when the timed region starts.
+Prints ONE JSON line on rank 0.  Inputs are resident in HBM when the timed region starts.  A plain run measures the
+headline only; --full adds the cold start, the roofline leg, the CPU baseline and the renumbered second line.
+--dump-outputs DIR writes what the last timed step computed (same arguments, same inputs: builds compare output for output).
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -64,6 +67,21 @@ def launch_ranks(n, argv):
     print(line, flush=True)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of values + indices written per run (all ranks together)
+
+
+def dump_outputs(dirname, name, y, budget):
+    """--dump-outputs: the device vector y as DIR/<name>.npy (float32 / float64 as computed).  Larger than `budget`
+    bytes: a fixed seeded sample of its entries instead, in ascending index order, and the indices (float64, exact)
+    as DIR/<name>_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    n, s = y.numel(), y.element_size()
+    if n * s <= budget:
+        np.save(os.path.join(dirname, name + ".npy"), y.cpu().numpy())
+        return
+    idx = np.sort(np.random.default_rng(20241016).choice(n, budget // (s + 8), replace=False))
+    np.save(os.path.join(dirname, name + ".npy"), y[torch.from_numpy(idx).to(y.device)].cpu().numpy())
+    np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
 
 
 def algorithmic_bytes(n_dofs, n_cells, nd, s):
@@ -130,8 +148,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ramp-steps", type=int, default=2000,
                     help="untimed applies BEFORE the warm-up steps (0: none): an MI355X that idled through the set-up needs "
-                         "~0.2 s of load to reach its sustained clocks; the first --steps applies are timed cold and "
-                         "reported beside the headline (config.cold_start)")
+                         "~0.2 s of load to reach its sustained clocks; with --full the first --steps applies are timed "
+                         "cold and reported beside the headline (config.cold_start)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the cold start, the roofline leg (per-launch "
+                         "kernel timing), the CPU baseline with the GPU-vs-CPU figure and the renumbered second line. "
+                         "Without it the run sets up, warms up, times --steps applies and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the vector the last timed step computed to DIR/*.npy "
+                         "(whole, or a fixed seeded sample of it with its indices when larger than %d MiB)" % (DUMP_BYTES >> 20))
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--cells", type=int, default=54, help="cells per direction at N=1")
     ap.add_argument("--cpu-cells", type=int, default=0, help="cells per direction of the CPU sample (0: as --cells)")
@@ -140,7 +165,7 @@ def main():
                     help="N > 1: exchange of the slab interface planes. cxx (default): the library's C++ path behind "
                          "the C-ABI (mfgpu_vmult_dist: RCCL send/recv on a side stream, overlapped with pass 2); the "
                          "others: the Python test double pymfgpu/parallel.py over torch.distributed")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--kernel", default="auto", choices=["auto", "pencils", "pencils_x", "planes", "planes_2w"],
                     help="mfgpu_desc.kernel: cell-loop kernel family (measurements; the default is the library's choice)")
     ap.add_argument("--segments", type=int, default=0,
@@ -156,7 +181,7 @@ def main():
     ap.add_argument("--renumber", action="store_true",
                     help="second line, NOT the headline: renumber the mesh's dofs batch-major first (mfgpu_suggest_renumbering, "
                          "the MatrixFree::renumber_dofs analogue); the reference and the default run keep the caller's numbering")
-    ap.add_argument("--no-second-line", action="store_true", help="skip the renumbered second line of the default run")
+    ap.add_argument("--no-second-line", action="store_true", help="--full: skip the renumbered second line of the default run")
     ap.add_argument("--ball", type=int, default=-1, metavar="NREF",
                     help="bmop -DBALL_GRID: hyper_ball with NREF global refinements (unstructured, general-geometry path; 1 GPU)")
     args = ap.parse_args()
@@ -310,44 +335,64 @@ def main():
 
     def renorm():
         # the un-normalised protocol overflows double after ~100 applies (values grow by ||A|| per
-        # apply); rescale OUTSIDE the timed region so warm-up + profile legs never hit inf
+        # apply); rescale so warm-up + profile legs never hit inf (in the timed region: see `every` below)
         nonlocal dst
-        m = dst.abs().max()
+        m = torch.linalg.vector_norm(dst, float("inf"))  # == dst.abs().max(), without the temporary
         if world > 1:
             dist.all_reduce(m, op=dist.ReduceOp.MAX)
         dst.mul_(0.1 / m)
+        return m  # the max before the rescale (0.1 after it)
 
     # Clock ramp.  The GPU idles while the host builds mesh and plan; its power management then takes ~0.1-0.3 s of load
     # to reach the sustained clocks (C2: 0.153-0.159 ms per vmult for 100 applies right after set-up, 0.137-0.140 after
     # 2000 untimed applies).  The same K applies timed cold, right now, are reported as
-    # config.cold_start; then --ramp-steps untimed applies (renormalised every 50: the un-normalised protocol
-    # overflows after ~100), then the contract's W warm-up and K timed steps.  Same counts on every rank.
+    # config.cold_start (--full; a plain run applies them untimed, so both compute the same); then --ramp-steps untimed
+    # applies (renormalised every 50: the un-normalised protocol overflows after ~100), then the contract's W warm-up and
+    # K timed steps.  Same counts on every rank.
     cold_ms = None
+    window = None  # (max of dst, n): n applies grew a vector of max 0.1 to that max, the last such span before timing
     if args.ramp_steps > 0:
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        tc = time.perf_counter()
+        if args.full:
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            tc = time.perf_counter()
         n_cold = min(args.steps, 100)
         for _ in range(n_cold):
             step()
-        torch.cuda.synchronize()
-        cold_ms = (time.perf_counter() - tc) / n_cold * 1e3
+        if args.full:
+            torch.cuda.synchronize()
+            cold_ms = (time.perf_counter() - tc) / n_cold * 1e3
         renorm()
         for i in range(args.ramp_steps):
             step()
             if i % 50 == 49:
-                renorm()
+                window = (renorm(), 50)
         renorm()
     for _ in range(args.warmup):
         step()
-    renorm()
+    m = renorm()
+    if args.warmup > 0:
+        window = (m, args.warmup)
+    # Rescaling in the timed region.  An apply multiplies the values by up to the operator's largest eigenvalue g (~2.6
+    # per apply at the default size), so K timed applies overflow once 0.1 g^K leaves the number type's range (double:
+    # ~740 applies, float: ~90), and the last step's output would be inf.  The input of every `every`-th timed apply
+    # is rescaled as renorm() does (a reduction and a scale on the stream, no host synchronisation; the output of the
+    # last step is a plain apply).  `every` keeps a factor 2 in the exponent over the growth measured just before
+    # timing; without a long ramp the vector is not near the top eigenvector yet, and 50 per apply is assumed.
+    # K <= every (the default K = 100 in double, every ~370): no rescaling, the timed loop is the plain protocol.
+    g = 2.0 if window is None else max(2.0, (float(window[0]) / 0.1) ** (1.0 / window[1]))
+    if window is None or args.ramp_steps < 1000:
+        g = max(g, 50.0)
+    every = max(1, int(math.log(torch.finfo(tdt).max * 1e-3 / 0.1) / math.log(g) / 2))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i and i % every == 0:
+            renorm()
         step()
     torch.cuda.synchronize()
     if world > 1:
@@ -360,59 +405,63 @@ def main():
     t = float(tt.item())
     finite = bool(torch.isfinite(dst).all().item())
 
-    # ---- roofline leg: per-launch HIP-event timing of the cell-loop kernel on the launch stream
-    # In the state the timed region ran in: a first pass creates the handle's events (host work between the launches,
-    # and the host synchronisations above, let the clocks sag: 20 launches measured right here read 112-121 us where the
-    # steady state is 96-98), then untimed applies back to the steady state, then the measured launches with nothing
-    # but the event records between them.
-    n_prof = min(args.steps, 50)
-
-    def apply_local(count):
-        nonlocal dst, src
-        for i in range(count):
-            dst, src = src, dst
-            op.vmult(dst, src, stream)
-            if i % 50 == 49:
-                dst.mul_(0.1 / dst.abs().max())
-
-    renorm()
-    op.profile_enable(True)
-    apply_local(n_prof)
-    op.profile_read()
-    op.profile_read_pass2()
-    op.profile_enable(False)
-    renorm()
-    apply_local(min(args.ramp_steps, 500))
-    renorm()
-    op.profile_enable(True)
-    apply_local(n_prof)
-    k_ms, n_v = op.profile_read()
-    p2_ms = op.profile_read_pass2()
-    op.profile_enable(False)
-    launches = n_v * stats["n_launches"]
+    if args.dump_outputs:  # what the last timed step computed, before anything else touches dst
+        dump_outputs(args.dump_outputs, "dst" if world == 1 else f"dst_rank{rank}", dst, DUMP_BYTES // world)
     b_alg_loc = algorithmic_bytes(N_loc, mesh.n_cells, nd, s)
     general = bool(args.general_jacobian) or args.ball >= 0
     if general:  # per quadrature point: the 6 entries of the symmetric a JxW J J^T instead of one scalar
         b_alg_loc += mesh.n_cells * nd * 5 * s
-    achieved = b_alg_loc * n_v / (k_ms * 1e-3) / 1e9  # GB/s, == (B_alg/launch) / (avg launch duration)
-    # HBM traffic of the dominant kernel: NOT measured by this run (PMC counters need rocprofv3 passes of their own,
-    # tools/profile_bench.sh); copied from the committed summary of the last such passes IF it was taken on this
-    # workload, kernel and library source (hash of csrc/), else null.  `traffic_source` says where it came from.
-    traffic, traffic_step, traffic_source = None, None, None
-    tj = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tj):
-        try:
-            tr = json.load(open(tj))
-            if (tr.get("workload") == f"p{p}_3d_n{n_glob}_{'f32' if args.float else 'f64'}" and world == 1
-                    and op.kernel_name() + "<" in tr.get("kernel", "") and tr.get("csrc_sha16") == csrc_sha16()
-                    and not args.adaptive and not args.colored and not args.batch_cells and not args.batch_dofs
-                    and not general and args.kernel == "auto" and not args.renumber):
-                traffic = tr["hbm_bytes_per_launch"]
-                traffic_step = tr.get("step_hbm_bytes_per_vmult")
-                traffic_source = {"file": "profiles/traffic_latest.json", "profile": tr.get("profile"),
-                                  "csrc_sha16": tr.get("csrc_sha16")}
-        except Exception:
-            traffic = None
+
+    if args.full:
+        # ---- roofline leg: per-launch HIP-event timing of the cell-loop kernel on the launch stream
+        # In the state the timed region ran in: a first pass creates the handle's events (host work between the launches,
+        # and the host synchronisations above, let the clocks sag: 20 launches measured right here read 112-121 us where the
+        # steady state is 96-98), then untimed applies back to the steady state, then the measured launches with nothing
+        # but the event records between them.
+        n_prof = min(args.steps, 50)
+
+        def apply_local(count):
+            nonlocal dst, src
+            for i in range(count):
+                dst, src = src, dst
+                op.vmult(dst, src, stream)
+                if i % 50 == 49:
+                    dst.mul_(0.1 / dst.abs().max())
+
+        renorm()
+        op.profile_enable(True)
+        apply_local(n_prof)
+        op.profile_read()
+        op.profile_read_pass2()
+        op.profile_enable(False)
+        renorm()
+        apply_local(min(args.ramp_steps, 500))
+        renorm()
+        op.profile_enable(True)
+        apply_local(n_prof)
+        k_ms, n_v = op.profile_read()
+        p2_ms = op.profile_read_pass2()
+        op.profile_enable(False)
+        launches = n_v * stats["n_launches"]
+        achieved = b_alg_loc * n_v / (k_ms * 1e-3) / 1e9  # GB/s, == (B_alg/launch) / (avg launch duration)
+        # HBM traffic of the dominant kernel: NOT measured by this run (PMC counters need rocprofv3 passes of their own,
+        # tools/profile_bench.sh); copied from the committed summary of the last such passes IF it was taken on this
+        # workload, kernel and library source (hash of csrc/), else null.  `traffic_source` says where it came from.
+        traffic, traffic_step, traffic_source = None, None, None
+        tj = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if os.path.exists(tj):
+            try:
+                tr = json.load(open(tj))
+                if (tr.get("workload") == f"p{p}_3d_n{n_glob}_{'f32' if args.float else 'f64'}" and world == 1
+                        and op.kernel_name() + "<" in tr.get("kernel", "") and tr.get("csrc_sha16") == csrc_sha16()
+                        and not args.adaptive and not args.colored and not args.batch_cells and not args.batch_dofs
+                        and not general and args.kernel == "auto" and not args.renumber):
+                    traffic = tr["hbm_bytes_per_launch"]
+                    traffic_step = tr.get("step_hbm_bytes_per_vmult")
+                    traffic_source = {"file": "profiles/traffic_latest.json", "profile": tr.get("profile"),
+                                      "csrc_sha16": tr.get("csrc_sha16")}
+            except Exception:
+                traffic = None
 
     out = {
         "metric": f"DoFs/s on {args.steps}x Laplace vmult (bmop), p={p} 3D uniform",
@@ -444,24 +493,28 @@ def main():
                    "plan": stats, "finite": finite,
                    # the same K applies timed right after set-up, before the clock ramp (rank 0's clock; not the headline)
                    "clock_ramp_steps": args.ramp_steps,
+                   # timed applies between rescales of the input (null: none, K <= the interval)
+                   "timed_rescale_every": every if every < args.steps else None,
                    "cold_start": None if cold_ms is None else
                    {"ms_per_step": cold_ms, "value": n_dofs_glob / (cold_ms * 1e-3), "steps": min(args.steps, 100)}},
+    }
+    if args.full:
         # `achieved` / `frac`: the dominant kernel (the cell loop), algorithmic bytes per launch over its average launch
         # duration, as the bench contract defines it.  Pass 2 writes the shared and constrained dofs, so the cell loop alone
         # does not move all of B_alg: `vmult_frac` divides by the time of ALL kernels of a vmult (cell loop + pass 2, HIP
         # events on the launch stream), `step_frac` by ms_per_step.  `traffic`: PMC bytes of the cell-loop kernel per launch,
         # `traffic_step`: of all kernels of a vmult.
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "vmult_achieved": b_alg_loc * n_v / ((k_ms + p2_ms) * 1e-3) / 1e9,
-                     "vmult_frac": b_alg_loc * n_v / ((k_ms + p2_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "step_frac": b_alg_loc / (1e-3 * (1e3 * t / args.steps)) / 1e9 / HBM_PEAK_GBS,
-                     "traffic": traffic, "traffic_step": traffic_step, "traffic_source": traffic_source,
-                     "kernel": op.kernel_name(), "launches": launches,
-                     "avg_launch_us": 1e3 * k_ms / max(launches, 1),
-                     "alg_bytes_per_launch": b_alg_loc / stats["n_launches"],
-                     "kernel_ms_per_vmult": k_ms / max(n_v, 1), "pass2_ms_per_vmult": p2_ms / max(n_v, 1)},
-    }
-    if rank == 0 and world == 1 and not args.no_cpu and not args.adaptive and not general and not args.renumber:
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS,
+                           "vmult_achieved": b_alg_loc * n_v / ((k_ms + p2_ms) * 1e-3) / 1e9,
+                           "vmult_frac": b_alg_loc * n_v / ((k_ms + p2_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "step_frac": b_alg_loc / (1e-3 * (1e3 * t / args.steps)) / 1e9 / HBM_PEAK_GBS,
+                           "traffic": traffic, "traffic_step": traffic_step, "traffic_source": traffic_source,
+                           "kernel": op.kernel_name(), "launches": launches,
+                           "avg_launch_us": 1e3 * k_ms / max(launches, 1),
+                           "alg_bytes_per_launch": b_alg_loc / stats["n_launches"],
+                           "kernel_ms_per_vmult": k_ms / max(n_v, 1), "pass2_ms_per_vmult": p2_ms / max(n_v, 1)}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.adaptive and not general and not args.renumber:
         cb, n_cpu, y_cpu = cpu_baseline(args)
         out["cpu_baseline"] = cb
         if n_cpu == n_glob and not args.float:
@@ -472,8 +525,8 @@ def main():
             torch.cuda.synchronize()
             y_gpu = dst.cpu().numpy()
             out["gpu_vs_cpu_rel_l2"] = float(np.linalg.norm(y_gpu - y_cpu) / np.linalg.norm(y_cpu))
-    if (rank == 0 and world == 1 and not args.no_second_line and not args.renumber and not args.adaptive and not general
-            and not args.colored):
+    if (args.full and rank == 0 and world == 1 and not args.no_second_line and not args.renumber and not args.adaptive
+            and not general and not args.colored):
         # SECOND line, not the headline: the same workload after the optional batch-major dof renumbering
         # (mfgpu_suggest_renumbering, the MatrixFree::renumber_dofs analogue the reference does not use).  `value`
         # above is measured in the caller's numbering.

@@ -10,7 +10,7 @@ for i in 1 2 3; do
   for which in prev cur; do
     if [ $which = prev ]; then export MFGPU_LIB=$R/dealii-cuda_amd/lib/libmfgpu_prev.so; else unset MFGPU_LIB; fi
     echo "== $which" >> $OUT
-    python3 $R/bench.py --no-cpu --no-second-line "$@" 2>/dev/null | tail -1 >> $OUT
+    python3 $R/bench.py --full --no-cpu --no-second-line "$@" 2>/dev/null | tail -1 >> $OUT
   done
 done
 python3 - $OUT <<'PY'

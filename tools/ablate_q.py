@@ -82,7 +82,7 @@ def run():
     for name in ["full"] + list(VARIANTS):
         lib = os.path.join(R, "dealii-cuda_amd", "lib", "libmfgpu.so" if name == "full" else f"libmfgpu_ablq_{name}.so")
         env = dict(os.environ, MFGPU_LIB=lib)
-        out = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--steps", "30", "--warmup", "3", "--no-cpu",
+        out = subprocess.run([sys.executable, os.path.join(R, "bench.py"), "--full", "--steps", "30", "--warmup", "3", "--no-cpu",
                               "--no-second-line", "--kernel", "planes_2w"] + sys.argv[2:], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True).stdout
         m = re.search(r'"avg_launch_us": ([0-9.]+)', out)
         print(f"{name:10s} avg_launch_us {m.group(1) if m else '??'}", flush=True)
