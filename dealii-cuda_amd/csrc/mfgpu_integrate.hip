@@ -1,0 +1,698 @@
+// Cell integrals of a Poisson solve (include/mfgpu.h, "integrator"): the load vector with the Dirichlet lift of
+// poisson.cu:182-221 and the L2 error of VectorTools::integrate_difference(..., QGauss(p+2), L2_norm),
+// poisson.cu:277-292.  Double only (the reference's poisson uses `typedef double number`).
+//
+// Structure: one wave64 workgroup per cell; every per-point array is cell-major, so a wave reads its cell contiguously.
+// Inside the cell all tensor work is sum-factorised in LDS (tpass: one 1D contraction along one direction; a thread owns
+// output entries).  Hanging-node resolution is the 1D pencil pass of mfgpu_cell.h (hn_pencil / hn_flag2 / hn_flag3) on
+// LDS pencils, in the order of oracle/mf_oracle.py hn_resolve.
+//   rhs:   cell kernel -> per-cell local vectors (scratch) -> per-dof gather over a host-built CSR (dof -> cell-major
+//          local index, ascending), constrained and unreferenced dofs 0.  No atomics: bitwise repeatable.
+//   error: cell kernel -> squared cell errors -> the two-stage fixed-order reduction of mfgpu_vec_dot.
+// Geometry at the (p+2)^dim error points is interpolated from the description's QGauss(p+1) points with the 1D Lagrange
+// basis on those points (values and derivatives): exact for mappings of degree <= p per direction (affine cells,
+// MappingQ1, i.e. all mesh stand-ins).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mfgpu_cell.h"
+
+using namespace mfgpu;
+
+namespace {
+
+constexpr int cpow(int a, int e) { return e == 0 ? 1 : a * cpow(a, e - 1); }
+
+// 1D tables (row-major [out][in]), one device array, copied to LDS by every workgroup
+template <int N>
+struct Tab {
+  static constexpr int M = N + 1;
+  static constexpr int SE = 0;              // [q][i] = phi_i(x_q)      nodal -> QGauss(N) values
+  static constexpr int GE = SE + N * N;     // [q][i] = phi_i'(x_q)     nodal -> QGauss(N) derivatives
+  static constexpr int SI = GE + N * N;     // [i][q] = phi_i(x_q)      integration of values
+  static constexpr int GI = SI + N * N;     // [i][q] = phi_i'(x_q)     integration against derivatives
+  static constexpr int E = GI + N * N;      // [k][i] = phi_i(y_k)      nodal -> QGauss(M) values
+  static constexpr int LV = E + M * N;      // [k][q] = L_q(y_k)        Lagrange basis on QGauss(N) points
+  static constexpr int LD = LV + M * N;     // [k][q] = L_q'(y_k)
+  static constexpr int WM = LD + M * N;     // [k]    QGauss(M) weights on [0,1]
+  static constexpr int W = WM + M;          // [i][j] hanging-node weights
+  static constexpr int size = W + N * N;
+};
+
+struct IntArgs {
+  const uint32_t *loc2glob;  // [n_cells * N^dim]
+  const uint32_t *cmask;     // [n_cells] or nullptr
+  const double *tab;         // Tab<N>
+  const double *qpts;        // [n_cells * N^dim * dim]
+  const double *jxw;         // [n_cells * N^dim]
+  const double *metric;      // uniform: [cell][q] a J0^2 JxW; general: [cell][e][q] symmetric a JxW J^-1 J^-T
+  int general;
+  // rhs
+  const double *f_qp, *u_b;
+  double *local;  // [n_cells * N^dim]
+  // error
+  const double *u, *exact;
+  double *per_cell;
+  double *points;  // error_points
+  uint32_t n_cells;
+};
+
+// ---- Solution<dim> (poisson_common.cc:5-175) and RightHandSide<dim> (poisson_common.h:277-296), in double
+template <int dim>
+__device__ __forceinline__ double center(int i, int d) {
+  if (dim == 2) {
+    constexpr double c[3][2] = {{-0.5, +0.5}, {-0.5, -0.5}, {+0.5, -0.5}};
+    return c[i][d];
+  }
+  constexpr double c[3][3] = {{-0.5, +0.5, 0.25}, {-0.6, -0.5, -0.125}, {+0.5, -0.5, 0.5}};
+  return c[i][d];
+}
+
+template <int dim>
+__device__ __forceinline__ double sol_norm() {
+  const double s = sqrt(2 * M_PI) * (1. / 3.);
+  return dim == 2 ? s * s : s * s * s;
+}
+
+template <int dim>
+__device__ double solution_value(const double (&x)[dim]) {
+  const double w = 1. / 3.;
+  double r = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double n2 = 0;
+#pragma unroll
+    for (int d = 0; d < dim; ++d) {
+      const double t = x[d] - center<dim>(i, d);
+      n2 += t * t;
+    }
+    r += exp(-n2 / (w * w));
+  }
+  return r / sol_norm<dim>();
+}
+
+template <int dim>
+__device__ double rhs_value(const double (&x)[dim]) {
+  const double w = 1. / 3.;
+  double lap = 0, grad[dim], xx = 0;
+#pragma unroll
+  for (int d = 0; d < dim; ++d) {
+    grad[d] = 0;
+    xx += x[d] * x[d];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double t[dim], n2 = 0;
+#pragma unroll
+    for (int d = 0; d < dim; ++d) {
+      t[d] = x[d] - center<dim>(i, d);
+      n2 += t[d] * t[d];
+    }
+    const double e = exp(-n2 / (w * w));
+    lap += (-2 * dim + 4 * n2 / (w * w)) / (w * w) * e;
+#pragma unroll
+    for (int d = 0; d < dim; ++d) grad[d] += -2 / (w * w) * e * t[d];
+  }
+  lap /= sol_norm<dim>();
+  // Coefficient<dim>::value / ::gradient (poisson_common.h:146-170)
+  const double a = 1. / (0.05 + 2. * xx);
+  const double den = 0.05 + 2. * xx;
+  double ga_gu = 0;
+#pragma unroll
+  for (int d = 0; d < dim; ++d) ga_gu += (4. / (den * den)) * (-x[d]) * (grad[d] / sol_norm<dim>());
+  return -(lap * a + ga_gu);
+}
+
+// ---- sum factorisation in LDS
+// out = M (NB x NA) applied along direction `dir` of `in` (extents E0, E1, E2, x fastest; E_dir == NA)
+template <int dir, int NA, int NB, int E0, int E1, int E2>
+__device__ __forceinline__ void tpass(const double *__restrict__ in, double *__restrict__ out,
+                                      const double *__restrict__ M) {
+  constexpr int O0 = dir == 0 ? NB : E0, O1 = dir == 1 ? NB : E1, O2 = dir == 2 ? NB : E2;
+  constexpr int stride = dir == 0 ? 1 : dir == 1 ? E0 : E0 * E1;
+  for (int t = threadIdx.x; t < O0 * O1 * O2; t += 64) {
+    const int x = t % O0, y = (t / O0) % O1, z = t / (O0 * O1);
+    const int k = dir == 0 ? x : dir == 1 ? y : z;
+    const double *src = in + (dir == 0 ? 0 : x) + E0 * ((dir == 1 ? 0 : y) + E1 * (dir == 2 ? 0 : z));
+    double s = 0;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) s = fma(M[k * NA + i], src[i * stride], s);
+    out[t] = s;
+  }
+  __syncthreads();
+}
+
+// out = (Mz x My x Mx) in, NA^dim -> NB^dim, through the temporaries t1, t2 (NB^dim each)
+template <int dim, int NA, int NB>
+__device__ __forceinline__ void tensor(const double *in, double *out, const double *Mx, const double *My,
+                                       const double *Mz, double *t1, double *t2) {
+  __syncthreads();
+  if constexpr (dim == 2) {
+    tpass<0, NA, NB, NA, NA, 1>(in, t1, Mx);
+    tpass<1, NA, NB, NB, NA, 1>(t1, out, My);
+  } else {
+    tpass<0, NA, NB, NA, NA, NA>(in, t1, Mx);
+    tpass<1, NA, NB, NB, NA, NA>(t1, t2, My);
+    tpass<2, NA, NB, NB, NB, NA>(t2, out, Mz);
+  }
+}
+
+// resolve_hanging_nodes on the LDS values of one cell, directions x, y(, z) in that order (hn_resolve)
+template <int dim, int N, bool TR, int dir>
+__device__ __forceinline__ void hn_dir(double *v, unsigned mask, const double *W) {
+  constexpr int d1 = (dir + 1) % 3, d2 = (dir + 2) % 3;
+  for (int t = threadIdx.x; t < cpow(N, dim - 1); t += 64) {
+    bool type = false, flag;
+    int base;
+    if constexpr (dim == 3) {
+      const int a = t % N, b = t / N;
+      flag = hn_flag3<N, dir>(mask, a, b, type);
+      base = a * cpow(N, d1) + b * cpow(N, d2);
+    } else {
+      flag = hn_flag2<N, dir>(mask, t, type);
+      base = t * cpow(N, 1 - dir);
+    }
+    if (flag) {
+      double p[N];
+#pragma unroll
+      for (int i = 0; i < N; ++i) p[i] = v[base + i * cpow(N, dir)];
+      hn_pencil<N, double, TR>(W, type, p);
+#pragma unroll
+      for (int i = 0; i < N; ++i) v[base + i * cpow(N, dir)] = p[i];
+    }
+  }
+  __syncthreads();
+}
+
+template <int dim, int N, bool TR>
+__device__ __forceinline__ void hn_resolve(double *v, unsigned mask, const double *W) {
+  __syncthreads();
+  hn_dir<dim, N, TR, 0>(v, mask, W);
+  hn_dir<dim, N, TR, 1>(v, mask, W);
+  if constexpr (dim == 3) hn_dir<dim, N, TR, 2>(v, mask, W);
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+
+template <int N>
+__device__ __forceinline__ void load_tab(double *tab, const double *g) {
+  for (int i = threadIdx.x; i < Tab<N>::size; i += 64) tab[i] = g[i];
+}
+
+// rhs_i = int phi_i f - int grad phi_i . a grad u_b  (poisson.cu:198-214), hanging-node TRANSPOSE, to a.local
+template <int dim, int N>
+__global__ void __launch_bounds__(64) rhs_cell_kernel(IntArgs a) {
+  constexpr int ND = cpow(N, dim);
+  using TB = Tab<N>;
+  __shared__ double tab[TB::size], A[ND], G[dim * ND], F[ND], LOC[ND], TO[ND], T1[ND], T2[ND];
+  const uint32_t c = blockIdx.x;
+  const size_t c0 = (size_t)c * ND;
+  load_tab<N>(tab, a.tab);
+  const unsigned mask = a.cmask ? a.cmask[c] : 0u;
+  for (int q = threadIdx.x; q < ND; q += 64) {
+    double f;
+    if (a.f_qp) {
+      f = a.f_qp[c0 + q];
+    } else {
+      double x[dim];
+#pragma unroll
+      for (int d = 0; d < dim; ++d) x[d] = a.qpts[(c0 + q) * dim + d];
+      f = rhs_value<dim>(x);
+    }
+    F[q] = f * a.jxw[c0 + q];
+    if (a.u_b) A[q] = a.u_b[a.loc2glob[c0 + q]];
+  }
+  const double *S = tab + TB::SE, *D = tab + TB::GE, *SI = tab + TB::SI, *GI = tab + TB::GI;
+  tensor<dim, N, N>(F, LOC, SI, SI, SI, T1, T2);
+  if (a.u_b) {
+    if (mask) hn_resolve<dim, N, false>(A, mask, tab + TB::W);
+    // reference gradients at the quadrature points
+#pragma unroll
+    for (int e = 0; e < dim; ++e) tensor<dim, N, N>(A, G + e * ND, e == 0 ? D : S, e == 1 ? D : S, e == 2 ? D : S, T1, T2);
+    // flux in reference coordinates: a J0^2 JxW g, or (a JxW J^-1 J^-T) g
+    for (int q = threadIdx.x; q < ND; q += 64) {
+      if (!a.general) {
+        const double m = a.metric[c0 + q];
+#pragma unroll
+        for (int e = 0; e < dim; ++e) G[e * ND + q] *= m;
+      } else if (dim == 3) {
+        const double *m = a.metric + c0 * 6 + q;
+        const double g0 = G[q], g1 = G[ND + q], g2 = G[2 * ND + q];
+        const double m00 = m[0], m01 = m[ND], m02 = m[2 * ND], m11 = m[3 * ND], m12 = m[4 * ND], m22 = m[5 * ND];
+        G[q] = m00 * g0 + m01 * g1 + m02 * g2;
+        G[ND + q] = m01 * g0 + m11 * g1 + m12 * g2;
+        G[2 * ND + q] = m02 * g0 + m12 * g1 + m22 * g2;
+      } else {
+        const double *m = a.metric + c0 * 3 + q;
+        const double g0 = G[q], g1 = G[ND + q];
+        const double m00 = m[0], m01 = m[ND], m11 = m[2 * ND];
+        G[q] = m00 * g0 + m01 * g1;
+        G[ND + q] = m01 * g0 + m11 * g1;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < dim; ++e) {
+      tensor<dim, N, N>(G + e * ND, TO, e == 0 ? GI : SI, e == 1 ? GI : SI, e == 2 ? GI : SI, T1, T2);
+      for (int i = threadIdx.x; i < ND; i += 64) LOC[i] -= TO[i];
+    }
+  }
+  if (mask) hn_resolve<dim, N, true>(LOC, mask, tab + TB::W);
+  __syncthreads();
+  for (int i = threadIdx.x; i < ND; i += 64) a.local[c0 + i] = LOC[i];
+}
+
+// rhs[dof] = sum of the dof's local entries in ascending (cell, local index) order; empty ranges (constrained or
+// unreferenced dofs) give 0
+__global__ void __launch_bounds__(256) rhs_gather_kernel(double *__restrict__ rhs, const double *__restrict__ local,
+                                                         const uint32_t *__restrict__ off,
+                                                         const uint32_t *__restrict__ idx, uint32_t n_dofs) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_dofs) return;
+  double s = 0;
+  for (uint32_t j = off[i]; j < off[i + 1]; ++j) s += local[idx[j]];
+  rhs[i] = s;
+}
+
+// x (into X, dim x M^dim) and |det J| (into DET) at the error points of the cell whose QGauss(N) points are in Q
+template <int dim, int N>
+__device__ __forceinline__ void geometry(const double *tab, const double *Q, double *X, double *C1, double *DET,
+                                         double *TO, double *T1, double *T2) {
+  constexpr int ND = cpow(N, dim), M = N + 1, MD = cpow(M, dim);
+  using TB = Tab<N>;
+  const double *V = tab + TB::LV, *D = tab + TB::LD;
+  // columns 0 and 1 of J = dx / dxi
+#pragma unroll
+  for (int d = 0; d < dim; ++d) {
+    tensor<dim, N, M>(Q + d * ND, X + d * MD, D, V, V, T1, T2);
+    tensor<dim, N, M>(Q + d * ND, C1 + d * MD, V, D, V, T1, T2);
+  }
+  if constexpr (dim == 2) {
+    for (int k = threadIdx.x; k < MD; k += 64) DET[k] = fabs(X[k] * C1[MD + k] - X[MD + k] * C1[k]);
+  } else {
+    // det J = col2 . (col0 x col1); the cross product replaces col0 (the thread owns point k throughout)
+    for (int k = threadIdx.x; k < MD; k += 64) {
+      const double a0 = X[k], a1 = X[MD + k], a2 = X[2 * MD + k];
+      const double b0 = C1[k], b1 = C1[MD + k], b2 = C1[2 * MD + k];
+      X[k] = a1 * b2 - a2 * b1;
+      X[MD + k] = a2 * b0 - a0 * b2;
+      X[2 * MD + k] = a0 * b1 - a1 * b0;
+      DET[k] = 0;
+    }
+#pragma unroll
+    for (int d = 0; d < dim; ++d) {
+      tensor<dim, N, M>(Q + d * ND, TO, V, V, D, T1, T2);
+      for (int k = threadIdx.x; k < MD; k += 64) DET[k] += X[d * MD + k] * TO[k];
+    }
+    for (int k = threadIdx.x; k < MD; k += 64) DET[k] = fabs(DET[k]);
+  }
+#pragma unroll
+  for (int d = 0; d < dim; ++d) tensor<dim, N, M>(Q + d * ND, X + d * MD, V, V, V, T1, T2);
+  __syncthreads();
+}
+
+template <int dim, int N>
+__device__ __forceinline__ void load_qpts(double *Q, const double *qpts, uint32_t c) {
+  constexpr int ND = cpow(N, dim);
+  for (int t = threadIdx.x; t < ND * dim; t += 64) {
+    const int q = t / dim, d = t - q * dim;
+    Q[d * ND + q] = qpts[(size_t)c * ND * dim + t];
+  }
+}
+
+// squared L2 error of the cell on QGauss(N + 1) (VectorTools::integrate_difference, L2_norm)
+template <int dim, int N>
+__global__ void __launch_bounds__(64) l2_error_kernel(IntArgs a) {
+  constexpr int ND = cpow(N, dim), M = N + 1, MD = cpow(M, dim);
+  using TB = Tab<N>;
+  __shared__ double tab[TB::size], A[ND], U[MD], Q[dim * ND], X[dim * MD], C1[dim * MD], DET[MD], TO[MD], T1[MD],
+      T2[MD];
+  const uint32_t c = blockIdx.x;
+  const size_t c0 = (size_t)c * ND;
+  load_tab<N>(tab, a.tab);
+  for (int i = threadIdx.x; i < ND; i += 64) A[i] = a.u[a.loc2glob[c0 + i]];
+  load_qpts<dim, N>(Q, a.qpts, c);
+  const unsigned mask = a.cmask ? a.cmask[c] : 0u;
+  if (mask) hn_resolve<dim, N, false>(A, mask, tab + TB::W);
+  const double *E = tab + TB::E;
+  tensor<dim, N, M>(A, U, E, E, E, T1, T2);
+  geometry<dim, N>(tab, Q, X, C1, DET, TO, T1, T2);
+  double acc = 0;
+  for (int k = threadIdx.x; k < MD; k += 64) {
+    double ex;
+    if (a.exact) {
+      ex = a.exact[(size_t)c * MD + k];
+    } else {
+      double x[dim];
+#pragma unroll
+      for (int d = 0; d < dim; ++d) x[d] = X[d * MD + k];
+      ex = solution_value<dim>(x);
+    }
+    const int kx = k % M, ky = (k / M) % M, kz = k / (M * M);
+    double w = tab[TB::WM + kx] * tab[TB::WM + ky];
+    if (dim == 3) w *= tab[TB::WM + kz];
+    const double diff = U[k] - ex;
+    acc += diff * diff * (w * DET[k]);
+  }
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) a.per_cell[c] = acc;
+}
+
+template <int dim, int N>
+__global__ void __launch_bounds__(64) error_points_kernel(IntArgs a) {
+  constexpr int ND = cpow(N, dim), M = N + 1, MD = cpow(M, dim);
+  using TB = Tab<N>;
+  __shared__ double tab[TB::size], Q[dim * ND], X[dim * MD], C1[dim * MD], DET[MD], TO[MD], T1[MD], T2[MD];
+  const uint32_t c = blockIdx.x;
+  load_tab<N>(tab, a.tab);
+  load_qpts<dim, N>(Q, a.qpts, c);
+  geometry<dim, N>(tab, Q, X, C1, DET, TO, T1, T2);
+  for (int t = threadIdx.x; t < MD * dim; t += 64) {
+    const int k = t / dim, d = t - k * dim;
+    a.points[(size_t)c * MD * dim + t] = X[d * MD + k];
+  }
+}
+
+enum Which { RHS, L2, POINTS };
+
+template <int dim, int N>
+hipError_t launch_dn(Which w, const IntArgs &a, hipStream_t st) {
+  const dim3 grid(a.n_cells), block(64);
+  if (w == RHS) hipLaunchKernelGGL((rhs_cell_kernel<dim, N>), grid, block, 0, st, a);
+  if (w == L2) hipLaunchKernelGGL((l2_error_kernel<dim, N>), grid, block, 0, st, a);
+  if (w == POINTS) hipLaunchKernelGGL((error_points_kernel<dim, N>), grid, block, 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch(int dim, int n, Which w, const IntArgs &a, hipStream_t st) {
+#define CASE(N)                                                                      \
+  case N:                                                                            \
+    return dim == 2 ? launch_dn<2, N>(w, a, st) : launch_dn<3, N>(w, a, st);
+  switch (n) {
+    CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7)
+    default: return hipErrorInvalidValue;
+  }
+#undef CASE
+}
+
+// Gauss-Legendre points and weights on [0,1], ascending
+void gauss_01(int m, std::vector<double> &x, std::vector<double> &w) {
+  x.assign(m, 0.0);
+  w.assign(m, 0.0);
+  for (int i = 0; i < m; ++i) {
+    double z = std::cos(M_PI * (i + 0.75) / (m + 0.5)), dp = 1;
+    for (int it = 0; it < 100; ++it) {
+      double p0 = 1, p1 = z;
+      for (int k = 2; k <= m; ++k) {
+        const double p2 = ((2 * k - 1) * z * p1 - (k - 1) * p0) / k;
+        p0 = p1;
+        p1 = p2;
+      }
+      dp = m * (z * p1 - p0) / (z * z - 1);
+      const double dz = p1 / dp;
+      z -= dz;
+      if (std::fabs(dz) < 1e-16) break;
+    }
+    x[m - 1 - i] = 0.5 * (z + 1);
+    w[m - 1 - i] = 1.0 / ((1 - z * z) * dp * dp);  // 2 / ((1 - z^2) P'^2) on [-1,1], halved
+  }
+}
+
+// l[j] = L_j(y), dl[j] = L_j'(y) for the Lagrange basis on `nodes`
+void lagrange(const std::vector<double> &nodes, double y, std::vector<double> &l, std::vector<double> &dl) {
+  const int n = (int)nodes.size();
+  l.assign(n, 0.0);
+  dl.assign(n, 0.0);
+  for (int j = 0; j < n; ++j) {
+    double den = 1, v = 1, d = 0;
+    for (int k = 0; k < n; ++k) {
+      if (k == j) continue;
+      den *= nodes[j] - nodes[k];
+      v *= y - nodes[k];
+      double t = 1;
+      for (int m = 0; m < n; ++m)
+        if (m != j && m != k) t *= y - nodes[m];
+      d += t;
+    }
+    l[j] = v / den;
+    dl[j] = d / den;
+  }
+}
+
+#define HIP_TRY(expr)                                                  \
+  do {                                                                 \
+    hipError_t e_ = (expr);                                            \
+    if (e_ != hipSuccess) {                                            \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));    \
+      return e_ == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;    \
+    }                                                                  \
+  } while (0)
+
+template <typename P>
+int upload(P **dst, const void *src, size_t bytes) {
+  *dst = nullptr;
+  if (!bytes) return 0;
+  HIP_TRY(hipMalloc((void **)dst, bytes));
+  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+
+}  // namespace
+
+struct mfgpu_integrator {
+  int dim = 0, n = 0;
+  bool general = false;
+  uint32_t n_cells = 0, n_dofs = 0;
+  uint32_t *d_l2g = nullptr, *d_cmask = nullptr, *d_off = nullptr, *d_idx = nullptr;
+  double *d_tab = nullptr, *d_qpts = nullptr, *d_jxw = nullptr, *d_metric = nullptr;
+  double *d_local = nullptr, *d_err = nullptr, *d_ones = nullptr;
+};
+
+void mfgpu_integrator_destroy(mfgpu_integrator *it) {
+  if (!it) return;
+  hipFree(it->d_l2g);
+  hipFree(it->d_cmask);
+  hipFree(it->d_off);
+  hipFree(it->d_idx);
+  hipFree(it->d_tab);
+  hipFree(it->d_qpts);
+  hipFree(it->d_jxw);
+  hipFree(it->d_metric);
+  hipFree(it->d_local);
+  hipFree(it->d_err);
+  hipFree(it->d_ones);
+  delete it;
+}
+
+static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
+  const int dim = d.dim, n = d.degree + 1, m = n + 1;
+  const size_t nc = d.n_cells, nd = (size_t)ipow(n, dim);
+  it->dim = dim;
+  it->n = n;
+  it->n_cells = d.n_cells;
+  it->n_dofs = d.n_dofs;
+  it->general = !(d.flags & MFGPU_UNIFORM_J0);
+  const bool hn = (d.flags & MFGPU_HANGING_NODES) && d.constraint_mask;
+  // tables (layout Tab<N>)
+  const double *sv = (const double *)d.shape_values, *sg = (const double *)d.shape_gradients;
+  std::vector<double> xq, wq, ym, wm;
+  gauss_01(n, xq, wq);
+  gauss_01(m, ym, wm);
+  std::vector<double> tab;
+  for (int q = 0; q < n; ++q)
+    for (int i = 0; i < n; ++i) tab.push_back(sv[i * n + q]);
+  for (int q = 0; q < n; ++q)
+    for (int i = 0; i < n; ++i) tab.push_back(sg[i * n + q]);
+  tab.insert(tab.end(), sv, sv + n * n);
+  tab.insert(tab.end(), sg, sg + n * n);
+  std::vector<std::vector<double>> L(m), DL(m);
+  for (int k = 0; k < m; ++k) lagrange(xq, ym[k], L[k], DL[k]);
+  for (int k = 0; k < m; ++k)  // phi_i(y_k) = sum_q L_q(y_k) phi_i(x_q): the degree-p shape function through its values
+    for (int i = 0; i < n; ++i) {
+      double s = 0;
+      for (int q = 0; q < n; ++q) s += L[k][q] * sv[i * n + q];
+      tab.push_back(s);
+    }
+  for (int k = 0; k < m; ++k) tab.insert(tab.end(), L[k].begin(), L[k].end());
+  for (int k = 0; k < m; ++k) tab.insert(tab.end(), DL[k].begin(), DL[k].end());
+  tab.insert(tab.end(), wm.begin(), wm.end());
+  for (int i = 0; i < n * n; ++i) tab.push_back(hn ? d.constraint_weights[i] : 0.0);
+  int rc;
+  if ((rc = upload(&it->d_tab, tab.data(), tab.size() * 8))) return rc;
+  if ((rc = upload(&it->d_l2g, d.loc2glob, nc * nd * 4))) return rc;
+  if (hn && (rc = upload(&it->d_cmask, d.constraint_mask, nc * 4))) return rc;
+  if ((rc = upload(&it->d_qpts, d.quadrature_points, nc * nd * dim * 8))) return rc;
+  if ((rc = upload(&it->d_jxw, d.JxW, nc * nd * 8))) return rc;
+  // dof -> (cell, local index) CSR, constrained dofs left empty
+  std::vector<uint8_t> con(d.n_dofs, 0);
+  for (uint32_t i = 0; i < d.n_constrained; ++i) con[d.constrained_dofs[i]] = 1;
+  std::vector<uint32_t> off(d.n_dofs + 1, 0);
+  for (size_t j = 0; j < nc * nd; ++j)
+    if (!con[d.loc2glob[j]]) ++off[d.loc2glob[j] + 1];
+  for (uint32_t i = 0; i < d.n_dofs; ++i) off[i + 1] += off[i];
+  std::vector<uint32_t> idx(off[d.n_dofs]), pos(off.begin(), off.end() - 1);
+  for (size_t j = 0; j < nc * nd; ++j)
+    if (!con[d.loc2glob[j]]) idx[pos[d.loc2glob[j]]++] = (uint32_t)j;
+  if ((rc = upload(&it->d_off, off.data(), off.size() * 4))) return rc;
+  if ((rc = upload(&it->d_idx, idx.data(), idx.size() * 4))) return rc;
+  HIP_TRY(hipMalloc((void **)&it->d_local, nc * nd * 8));
+  HIP_TRY(hipMalloc((void **)&it->d_err, nc * 8));
+  std::vector<double> ones(nc, 1.0);
+  if ((rc = upload(&it->d_ones, ones.data(), nc * 8))) return rc;
+  // coefficient (given, or evaluated from the quadrature points) folded with JxW and the inverse Jacobian by the
+  // operator's own setup kernels (cell order = identity)
+  double *t_coef = nullptr, *t_j = nullptr;
+  uint32_t *t_order = nullptr;
+  auto cleanup = [&]() {
+    hipFree(t_coef);
+    hipFree(t_j);
+    hipFree(t_order);
+  };
+  std::vector<uint32_t> order(nc);
+  for (size_t c = 0; c < nc; ++c) order[c] = (uint32_t)c;
+  const size_t jac = it->general ? nd * dim * dim : 1;
+  const size_t mper = it->general ? (dim == 3 ? 6 : 3) : 1;
+  rc = upload(&t_order, order.data(), nc * 4);
+  if (!rc) rc = upload(&t_j, d.inv_jac, nc * jac * 8);
+  if (!rc && d.coefficient) rc = upload(&t_coef, d.coefficient, nc * nd * 8);
+  if (rc) {
+    cleanup();
+    return rc;
+  }
+  hipError_t e = hipSuccess;
+  if (!d.coefficient) {
+    e = hipMalloc((void **)&t_coef, nc * nd * 8);
+    if (e == hipSuccess) e = coefficient_launch<double>(t_coef, it->d_qpts, nc * nd, dim, nullptr);
+  }
+  if (e == hipSuccess) e = hipMalloc((void **)&it->d_metric, nc * nd * mper * 8);
+  if (e == hipSuccess)
+    e = !it->general ? fold_launch<double>(it->d_metric, t_coef, it->d_jxw, t_j, t_order, (uint32_t)nc, (uint32_t)nd, nullptr)
+        : dim == 3   ? fold_general_launch<double>(it->d_metric, t_coef, it->d_jxw, t_j, t_order, (uint32_t)nc, (uint32_t)nd, nullptr)
+                     : fold_general2_launch<double>(it->d_metric, t_coef, it->d_jxw, t_j, t_order, (uint32_t)nc, (uint32_t)nd, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  cleanup();
+  if (e != hipSuccess) {
+    set_error(std::string("integrator coefficient fold: ") + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;
+  }
+  return 0;
+}
+
+int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out) {
+  if (!desc || !out) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  *out = nullptr;
+  const mfgpu_desc &d = *desc;
+  if (d.number_type == MFGPU_F32) {
+    set_error("mfgpu_integrator: MFGPU_F64 only (the reference's poisson uses double)");
+    return MFGPU_EUNSUPPORTED;
+  }
+  if (d.number_type != MFGPU_F64) {
+    set_error("number_type must be MFGPU_F64");
+    return MFGPU_EINVAL;
+  }
+  if ((d.dim != 2 && d.dim != 3) || d.degree < 1 || d.degree > 6) {
+    set_error("mfgpu_integrator: dim 2 or 3, degree 1..6");
+    return MFGPU_EUNSUPPORTED;
+  }
+  if (!d.quadrature_points) {
+    set_error("mfgpu_integrator: quadrature_points are required (right-hand side, error-point geometry)");
+    return MFGPU_EINVAL;
+  }
+  if (!d.loc2glob || !d.JxW || !d.inv_jac || !d.shape_values || !d.shape_gradients || d.n_cells == 0 ||
+      (d.n_constrained && !d.constrained_dofs)) {
+    set_error("mfgpu_integrator: loc2glob, JxW, inv_jac, shape tables and cells are required");
+    return MFGPU_EINVAL;
+  }
+  if ((d.flags & MFGPU_HANGING_NODES) && (!d.constraint_mask || !d.constraint_weights)) {
+    set_error("MFGPU_HANGING_NODES needs constraint_mask and constraint_weights");
+    return MFGPU_EINVAL;
+  }
+  const size_t nd = (size_t)ipow(d.degree + 1, d.dim);
+  for (size_t j = 0; j < (size_t)d.n_cells * nd; ++j)
+    if (d.loc2glob[j] >= d.n_dofs) {
+      set_error("loc2glob entry out of range");
+      return MFGPU_EINVAL;
+    }
+  for (uint32_t i = 0; i < d.n_constrained; ++i)
+    if (d.constrained_dofs[i] >= d.n_dofs) {
+      set_error("constrained dof out of range");
+      return MFGPU_EINVAL;
+    }
+  mfgpu_integrator *it = new mfgpu_integrator();
+  const int rc = integrator_setup(it, d);
+  if (rc) {
+    mfgpu_integrator_destroy(it);
+    return rc;
+  }
+  *out = it;
+  return 0;
+}
+
+static IntArgs base_args(const mfgpu_integrator *it) {
+  IntArgs a{};
+  a.loc2glob = it->d_l2g;
+  a.cmask = it->d_cmask;
+  a.tab = it->d_tab;
+  a.qpts = it->d_qpts;
+  a.jxw = it->d_jxw;
+  a.metric = it->d_metric;
+  a.general = it->general ? 1 : 0;
+  a.n_cells = it->n_cells;
+  return a;
+}
+
+int mfgpu_integrator_rhs(mfgpu_integrator *it, void *rhs, const void *f_qp, const void *u_b, void *stream) {
+  if (!it || !rhs) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  IntArgs a = base_args(it);
+  a.f_qp = (const double *)f_qp;
+  a.u_b = (const double *)u_b;
+  a.local = it->d_local;
+  HIP_TRY(launch(it->dim, it->n, RHS, a, st));
+  hipLaunchKernelGGL(rhs_gather_kernel, dim3((it->n_dofs + 255) / 256), dim3(256), 0, st, (double *)rhs,
+                     (const double *)it->d_local, it->d_off, it->d_idx, it->n_dofs);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int mfgpu_integrator_l2_error(mfgpu_integrator *it, const void *u, const void *exact, void *per_cell, void *stream,
+                              double *l2) {
+  if (!it || !u || !l2) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  IntArgs a = base_args(it);
+  a.u = (const double *)u;
+  a.exact = (const double *)exact;
+  a.per_cell = per_cell ? (double *)per_cell : it->d_err;
+  HIP_TRY(launch(it->dim, it->n, L2, a, st));
+  double sum = 0;
+  HIP_TRY(vec_reduce_launch<double>(0, a.per_cell, nullptr, it->d_ones, 0.0, it->n_cells, st, &sum));
+  *l2 = std::sqrt(sum);
+  return 0;
+}
+
+int mfgpu_integrator_error_points(mfgpu_integrator *it, void *points, void *stream) {
+  if (!it || !points) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  IntArgs a = base_args(it);
+  a.points = (double *)points;
+  HIP_TRY(launch(it->dim, it->n, POINTS, a, (hipStream_t)stream));
+  return 0;
+}

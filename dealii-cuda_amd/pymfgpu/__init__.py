@@ -58,6 +58,8 @@ SYMBOLS = [
     "mfgpu_level_destroy", "mfgpu_index_pairs_create", "mfgpu_vec_copy_pairs", "mfgpu_index_pairs_destroy",
     "mfgpu_mesh_create_adaptive_mg", "mfgpu_mg_hierarchy_create", "mfgpu_mg_n_levels", "mfgpu_mg_level_mesh",
     "mfgpu_mg_edge_dofs", "mfgpu_mg_copy_pairs", "mfgpu_mg_transfer_arrays", "mfgpu_mg_hierarchy_destroy",
+    "mfgpu_integrator_create", "mfgpu_integrator_rhs", "mfgpu_integrator_l2_error", "mfgpu_integrator_error_points",
+    "mfgpu_integrator_destroy",
 ]
 
 _lib = None
@@ -165,6 +167,13 @@ def lib():
         L.mfgpu_level_destroy.restype = None
         L.mfgpu_transfer_destroy.argtypes = [C.c_void_p]
         L.mfgpu_transfer_destroy.restype = None
+        L.mfgpu_integrator_create.argtypes = [C.POINTER(Desc), C.POINTER(C.c_void_p)]
+        L.mfgpu_integrator_rhs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mfgpu_integrator_l2_error.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_double)]
+        L.mfgpu_integrator_error_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mfgpu_integrator_destroy.argtypes = [C.c_void_p]
+        L.mfgpu_integrator_destroy.restype = None
         _lib = L
     return _lib
 
@@ -547,6 +556,47 @@ class Operator:
         ms = C.c_double()
         _check(lib().mfgpu_profile_read_pass2(self._h, C.byref(ms)))
         return ms.value
+
+
+class Integrator:
+    """Cell integrals of a Poisson solve (mfgpu_integrator_*): the load vector with the Dirichlet lift
+    (poisson.cu:182-221) and the L2 error on QGauss(p+2) (VectorTools::integrate_difference, poisson.cu:277-292).
+    Double only.  Vectors: DeviceVector or anything _ptr accepts; None = the built-in function / no lift."""
+
+    def __init__(self, desc: Desc, keep=None):
+        self._keep = keep
+        self.dim, self.degree, self.n_cells = int(desc.dim), int(desc.degree), int(desc.n_cells)
+        h = C.c_void_p()
+        _check(lib().mfgpu_integrator_create(C.byref(desc), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_integrator_destroy(self._h)
+            self._h = None
+
+    @property
+    def n_error_points(self):
+        """(p+2)^dim points per cell"""
+        return (self.degree + 2) ** self.dim
+
+    def rhs(self, dst, f=None, u_b=None, stream=None):
+        """dst = int phi_i f - int grad phi_i . a grad u_b; f: values at the quadrature points [n_cells * (p+1)^dim]"""
+        _check(lib().mfgpu_integrator_rhs(self._h, _ptr(dst), None if f is None else _ptr(f),
+                                          None if u_b is None else _ptr(u_b), stream))
+
+    def l2_error(self, u, exact=None, per_cell=None, stream=None):
+        """|u - exact|_L2; exact: values at the error points [n_cells * (p+2)^dim]; per_cell: squared cell errors"""
+        r = C.c_double()
+        _check(lib().mfgpu_integrator_l2_error(self._h, _ptr(u), None if exact is None else _ptr(exact),
+                                               None if per_cell is None else _ptr(per_cell), stream, C.byref(r)))
+        return r.value
+
+    def error_points(self):
+        """the error points of every cell on the host, [n_cells, (p+2)^dim, dim]"""
+        v = DeviceVector(self.n_cells * self.n_error_points * self.dim)
+        _check(lib().mfgpu_integrator_error_points(self._h, v.ptr, None))
+        return v.to_host().reshape(self.n_cells, self.n_error_points, self.dim)
 
 
 class MgHierarchy:

@@ -287,6 +287,35 @@ int mfgpu_index_pairs_create(const uint32_t *dst_idx, const uint32_t *src_idx, u
 int mfgpu_vec_copy_pairs(const mfgpu_index_pairs *p, void *dst_dev, const void *src_dev, int number_type, void *stream);
 void mfgpu_index_pairs_destroy(mfgpu_index_pairs *p);
 
+/* ---- cell integrals of a Poisson solve (poisson.cu:152-229, 277-292) ------------------------------------------
+ * A separate object created from the same description as the operator; it keeps its own device copy of the geometry
+ * (loc2glob, constraint mask, quadrature points, JxW, the folded coefficient) and leaves mfgpu_handle untouched.
+ * MFGPU_F64 only (MFGPU_F32: MFGPU_EUNSUPPORTED; the reference's poisson uses double); every (dim, degree) of
+ * mfgpu_create, uniform-J0 and general geometry, with and without hanging nodes.  quadrature_points are required
+ * (MFGPU_EINVAL without).  Geometry at the QGauss(p+2) error points is interpolated from the QGauss(p+1) quadrature
+ * points with the 1D Lagrange basis on those points: exact for mappings of degree <= p per direction (affine cells and
+ * MappingQ1, i.e. every mesh stand-in below), not for higher-order mappings.  No floating-point atomics: two calls on
+ * the same inputs give bitwise-equal results.  All vectors are device vectors of doubles.                          */
+typedef struct mfgpu_integrator mfgpu_integrator;
+int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out);
+/* poisson.cu:182-221: rhs_i = sum_cells int phi_i f - int grad phi_i . a grad u_b on the description's quadrature
+ * points, distributed like a cell result (transposed hanging-node resolution), constrained rows 0, every entry written.
+ * f_qp: [n_cells * (p+1)^dim] values at the quadrature points, or NULL = RightHandSide<dim> (poisson_common.h:277-296,
+ * which assumes the built-in coefficient).  u_b: read on every dof a cell references, constrained dofs included (unlike
+ * vmult), hanging-node interpolated as in the cell loop; NULL = no lift.  a = the description's coefficient or the
+ * built-in one, as mfgpu_create.  Asynchronous.                                                                   */
+int mfgpu_integrator_rhs(mfgpu_integrator *it, void *rhs, const void *f_qp, const void *u_b, void *stream);
+/* VectorTools::integrate_difference(..., QGauss(p+2), L2_norm), poisson.cu:277-292.  u in the operator's numbering;
+ * entries of hanging dofs are not read (values come through loc2glob + hanging-node interpolation).  exact:
+ * [n_cells * (p+2)^dim] values at the error points, or NULL = Solution<dim> (poisson_common.cc:5-175).  per_cell:
+ * [n_cells] squared cell errors, or NULL.  *l2 = sqrt(sum of the squared cell errors), fixed-order sum; blocks.     */
+int mfgpu_integrator_l2_error(mfgpu_integrator *it, const void *u, const void *exact, void *per_cell, void *stream,
+                              double *l2);
+/* the (p+2)^dim error points of every cell, [n_cells * (p+2)^dim * dim] (x, y, z per point, x fastest), so that a
+ * caller can supply `exact`.  Asynchronous.                                                                       */
+int mfgpu_integrator_error_points(mfgpu_integrator *it, void *points, void *stream);
+void mfgpu_integrator_destroy(mfgpu_integrator *it);
+
 /* ---- deal.II stand-in for the setup side (host only) --------------------------------------
  * Produces what Triangulation + DoFHandler + ConstraintMatrix + FEValues + ShapeInfo hand to
  * MatrixFreeGpu::reinit, for the meshes bmop uses (bmop_common.h:108-120).                    */
