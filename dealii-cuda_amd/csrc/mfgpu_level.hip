@@ -44,6 +44,14 @@ __global__ void copy_pairs_kernel(T *dst, const T *src, const uint32_t *di, cons
   if (i < n) dst[di[i]] = src[si[i]];
 }
 
+// copy_to_mg / copy_from_mg across number types (deal.II's OtherNumber): dst[di[i]] = (D) src[si[i]]
+template <typename D, typename S>
+__global__ void __launch_bounds__(256)
+copy_pairs_convert_kernel(D *dst, const S *src, const uint32_t *di, const uint32_t *si, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[di[i]] = (D)src[si[i]];
+}
+
 template <typename T>
 __global__ void set_indexed_kernel(T *v, const uint32_t *idx, uint32_t n, T value) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -191,6 +199,34 @@ int mfgpu_vec_copy_pairs(const mfgpu_index_pairs *p, void *dst, const void *src,
   else
     hipLaunchKernelGGL(copy_pairs_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float *)dst,
                        (const float *)src, p->d_dst, p->d_src, p->n);
+  return hipGetLastError() == hipSuccess ? 0 : MFGPU_EHIP;
+}
+
+int mfgpu_vec_copy_pairs_convert(const mfgpu_index_pairs *p, void *dst, int dst_type, const void *src, int src_type,
+                                 void *stream) {
+  if ((dst_type != MFGPU_F64 && dst_type != MFGPU_F32) || (src_type != MFGPU_F64 && src_type != MFGPU_F32)) {
+    mfgpu::set_error("mfgpu_vec_copy_pairs_convert: number type must be MFGPU_F64 or MFGPU_F32");
+    return MFGPU_EINVAL;
+  }
+  if (!p || !dst || !src) {
+    mfgpu::set_error("mfgpu_vec_copy_pairs_convert: null argument");
+    return MFGPU_EINVAL;
+  }
+  if (p->n == 0) return 0;
+  const unsigned grid = (p->n + 255) / 256;
+  const hipStream_t st = (hipStream_t)stream;
+#define CPC(D, S)                                                                                                  \
+  hipLaunchKernelGGL((copy_pairs_convert_kernel<D, S>), dim3(grid), dim3(256), 0, st, (D *)dst, (const S *)src, \
+                     p->d_dst, p->d_src, p->n)
+  if (dst_type == MFGPU_F64 && src_type == MFGPU_F64)
+    CPC(double, double);
+  else if (dst_type == MFGPU_F64)
+    CPC(double, float);
+  else if (src_type == MFGPU_F64)
+    CPC(float, double);
+  else
+    CPC(float, float);
+#undef CPC
   return hipGetLastError() == hipSuccess ? 0 : MFGPU_EHIP;
 }
 

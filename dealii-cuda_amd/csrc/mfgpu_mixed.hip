@@ -1,0 +1,307 @@
+// Mixed-precision multigrid and the fused Chebyshev smoother (mixed precision).
+//   mfgpu_vec_convert            dst = (dst type) src between double and float vectors: the OtherNumber side of
+//                                deal.II's copy_to_mg / copy_from_mg (a float V-cycle under a double CG,
+//                                level_number in the reference's bmop_mg.cu:58-59 and poisson_mg.cu:51)
+//   mfgpu_vec_chebyshev_start    the vector updates of one PreconditionChebyshev sweep (host/mfgpu_shim_mg.h) in ONE
+//   mfgpu_vec_chebyshev_update   launch each instead of the BLAS-1 sequence r.add, t.equ, t.scale, upd.sadd, x.add
+// All kernels stream: grid-stride over 16-byte chunks per lane (2 doubles or 4 floats; 4 elements for the
+// conversion), a scalar loop for the tail (and for vectors that are not 16-byte aligned), no atomics, no LDS, every
+// element computed by one lane in a fixed order (deterministic).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mfgpu_internal.h"
+
+namespace {
+
+constexpr unsigned kBlocks = 2048;  // 256 CUs x 8 resident blocks of 256 threads, grid-stride (as mfgpu_aux.hip)
+
+template <typename T>
+constexpr int lanes16() {
+  return 16 / (int)sizeof(T);
+}
+
+template <typename T>
+__device__ __forceinline__ void ld16(const T *p, T (&v)[lanes16<T>()]) {
+  if constexpr (sizeof(T) == 8) {
+    const double2 a = *reinterpret_cast<const double2 *>(p);
+    v[0] = a.x;
+    v[1] = a.y;
+  } else {
+    const float4 a = *reinterpret_cast<const float4 *>(p);
+    v[0] = a.x;
+    v[1] = a.y;
+    v[2] = a.z;
+    v[3] = a.w;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void st16(T *p, const T (&v)[lanes16<T>()]) {
+  if constexpr (sizeof(T) == 8) {
+    *reinterpret_cast<double2 *>(p) = make_double2(v[0], v[1]);
+  } else {
+    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// four elements per chunk: one 16-byte access on the float side, two on the double side
+template <typename T>
+__device__ __forceinline__ void ld4(const T *p, T (&v)[4]) {
+  if constexpr (sizeof(T) == 8) {
+    T a[2], b[2];
+    ld16<T>(p, a);
+    ld16<T>(p + 2, b);
+    v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1];
+  } else {
+    ld16<T>(p, v);
+  }
+}
+template <typename T>
+__device__ __forceinline__ void st4(T *p, const T (&v)[4]) {
+  if constexpr (sizeof(T) == 8) {
+    const T a[2] = {v[0], v[1]}, b[2] = {v[2], v[3]};
+    st16<T>(p, a);
+    st16<T>(p + 2, b);
+  } else {
+    st16<T>(p, v);
+  }
+}
+
+// dst[i] = (D) src[i]; double -> float rounds to nearest even (overflow gives +-inf), float -> double is exact
+template <typename D, typename S, bool VEC>
+__global__ void __launch_bounds__(256) convert_kernel(D *__restrict__ dst, const S *__restrict__ src, size_t n) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (VEC) {
+    const size_t nc = n / 4;
+    for (size_t c = tid; c < nc; c += stride) {
+      S a[4];
+      D b[4];
+      ld4<S>(src + 4 * c, a);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) b[k] = (D)a[k];
+      st4<D>(dst + 4 * c, b);
+    }
+    done = nc * 4;
+  }
+  for (size_t i = done + tid; i < n; i += stride) dst[i] = (D)src[i];
+}
+
+// r = b - t (t == nullptr: r = b); upd = (f r) dinv; x = upd (ZERO) or x += upd.  The operations and their order are
+// those of the BLAS-1 sequence r.equ(1, b), r.add(-1, t), upd.equ(f, r), upd.scale(dinv), x.equ / x.add(1, upd).
+template <typename T, bool HAS_T, bool ZERO>
+__device__ __forceinline__ void cheb_start_elem(T &x, T &u, T &r, T b, T t, T d, T f) {
+  r = HAS_T ? b - t : b;
+  u = (f * r) * d;
+  x = ZERO ? u : x + u;
+}
+
+template <typename T, bool VEC, bool HAS_T, bool ZERO>
+__global__ void __launch_bounds__(256)
+cheb_start_kernel(T *__restrict__ x, T *__restrict__ upd, T *__restrict__ r, const T *__restrict__ b,
+                  const T *__restrict__ t, const T *__restrict__ dinv, T f, size_t n) {
+  constexpr int W = lanes16<T>();
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (VEC) {
+    const size_t nc = n / W;
+    for (size_t c = tid; c < nc; c += stride) {
+      const size_t o = c * W;
+      T xv[W], uv[W], rv[W], bv[W], tv[W], dv[W];
+      ld16<T>(b + o, bv);
+      if (HAS_T) ld16<T>(t + o, tv);
+      ld16<T>(dinv + o, dv);
+      if (!ZERO) ld16<T>(x + o, xv);
+#pragma unroll
+      for (int k = 0; k < W; ++k) cheb_start_elem<T, HAS_T, ZERO>(xv[k], uv[k], rv[k], bv[k], HAS_T ? tv[k] : T(0), dv[k], f);
+      st16<T>(r + o, rv);
+      st16<T>(upd + o, uv);
+      st16<T>(x + o, xv);
+    }
+    done = nc * W;
+  }
+  for (size_t i = done + tid; i < n; i += stride) {
+    T xi = ZERO ? T(0) : x[i], ui, ri;
+    cheb_start_elem<T, HAS_T, ZERO>(xi, ui, ri, b[i], HAS_T ? t[i] : T(0), dinv[i], f);
+    r[i] = ri;
+    upd[i] = ui;
+    x[i] = xi;
+  }
+}
+
+// r -= t; upd = f1 upd + (f2 r) dinv; x += upd  (r.add(-1, t), t.equ(f2, r), t.scale(dinv), upd.sadd(f1, 1, t),
+// x.add(1, upd) without the store and reload of t)
+template <typename T>
+__device__ __forceinline__ void cheb_update_elem(T &x, T &u, T &r, T t, T d, T f1, T f2) {
+  r = r - t;
+  u = f1 * u + (f2 * r) * d;
+  x = x + u;
+}
+
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256)
+cheb_update_kernel(T *__restrict__ x, T *__restrict__ upd, T *__restrict__ r, const T *__restrict__ t,
+                   const T *__restrict__ dinv, T f1, T f2, size_t n) {
+  constexpr int W = lanes16<T>();
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (VEC) {
+    const size_t nc = n / W;
+    for (size_t c = tid; c < nc; c += stride) {
+      const size_t o = c * W;
+      T xv[W], uv[W], rv[W], tv[W], dv[W];
+      ld16<T>(r + o, rv);
+      ld16<T>(t + o, tv);
+      ld16<T>(dinv + o, dv);
+      ld16<T>(upd + o, uv);
+      ld16<T>(x + o, xv);
+#pragma unroll
+      for (int k = 0; k < W; ++k) cheb_update_elem<T>(xv[k], uv[k], rv[k], tv[k], dv[k], f1, f2);
+      st16<T>(r + o, rv);
+      st16<T>(upd + o, uv);
+      st16<T>(x + o, xv);
+    }
+    done = nc * W;
+  }
+  for (size_t i = done + tid; i < n; i += stride) {
+    T xi = x[i], ui = upd[i], ri = r[i];
+    cheb_update_elem<T>(xi, ui, ri, t[i], dinv[i], f1, f2);
+    r[i] = ri;
+    upd[i] = ui;
+    x[i] = xi;
+  }
+}
+
+unsigned grid_for(size_t work) {
+  const size_t blocks = (work + 255) / 256;
+  return (unsigned)(blocks == 0 ? 1 : blocks > kBlocks ? kBlocks : blocks);
+}
+
+bool aligned16(const void *p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
+
+bool valid_type(int nt) { return nt == MFGPU_F64 || nt == MFGPU_F32; }
+
+int hip_status(const char *what) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return MFGPU_OK;
+  mfgpu::set_error(std::string(what) + ": " + hipGetErrorString(e));
+  return MFGPU_EHIP;
+}
+
+int einval(const char *msg) {
+  mfgpu::set_error(msg);
+  return MFGPU_EINVAL;
+}
+
+template <typename D, typename S>
+void convert_launch(D *dst, const S *src, size_t n, hipStream_t st) {
+  if (aligned16(dst) && aligned16(src))
+    hipLaunchKernelGGL((convert_kernel<D, S, true>), dim3(grid_for(n / 4 + n % 4)), dim3(256), 0, st, dst, src, n);
+  else
+    hipLaunchKernelGGL((convert_kernel<D, S, false>), dim3(grid_for(n)), dim3(256), 0, st, dst, src, n);
+}
+
+template <typename T>
+void cheb_start_launch(T *x, T *upd, T *r, const T *b, const T *t, const T *dinv, T f, bool zero, size_t n,
+                       hipStream_t st) {
+  const bool vec = aligned16(x) && aligned16(upd) && aligned16(r) && aligned16(b) && aligned16(t) && aligned16(dinv);
+  const unsigned g = grid_for(vec ? n / lanes16<T>() + n % lanes16<T>() : n);
+#define CHEB_START(VEC, HT, Z)                                                                                    \
+  hipLaunchKernelGGL((cheb_start_kernel<T, VEC, HT, Z>), dim3(g), dim3(256), 0, st, x, upd, r, b, t, dinv, f, n)
+  const int sel = (vec ? 4 : 0) + (t ? 2 : 0) + (zero ? 1 : 0);
+  switch (sel) {
+    case 0: CHEB_START(false, false, false); break;
+    case 1: CHEB_START(false, false, true); break;
+    case 2: CHEB_START(false, true, false); break;
+    case 3: CHEB_START(false, true, true); break;
+    case 4: CHEB_START(true, false, false); break;
+    case 5: CHEB_START(true, false, true); break;
+    case 6: CHEB_START(true, true, false); break;
+    default: CHEB_START(true, true, true); break;
+  }
+#undef CHEB_START
+}
+
+template <typename T>
+void cheb_update_launch(T *x, T *upd, T *r, const T *t, const T *dinv, T f1, T f2, size_t n, hipStream_t st) {
+  if (aligned16(x) && aligned16(upd) && aligned16(r) && aligned16(t) && aligned16(dinv))
+    hipLaunchKernelGGL((cheb_update_kernel<T, true>), dim3(grid_for(n / lanes16<T>() + n % lanes16<T>())), dim3(256), 0,
+                       st, x, upd, r, t, dinv, f1, f2, n);
+  else
+    hipLaunchKernelGGL((cheb_update_kernel<T, false>), dim3(grid_for(n)), dim3(256), 0, st, x, upd, r, t, dinv, f1, f2,
+                       n);
+}
+
+// the three written vectors must be distinct and must not be one of the read ones
+bool outputs_alias(const void *x, const void *upd, const void *r, const void *a, const void *b, const void *c) {
+  const void *out[3] = {x, upd, r}, *in[3] = {a, b, c};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = i + 1; j < 3; ++j)
+      if (out[i] == out[j]) return true;
+    for (int j = 0; j < 3; ++j)
+      if (in[j] && out[i] == in[j]) return true;
+  }
+  return false;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfgpu_vec_convert(void *dst, int dst_type, const void *src, int src_type, size_t n, void *stream) {
+  if (!valid_type(dst_type) || !valid_type(src_type)) return einval("mfgpu_vec_convert: number type must be MFGPU_F64 or MFGPU_F32");
+  if (n == 0) return MFGPU_OK;
+  if (!dst || !src) return einval("mfgpu_vec_convert: null vector");
+  const hipStream_t st = (hipStream_t)stream;
+  if (dst_type == src_type) {
+    if (dst == src) return MFGPU_OK;
+    const hipError_t e = hipMemcpyAsync(dst, src, n * (dst_type == MFGPU_F64 ? 8 : 4), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) {
+      mfgpu::set_error(std::string("mfgpu_vec_convert: ") + hipGetErrorString(e));
+      return MFGPU_EHIP;
+    }
+    return MFGPU_OK;
+  }
+  if (dst == src) return einval("mfgpu_vec_convert: dst and src must not alias");
+  if (dst_type == MFGPU_F32)
+    convert_launch<float, double>((float *)dst, (const double *)src, n, st);
+  else
+    convert_launch<double, float>((double *)dst, (const float *)src, n, st);
+  return hip_status("mfgpu_vec_convert");
+}
+
+int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const void *t, const void *dinv, double f,
+                              int zero_start, size_t n, int number_type, void *stream) {
+  if (!valid_type(number_type)) return einval("mfgpu_vec_chebyshev_start: number type must be MFGPU_F64 or MFGPU_F32");
+  if (n == 0) return MFGPU_OK;
+  if (!x || !upd || !r || !b || !dinv) return einval("mfgpu_vec_chebyshev_start: null vector");
+  if (outputs_alias(x, upd, r, b, t, dinv)) return einval("mfgpu_vec_chebyshev_start: x, upd and r must not alias each other or an input");
+  const hipStream_t st = (hipStream_t)stream;
+  if (number_type == MFGPU_F64)
+    cheb_start_launch<double>((double *)x, (double *)upd, (double *)r, (const double *)b, (const double *)t,
+                              (const double *)dinv, f, zero_start != 0, n, st);
+  else
+    cheb_start_launch<float>((float *)x, (float *)upd, (float *)r, (const float *)b, (const float *)t,
+                             (const float *)dinv, (float)f, zero_start != 0, n, st);
+  return hip_status("mfgpu_vec_chebyshev_start");
+}
+
+int mfgpu_vec_chebyshev_update(void *x, void *upd, void *r, const void *t, const void *dinv, double f1, double f2,
+                               size_t n, int number_type, void *stream) {
+  if (!valid_type(number_type)) return einval("mfgpu_vec_chebyshev_update: number type must be MFGPU_F64 or MFGPU_F32");
+  if (n == 0) return MFGPU_OK;
+  if (!x || !upd || !r || !t || !dinv) return einval("mfgpu_vec_chebyshev_update: null vector");
+  if (outputs_alias(x, upd, r, t, dinv, nullptr)) return einval("mfgpu_vec_chebyshev_update: x, upd and r must not alias each other or an input");
+  const hipStream_t st = (hipStream_t)stream;
+  if (number_type == MFGPU_F64)
+    cheb_update_launch<double>((double *)x, (double *)upd, (double *)r, (const double *)t, (const double *)dinv, f1, f2,
+                               n, st);
+  else
+    cheb_update_launch<float>((float *)x, (float *)upd, (float *)r, (const float *)t, (const float *)dinv, (float)f1,
+                              (float)f2, n, st);
+  return hip_status("mfgpu_vec_chebyshev_update");
+}
+
+}  // extern "C"

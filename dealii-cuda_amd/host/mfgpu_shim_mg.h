@@ -10,7 +10,9 @@
 #define MFGPU_SHIM_MG_H
 
 #include <cmath>
+#include <limits>
 #include <memory>
+#include <type_traits>
 
 #include "mfgpu_shim.h"
 
@@ -58,35 +60,38 @@ public:
     if (hierarchy) {
       mfgpu_mg_hierarchy_destroy(hierarchy);  // owns its level meshes
       hierarchy = nullptr;
-      mfgpu_mesh_destroy(active);
+      mfgpu_mesh_destroy(level_active);
     } else {
       for (mfgpu_mesh *m : levels) mfgpu_mesh_destroy(m);
     }
-    active = nullptr;
+    if (active != level_active && (levels.empty() || active != levels.back())) mfgpu_mesh_destroy(active);
+    active = level_active = nullptr;
     levels.clear();
   }
   void distribute_mg_dofs(const FE_Q<dim> &fe, int number_type = MFGPU_F64) {
+    distribute_mg_dofs(fe, number_type, number_type);
+  }
+  // levels in level_number_type, the active mesh in active_number_type (a float V-cycle under a double solver,
+  // poisson_mg.cu:51 level_number).  When the two differ the active mesh is built again in its own type; the mesh
+  // generators are deterministic, so its numbering is that of the level-type active mesh the hierarchy comes from
+  void distribute_mg_dofs(const FE_Q<dim> &fe, int level_number_type, int active_number_type) {
     clear();
     degree = fe.degree;
     if (tria->adaptive) {
       if (tria->domain != CUBE) throw std::runtime_error("multigrid on adaptive meshes: CUBE domain only");
-      check(mfgpu_mesh_create_adaptive_mg(dim, (int)fe.degree, tria->n_ref, number_type, &active), "active mesh");
-      check(mfgpu_mg_hierarchy_create(active, &hierarchy), "level hierarchy");
+      check(mfgpu_mesh_create_adaptive_mg(dim, (int)fe.degree, tria->n_ref, level_number_type, &level_active), "active mesh");
+      active = level_active;
+      check(mfgpu_mg_hierarchy_create(level_active, &hierarchy), "level hierarchy");
       for (int l = 0; l < mfgpu_mg_n_levels(hierarchy); ++l)
         levels.push_back(const_cast<mfgpu_mesh *>(mfgpu_mg_level_mesh(hierarchy, l)));
+      if (active_number_type != level_number_type) {
+        active = nullptr;
+        check(mfgpu_mesh_create_adaptive_mg(dim, (int)fe.degree, tria->n_ref, active_number_type, &active), "active mesh");
+      }
       return;
     }
-    for (int l = 0; l <= tria->n_ref; ++l) {
-      mfgpu_mesh *m = nullptr;
-      if (tria->domain == BALL) {
-        check(mfgpu_mesh_create_ball(dim, (int)fe.degree, l, number_type, &m), "level mesh");
-      } else {
-        uint32_t nper[3] = {1u << l, 1u << l, 1u << l};
-        check(mfgpu_mesh_create_uniform(dim, (int)fe.degree, nper, -1.0, 1.0, 0, 0, number_type, &m), "level mesh");
-      }
-      levels.push_back(m);
-    }
-    active = levels.back();
+    for (int l = 0; l <= tria->n_ref; ++l) levels.push_back(create_level(l, level_number_type));
+    active = active_number_type == level_number_type ? levels.back() : create_level(tria->n_ref, active_number_type);
   }
   bool is_adaptive() const { return hierarchy != nullptr; }
   unsigned int n_levels() const { return (unsigned int)levels.size(); }
@@ -109,9 +114,22 @@ public:
   }
   const Triangulation<dim> *tria;
   std::vector<mfgpu_mesh *> levels;
-  mfgpu_mesh *active = nullptr;  // the active mesh (== levels.back() on globally refined meshes)
+  mfgpu_mesh *active = nullptr;  // the active mesh (== levels.back() on globally refined meshes of one number type)
   mfgpu_mg_hierarchy *hierarchy = nullptr;
   unsigned int degree = 0;
+
+private:
+  mfgpu_mesh *level_active = nullptr;  // adaptive: the level-type active mesh the hierarchy was built from
+  mfgpu_mesh *create_level(int l, int number_type) const {
+    mfgpu_mesh *m = nullptr;
+    if (tria->domain == BALL) {
+      check(mfgpu_mesh_create_ball(dim, (int)degree, l, number_type, &m), "level mesh");
+    } else {
+      uint32_t nper[3] = {1u << l, 1u << l, 1u << l};
+      check(mfgpu_mesh_create_uniform(dim, (int)degree, nper, -1.0, 1.0, 0, 0, number_type, &m), "level mesh");
+    }
+    return m;
+  }
 };
 
 // level-local operator (laplace_operator_gpu.h:154-186): the operator of the level mesh; the level's Dirichlet rows
@@ -242,25 +260,38 @@ public:
     check(mfgpu_transfer_restrict_and_add(transfers.at(from_level - 1), dst.getData(), src.getDataRO(), nullptr), "restrict_and_add");
   }
   // copy_to_mg / copy_from_mg (:690-760).  Globally refined: the active vector IS the finest level's.  Adaptive: the
-  // copy_indices of every level (dofs of the cells active on it, off its refinement edge)
-  void copy_to_mg(const MGDoFHandler<dim> &dh, MGLevelObject<GpuVector<Number>> &dst, const GpuVector<Number> &src) const {
+  // copy_indices of every level (dofs of the cells active on it, off its refinement edge).  OtherNumber: the active
+  // vector's type (deal.II's template of the same name); a different one is converted on the way
+  template <typename OtherNumber>
+  void copy_to_mg(const MGDoFHandler<dim> &dh, MGLevelObject<GpuVector<Number>> &dst, const GpuVector<OtherNumber> &src) const {
+    constexpr bool same = std::is_same<Number, OtherNumber>::value;
     for (unsigned int l = dst.min_level(); l <= dst.max_level(); ++l) {
       if (dst[l].size() != dh.n_dofs(l)) dst[l].reinit(dh.n_dofs(l));
       dst[l] = Number(0);
-      if (!to_mg.empty())
+      if (to_mg.empty()) continue;
+      if (same)
         check(mfgpu_vec_copy_pairs(to_mg[l], dst[l].getData(), src.getDataRO(), number_type<Number>(), nullptr), "copy_to_mg");
+      else
+        check(mfgpu_vec_copy_pairs_convert(to_mg[l], dst[l].getData(), number_type<Number>(), src.getDataRO(),
+                                           number_type<OtherNumber>(), nullptr), "copy_to_mg");
     }
-    if (to_mg.empty()) dst[dst.max_level()].equ(1, src);
+    if (to_mg.empty()) copy_active(dst[dst.max_level()], src);
   }
-  void copy_from_mg(const MGDoFHandler<dim> &dh, GpuVector<Number> &dst, const MGLevelObject<GpuVector<Number>> &src) const {
+  template <typename OtherNumber>
+  void copy_from_mg(const MGDoFHandler<dim> &dh, GpuVector<OtherNumber> &dst, const MGLevelObject<GpuVector<Number>> &src) const {
     if (from_mg.empty()) {
-      dst.equ(1, src[src.max_level()]);
+      copy_active(dst, src[src.max_level()]);
       return;
     }
     if (dst.size() != dh.n_dofs()) dst.reinit(dh.n_dofs());
-    dst = Number(0);
-    for (unsigned int l = src.min_level(); l <= src.max_level(); ++l)
-      check(mfgpu_vec_copy_pairs(from_mg[l], dst.getData(), src[l].getDataRO(), number_type<Number>(), nullptr), "copy_from_mg");
+    dst = OtherNumber(0);
+    for (unsigned int l = src.min_level(); l <= src.max_level(); ++l) {
+      if (std::is_same<Number, OtherNumber>::value)
+        check(mfgpu_vec_copy_pairs(from_mg[l], dst.getData(), src[l].getDataRO(), number_type<Number>(), nullptr), "copy_from_mg");
+      else
+        check(mfgpu_vec_copy_pairs_convert(from_mg[l], dst.getData(), number_type<OtherNumber>(), src[l].getDataRO(),
+                                           number_type<Number>(), nullptr), "copy_from_mg");
+    }
   }
   std::size_t memory_consumption() const {
     std::size_t s = 0;
@@ -269,6 +300,17 @@ public:
   }
 
 private:
+  // dst = src between the active vector and the finest level of a globally refined hierarchy
+  template <typename D, typename S>
+  static void copy_active(GpuVector<D> &dst, const GpuVector<S> &src) {
+    if constexpr (std::is_same<D, S>::value) {
+      dst.equ(1, src);
+    } else {
+      if (dst.size() != src.size()) dst.reinit(src.size());
+      check(mfgpu_vec_convert(dst.getData(), number_type<D>(), src.getDataRO(), number_type<S>(), src.size(), nullptr),
+            "copy_to_mg / copy_from_mg");
+    }
+  }
   std::vector<mfgpu_transfer *> transfers;
   std::vector<mfgpu_index_pairs *> to_mg, from_mg;
 };
@@ -286,6 +328,9 @@ public:
     double smoothing_range = 15.;
     unsigned int eig_cg_n_iterations = 15;
     std::shared_ptr<DiagonalMatrix<Number>> preconditioner;
+    // run the vector updates of a sweep as mfgpu_vec_chebyshev_start / _update (one launch per inner step instead of
+    // five BLAS-1 launches, 8 instead of 14 vectors of traffic; DESIGN.md §10, mixed precision)
+    bool fused_updates = false;
   };
   void initialize(const MatrixType &A, const AdditionalData &d) {
     matrix = &A;
@@ -318,6 +363,9 @@ public:
   // one more sweep on a non-zero iterate (post-smoothing)
   void step(VectorType &dst, const VectorType &src) const { run(dst, src, false); }
   double lambda_max = 0, lambda_min = 0;
+  std::size_t memory_consumption() const {
+    return r.memory_consumption() + t.memory_consumption() + upd.memory_consumption();
+  }
 
 private:
   void run(VectorType &x, const VectorType &b, bool zero_start) const {
@@ -325,6 +373,10 @@ private:
     const double sigma = theta / delta;
     double rho = 1.0 / sigma;
     const VectorType &dinv = data.preconditioner->get_vector();
+    if (data.fused_updates) {
+      run_fused(x, b, zero_start, theta, delta, sigma, rho, dinv);
+      return;
+    }
     r.equ(1, b);
     if (!zero_start) {
       matrix->vmult(t, x);
@@ -344,6 +396,24 @@ private:
       t.scale(dinv);
       upd.sadd((Number)(rho_new * rho), 1, t);
       x.add(1, upd);
+      rho = rho_new;
+    }
+  }
+  // the same recurrence with the vector updates fused (r, t, upd, x, dinv read; r, upd, x written)
+  void run_fused(VectorType &x, const VectorType &b, bool zero_start, double theta, double delta, double sigma, double rho,
+                 const VectorType &dinv) const {
+    const unsigned int N = b.size();
+    if (x.size() != N) x.reinit(N);
+    if (!zero_start) matrix->vmult(t, x);
+    check(mfgpu_vec_chebyshev_start(x.getData(), upd.getData(), r.getData(), b.getDataRO(), zero_start ? nullptr : t.getDataRO(),
+                                    dinv.getDataRO(), 1.0 / theta, zero_start ? 1 : 0, N, number_type<Number>(), nullptr),
+          "PreconditionChebyshev: fused start");
+    for (unsigned int k = 1; k < data.degree; ++k) {
+      matrix->vmult(t, upd);
+      const double rho_new = 1.0 / (2.0 * sigma - rho);
+      check(mfgpu_vec_chebyshev_update(x.getData(), upd.getData(), r.getData(), t.getDataRO(), dinv.getDataRO(),
+                                       rho_new * rho, 2.0 * rho_new / delta, N, number_type<Number>(), nullptr),
+            "PreconditionChebyshev: fused update");
       rho = rho_new;
     }
   }
@@ -374,11 +444,21 @@ public:
       edge[l].reinit(dh.n_dofs(l));
     }
   }
-  // PreconditionMG::vmult: copy_to_mg, one V-cycle, copy_from_mg
-  void vmult(VectorType &dst, const VectorType &src) const {
+  // PreconditionMG::vmult: copy_to_mg, one V-cycle, copy_from_mg; the outer vectors may be of another number type
+  // than the levels (PreconditionMG<dim, VectorType, TRANSFER>::vmult<OtherVectorType>)
+  template <typename OtherNumber>
+  void vmult(GpuVector<OtherNumber> &dst, const GpuVector<OtherNumber> &src) const {
     transfer->copy_to_mg(*dof_handler, defect, src);
     level_v_step(matrices->max_level());
     transfer->copy_from_mg(*dof_handler, dst, solution);
+  }
+  // the V-cycle's level vectors (defect, solution, tmp, edge)
+  std::size_t memory_consumption() const {
+    std::size_t s = 0;
+    for (unsigned int l = 0; l <= matrices->max_level(); ++l)
+      s += defect[l].memory_consumption() + solution[l].memory_consumption() + tmp[l].memory_consumption() +
+           edge[l].memory_consumption();
+    return s;
   }
 
 private:

@@ -6,11 +6,18 @@
 // Output:  dim  degree  n_dofs  levels  cg_iterations  wall_seconds  rel_error
 // usage: poisson-mg-<dim>d-p<k> n_ref          (-DBALL_GRID: the BALL domain; -DADAPTIVE_GRID: the pseudo-adaptive
 // mesh with hanging nodes, local smoothing with refinement-edge matrices, poisson_mg.cu:365-375)
+// -DMG_LEVEL_FLOAT: the whole multigrid hierarchy in float under the double CG (the reference's commented
+// `typedef float level_number;`, bmop_mg.cu:58-59); -DMG_FUSED_SMOOTHER: the Chebyshev smoothers with fused vector
+// updates.  With either, two more columns:  mg_bytes (level operators, inverse diagonals, transfers, level vectors)
+// vcycle_ms (mean of 10 preconditioner applications after the solve, each between two device synchronisations)
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
 #include <iostream>
+#include <limits>
+#include <type_traits>
 
 #include "mfgpu_shim_mg.h"
 
@@ -23,12 +30,23 @@ using namespace mfgpu_shim;
 #define DIMENSION 3
 #endif
 typedef double number;
+#ifdef MG_LEVEL_FLOAT
+typedef float level_number;
+#else
+typedef double level_number;
+#endif
+#if defined(MG_LEVEL_FLOAT) || defined(MG_FUSED_SMOOTHER)
+#define MG_REPORT 1
+#endif
 typedef GpuVector<number> VectorType;
 
-// coarse solver (poisson_mg.cu:61-83): unpreconditioned CG, relative tolerance 1e-10
+// coarse solver (poisson_mg.cu:61-83): unpreconditioned CG to a relative max(1e-10, 100 eps) -- 1e-10 in double, what
+// float can reach in float -- or as many iterations as the coarse level has dofs
 template <typename MatrixType>
 class MGCoarseIterative {
 public:
+  typedef typename MatrixType::value_type Number;
+  typedef GpuVector<Number> LevelVectorType;
   void initialize(const MatrixType &matrix) {
     coarse_matrix = &matrix;
     const unsigned int N = matrix.m();
@@ -36,29 +54,42 @@ public:
     p.reinit(N);
     q.reinit(N);
   }
-  void operator()(const unsigned int, VectorType &dst, const VectorType &src) const {
-    dst = number(0);
+  void operator()(const unsigned int, LevelVectorType &dst, const LevelVectorType &src) const {
+    dst = Number(0);
     r.equ(1, src);
     p.equ(1, r);
-    number rr = r * r;
-    const number tol = 1e-10 * std::sqrt(rr);
-    for (unsigned int it = 0; it < 10000 && std::sqrt(rr) > tol; ++it) {
+    Number rr = r * r;
+    const Number tol = std::max(1e-10, 100. * std::numeric_limits<Number>::epsilon()) * std::sqrt(rr);
+    for (unsigned int it = 0; it < coarse_matrix->m() && std::sqrt(rr) > tol; ++it) {
       coarse_matrix->vmult(q, p);
-      const number alpha = rr / (p * q);
+      const Number alpha = rr / (p * q);
       dst.add(alpha, p);
       r.add(-alpha, q);
-      const number rr_new = r * r;
+      const Number rr_new = r * r;
       p.sadd(rr_new / rr, 1, r);
       rr = rr_new;
     }
   }
+  std::size_t memory_consumption() const {
+    return r.memory_consumption() + p.memory_consumption() + q.memory_consumption();
+  }
   const MatrixType *coarse_matrix = nullptr;
-  mutable VectorType r, p, q;
+  mutable LevelVectorType r, p, q;
 };
+
+// the system matrix of a globally refined mesh is the finest level's when both are of one number type
+template <typename S, typename L>
+const S *finest_level_as_system(const L &finest) {
+  if constexpr (std::is_same<S, L>::value)
+    return &finest;
+  else
+    return nullptr;
+}
 
 template <int dim, int fe_degree>
 int run(int n_ref) {
-  typedef LevelOperatorGpu<dim, fe_degree, number> LevelMatrixType;
+  typedef LevelOperatorGpu<dim, fe_degree, level_number> LevelMatrixType;
+  typedef LevelOperatorGpu<dim, fe_degree, number> SystemMatrixType;
   Triangulation<dim> triangulation;
 #if defined(BALL_GRID)
   bmop_setup_mesh(triangulation, BALL, false, n_ref);
@@ -69,7 +100,7 @@ int run(int n_ref) {
 #endif
   FE_Q<dim> fe(fe_degree);
   MGDoFHandler<dim> dof_handler(triangulation);
-  dof_handler.distribute_mg_dofs(fe, number_type<number>());
+  dof_handler.distribute_mg_dofs(fe, number_type<level_number>(), number_type<number>());
   const unsigned int nlevels = dof_handler.n_levels();
 
   MGConstrainedDoFs mg_constrained_dofs;
@@ -79,18 +110,19 @@ int run(int n_ref) {
     mg_matrices[level].reinit(dof_handler, mg_constrained_dofs, level);
     mg_matrices[level].compute_diagonal();
   }
-  // the system matrix: on a globally refined mesh the finest level's; on the adaptive mesh the active cells' operator
-  // with hanging nodes
-  LevelMatrixType active_matrix;
-  if (dof_handler.is_adaptive()) active_matrix.reinit_active(dof_handler);
-  const LevelMatrixType &system_matrix = dof_handler.is_adaptive() ? active_matrix : mg_matrices[nlevels - 1];
+  // the system matrix: on a globally refined mesh the finest level's (the active mesh's operator in its own type when
+  // the levels are float); on the adaptive mesh the active cells' operator with hanging nodes
+  SystemMatrixType active_matrix;
+  const SystemMatrixType *finest = finest_level_as_system<SystemMatrixType>(mg_matrices[nlevels - 1]);
+  if (dof_handler.is_adaptive() || !finest) active_matrix.reinit_active(dof_handler);
+  const SystemMatrixType &system_matrix = dof_handler.is_adaptive() || !finest ? active_matrix : *finest;
   const unsigned int N = system_matrix.n();
 
-  MGTransferMatrixFreeGpu<dim, number> mg_transfer(mg_constrained_dofs);
+  MGTransferMatrixFreeGpu<dim, level_number> mg_transfer(mg_constrained_dofs);
   mg_transfer.build(dof_handler);
   MGCoarseIterative<LevelMatrixType> mg_coarse;
   mg_coarse.initialize(mg_matrices[0]);
-  typedef PreconditionChebyshev<LevelMatrixType, VectorType> SMOOTHER;
+  typedef PreconditionChebyshev<LevelMatrixType, GpuVector<level_number>> SMOOTHER;
   MGLevelObject<SMOOTHER> mg_smoother;
   mg_smoother.resize(0, nlevels - 1);
   for (unsigned int level = 0; level < nlevels; ++level) {
@@ -99,9 +131,12 @@ int run(int n_ref) {
     sd.degree = 5;
     sd.eig_cg_n_iterations = 15;
     sd.preconditioner = mg_matrices[level].get_diagonal_inverse();
+#ifdef MG_FUSED_SMOOTHER
+    sd.fused_updates = true;
+#endif
     mg_smoother[level].initialize(mg_matrices[level], sd);
   }
-  MultigridPreconditioner<dim, LevelMatrixType, number, MGCoarseIterative<LevelMatrixType>> preconditioner(
+  MultigridPreconditioner<dim, LevelMatrixType, level_number, MGCoarseIterative<LevelMatrixType>> preconditioner(
       dof_handler, mg_matrices, mg_coarse, mg_transfer, mg_smoother);
 
   // x*: zero on the Dirichlet dofs; b = A x*
@@ -135,7 +170,23 @@ int run(int n_ref) {
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   x.add(-1, x_star);
   const double err = x.l2_norm() / x_star.l2_norm();
+#ifdef MG_REPORT
+  std::size_t mg_bytes = mg_transfer.memory_consumption() + preconditioner.memory_consumption() + mg_coarse.memory_consumption();
+  for (unsigned int level = 0; level < nlevels; ++level)
+    mg_bytes += mg_matrices[level].memory_consumption() + mg_matrices[level].get_diagonal_inverse()->get_vector().memory_consumption() +
+                mg_smoother[level].memory_consumption();
+  double vcycle_ms = 0;
+  for (int k = 0; k < 10; ++k) {
+    mfgpu_device_synchronize();
+    const auto v0 = std::chrono::steady_clock::now();
+    preconditioner.vmult(z, b);
+    mfgpu_device_synchronize();
+    vcycle_ms += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - v0).count() / 10;
+  }
+  printf("%8d %8d %12u %8u %8u %14.8g %12.4g %12zu %10.4f\n", dim, fe_degree, N, nlevels, it, wall, err, mg_bytes, vcycle_ms);
+#else
   printf("%8d %8d %12u %8u %8u %14.8g %12.4g\n", dim, fe_degree, N, nlevels, it, wall, err);
+#endif
   return (it <= 1000 && err < 1e-8) ? 0 : 2;
 }
 

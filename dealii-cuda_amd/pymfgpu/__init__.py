@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFGPU_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libmfgpu.so")
 
 F64, F32 = 0, 1
+OK, EINVAL = 0, -1  # MFGPU_OK, MFGPU_EINVAL
 UNIFORM_J0, HANGING_NODES, COLORED_SCATTER = 1, 2, 1 << 8
 KERNEL_AUTO, KERNEL_PENCILS, KERNEL_PENCILS_X, KERNEL_PLANES, KERNEL_PLANES_2W = 0, 1, 2, 3, 4  # Desc.kernel
 
@@ -60,6 +61,7 @@ SYMBOLS = [
     "mfgpu_mg_edge_dofs", "mfgpu_mg_copy_pairs", "mfgpu_mg_transfer_arrays", "mfgpu_mg_hierarchy_destroy",
     "mfgpu_integrator_create", "mfgpu_integrator_rhs", "mfgpu_integrator_l2_error", "mfgpu_integrator_error_points",
     "mfgpu_integrator_destroy",
+    "mfgpu_vec_convert", "mfgpu_vec_copy_pairs_convert", "mfgpu_vec_chebyshev_start", "mfgpu_vec_chebyshev_update",
 ]
 
 _lib = None
@@ -174,6 +176,10 @@ def lib():
         L.mfgpu_integrator_error_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.mfgpu_integrator_destroy.argtypes = [C.c_void_p]
         L.mfgpu_integrator_destroy.restype = None
+        L.mfgpu_vec_convert.argtypes = [vp, i, vp, i, z, vp]
+        L.mfgpu_vec_copy_pairs_convert.argtypes = [vp, vp, i, vp, i, vp]
+        L.mfgpu_vec_chebyshev_start.argtypes = [vp, vp, vp, vp, vp, vp, d, i, z, i, vp]
+        L.mfgpu_vec_chebyshev_update.argtypes = [vp, vp, vp, vp, vp, d, d, z, i, vp]
         _lib = L
     return _lib
 
@@ -715,6 +721,55 @@ def _ptr(v):
     if hasattr(v, "data_ptr"):  # torch tensor on the GPU
         return v.data_ptr()
     return int(v)
+
+
+class IndexPairs:
+    """copy_to_mg / copy_from_mg index pairs on the device (mfgpu_index_pairs_*): dst[dst_idx[i]] = src[src_idx[i]]"""
+
+    def __init__(self, dst_idx, src_idx):
+        a = np.ascontiguousarray(dst_idx, dtype=np.uint32)
+        b = np.ascontiguousarray(src_idx, dtype=np.uint32)
+        assert a.size == b.size
+        h = C.c_void_p()
+        _check(lib().mfgpu_index_pairs_create(a.ctypes.data if a.size else None, b.ctypes.data if b.size else None,
+                                              a.size, C.byref(h)))
+        self._h = h
+
+    def copy(self, dst, src, number_type=F64, stream=None):
+        _check(lib().mfgpu_vec_copy_pairs(self._h, _ptr(dst), _ptr(src), number_type, stream))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_index_pairs_destroy(self._h)
+            self._h = None
+
+
+# ---- mixed-precision multigrid and the fused Chebyshev smoother (include/mfgpu.h).  Vectors: DeviceVector, a torch
+# tensor on the GPU or a device address; the raw return code is given back so that tests can check MFGPU_EINVAL.
+def vec_convert(dst, dst_type, src, src_type, n, stream=None, check=True):
+    """dst[i] = (dst_type) src[i] for i < n"""
+    rc = lib().mfgpu_vec_convert(_ptr(dst), dst_type, _ptr(src), src_type, n, stream)
+    return _check(rc) if check else rc
+
+
+def copy_pairs_convert(pairs: "IndexPairs", dst, dst_type, src, src_type, stream=None, check=True):
+    """dst[dst_idx[i]] = (dst_type) src[src_idx[i]] over the pairs; other entries of dst untouched"""
+    rc = lib().mfgpu_vec_copy_pairs_convert(pairs._h, _ptr(dst), dst_type, _ptr(src), src_type, stream)
+    return _check(rc) if check else rc
+
+
+def chebyshev_start(x, upd, r, b, t, dinv, f, zero_start, n, number_type, stream=None, check=True):
+    """r = b - t (t None: r = b); upd = f dinv r; x = upd (zero_start) or x += upd"""
+    rc = lib().mfgpu_vec_chebyshev_start(_ptr(x), _ptr(upd), _ptr(r), _ptr(b), None if t is None else _ptr(t),
+                                         _ptr(dinv), float(f), 1 if zero_start else 0, n, number_type, stream)
+    return _check(rc) if check else rc
+
+
+def chebyshev_update(x, upd, r, t, dinv, f1, f2, n, number_type, stream=None, check=True):
+    """r -= t; upd = f1 upd + f2 dinv r; x += upd"""
+    rc = lib().mfgpu_vec_chebyshev_update(_ptr(x), _ptr(upd), _ptr(r), _ptr(t), _ptr(dinv), float(f1), float(f2), n,
+                                          number_type, stream)
+    return _check(rc) if check else rc
 
 
 def synchronize():

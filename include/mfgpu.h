@@ -287,6 +287,26 @@ int mfgpu_index_pairs_create(const uint32_t *dst_idx, const uint32_t *src_idx, u
 int mfgpu_vec_copy_pairs(const mfgpu_index_pairs *p, void *dst_dev, const void *src_dev, int number_type, void *stream);
 void mfgpu_index_pairs_destroy(mfgpu_index_pairs *p);
 
+/* ---- mixed-precision multigrid: a float V-cycle under a double CG (the reference's level_number, bmop_mg.cu:58-59,
+ * poisson_mg.cu:51; deal.II's copy_to_mg / copy_from_mg with OtherNumber), and the fused Chebyshev smoother updates.
+ * All asynchronous on `stream`; MFGPU_EINVAL on a number type other than MFGPU_F64 / MFGPU_F32.                    */
+/* dst[i] = (dst_type) src[i], i < n.  MFGPU_F64 -> MFGPU_F32 rounds to nearest even (overflow gives +-inf, as numpy's
+ * astype(float32)); MFGPU_F32 -> MFGPU_F64 is exact; the same type is a copy.                                     */
+int mfgpu_vec_convert(void *dst, int dst_type, const void *src, int src_type, size_t n, void *stream);
+/* dst[dst_idx[i]] = (dst_type) src[src_idx[i]] over the pairs of mfgpu_index_pairs_create; other entries untouched */
+int mfgpu_vec_copy_pairs_convert(const mfgpu_index_pairs *p, void *dst, int dst_type, const void *src, int src_type,
+                                 void *stream);
+/* One PreconditionChebyshev sweep in two kinds of launch instead of five BLAS-1 launches per inner step.  Device
+ * vectors of n elements of number_type; x, upd and r are written and must not alias each other or an input
+ * (MFGPU_EINVAL).
+ *   start :  r = b - t (t == NULL: r = b);  upd = (f r) dinv;  x = upd if zero_start, else x += upd
+ *   update:  r -= t;  upd = f1 upd + (f2 r) dinv;  x += upd
+ * The scalars are rounded to number_type first, as GpuVector's calls round theirs.                                */
+int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const void *t, const void *dinv, double f,
+                              int zero_start, size_t n, int number_type, void *stream);
+int mfgpu_vec_chebyshev_update(void *x, void *upd, void *r, const void *t, const void *dinv, double f1, double f2,
+                               size_t n, int number_type, void *stream);
+
 /* ---- cell integrals of a Poisson solve (poisson.cu:152-229, 277-292) ------------------------------------------
  * A separate object created from the same description as the operator; it keeps its own device copy of the geometry
  * (loc2glob, constraint mask, quadrature points, JxW, the folded coefficient) and leaves mfgpu_handle untouched.
