@@ -66,13 +66,13 @@ struct mfgpu_handle {
   void *d_halo = nullptr;
   unsigned long long *d_stamps = nullptr;  // diagnostic build only
   size_t lds = 0, device_bytes = 0;
-  uint32_t max_grid = 0;    // resident workgroups of the cell-loop kernel
-  uint32_t max_grid_p = 0;  // ... of apply_planes3 (its batches: the first plan.n_plane_batches)
-  uint32_t max_grid_ph = 0;  // ... of apply_planes3<HN> (the plane batches of cells with a hanging-node mask)
-  bool xk = false;        // 3D two-pass kernel for three workgroups per CU (apply_batches_x)
-  bool gk = false;        // general-Jacobian kernel (apply_batches_g)
-  bool pk = false;        // plane-per-thread kernel: 3D uniform-Jacobian default for p = 4
-  bool qk = false;        // ... apply_planes4 (MFGPU_KERNEL_PLANES_2W) instead of apply_planes3
+  // the cell-loop kernel families (choose_kernel_and_plan): `planes` takes the first plan.n_plane_batches batches,
+  // `batches` the rest
+  PlaneKernel planes = PlaneKernel::none;
+  BatchKernel batches = BatchKernel::none;
+  uint32_t max_grid = 0;     // resident workgroups of the batch family
+  uint32_t max_grid_p = 0;   // ... of the plane family
+  uint32_t max_grid_ph = 0;  // ... of its <HN> instantiation (the plane batches of cells with a hanging-node mask)
   // profiling
   bool prof = false;
   std::vector<hipEvent_t> ev;  // start/stop pairs
@@ -86,9 +86,51 @@ struct mfgpu_handle {
 
 namespace {
 
+// The only mapping from a kernel family to its launcher pair (mfgpu_kernels.h); hn selects the <HN> instantiation.
 template <typename T>
-hipError_t planes_launch(mfgpu_handle *h, const ApplyArgs<T> &a, bool hn, uint32_t grid, hipStream_t st,
-                         bool configure_only, size_t *lds_out, int *occupancy);
+hipError_t family_configure(const mfgpu_handle *h, PlaneKernel k, bool hn, size_t *lds, int *blocks) {
+  const Plan &P = h->plan;
+  switch (k) {
+    case PlaneKernel::planes3: return p_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
+    case PlaneKernel::planes4: return q_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
+    default: return hipErrorInvalidValue;
+  }
+}
+template <typename T>
+hipError_t family_configure(const mfgpu_handle *h, BatchKernel k, bool hn, size_t *lds, int *blocks) {
+  const Plan &P = h->plan;
+  switch (k) {
+    case BatchKernel::batches: return apply_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
+    case BatchKernel::x: return x_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
+    case BatchKernel::g: return g_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
+    case BatchKernel::g2: return g2_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
+    default: return hipErrorInvalidValue;
+  }
+}
+template <typename T>
+hipError_t family_launch(const mfgpu_handle *h, PlaneKernel k, const ApplyArgs<T> &a, bool hn, uint32_t grid,
+                         hipStream_t st) {
+  const Plan &P = h->plan;
+  const double *S = h->S.data(), *Dt = h->Dt.data();
+  switch (k) {
+    case PlaneKernel::planes3: return p_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
+    case PlaneKernel::planes4: return q_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+template <typename T>
+hipError_t family_launch(const mfgpu_handle *h, BatchKernel k, const ApplyArgs<T> &a, bool hn, uint32_t grid,
+                         hipStream_t st) {
+  const Plan &P = h->plan;
+  const double *S = h->S.data(), *Dt = h->Dt.data();
+  switch (k) {
+    case BatchKernel::batches: return apply_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
+    case BatchKernel::x: return x_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
+    case BatchKernel::g: return g_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
+    case BatchKernel::g2: return g2_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
+    default: return hipErrorInvalidValue;
+  }
+}
 
 template <typename P>
 int dev_upload(P **dst, const void *src, size_t bytes, size_t &acct) {
@@ -206,7 +248,8 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
   if ((rc = dev_upload(&h->d_bdofs, P.bdofs.data(), P.bdofs.size() * 4, acct))) return rc;
   if ((rc = dev_upload(&h->d_bflags, P.bflags.data(), P.bflags.size(), acct))) return rc;
   if ((rc = dev_upload(&h->d_lmap, P.lmap.data(), P.lmap.size() * 2, acct))) return rc;
-  if (h->xk && !h->hn) {
+  const bool general = h->batches == BatchKernel::g || h->batches == BatchKernel::g2;
+  if (h->batches == BatchKernel::x && !h->hn) {
     // Lane -> pencil maps of the y- and z-stage (see apply_batches_x).  LDS rules (MI355X_MICROARCH.md): a
     // ds_read_b64 is served in 32-lane groups, a double occupies slot (index mod 32); ds_write_b64 / ds_read2_b64
     // in 16-lane groups, slot (index mod 16).  All n elements of a pencil shift its base by the same stride, so
@@ -234,7 +277,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     }
     if ((rc = dev_upload(&h->d_perm, perm.data(), perm.size() * 2, acct))) return rc;
   }
-  if (h->xk || h->gk) {
+  if (h->batches == BatchKernel::x || general) {
     // x-pencil index runs (n contiguous entries of lmap) padded to whole 32-bit words
     const size_t n = (size_t)P.n, np = (n + 1) & ~(size_t)1, runs = P.lmap.size() / n;
     std::vector<uint16_t> lx(runs * np, 0);
@@ -242,7 +285,15 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
       for (size_t i = 0; i < n; ++i) lx[r * np + i] = P.lmap[r * n + i];
     if ((rc = dev_upload(&h->d_lmapx, lx.data(), lx.size() * 2, acct))) return rc;
   }
-  if (h->pk) {
+  if (h->batches == BatchKernel::g2) {  // apply_batches_g2: the full 1D tables [S | Dt]
+    std::vector<T> sd(2 * (size_t)P.n * P.n);
+    for (int i = 0; i < P.n * P.n; ++i) {
+      sd[i] = (T)h->S[i];
+      sd[P.n * P.n + i] = (T)h->Dt[i];
+    }
+    if ((rc = dev_upload((T **)&h->d_tabsd, sd.data(), sd.size() * sizeof(T), acct))) return rc;
+  }
+  if (h->planes != PlaneKernel::none) {
     if ((rc = build_plane_records(h->plan, d.constraint_mask))) return rc;
     if (!P.pr_hn.empty()) {
       if ((rc = dev_upload(&h->d_hnrec, P.pr_hn.data(), P.pr_hn.size() * 4, acct))) return rc;
@@ -255,7 +306,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
   if (h->twopass) {
     if ((rc = dev_upload(&h->d_batch_nint, P.batch_nint.data(), P.batch_nint.size() * 4, acct))) return rc;
     if ((rc = dev_upload(&h->d_halo_off, P.halo_off.data(), P.halo_off.size() * 4, acct))) return rc;
-    if (h->pk && (uint64_t)P.halo_off.back() >= (1ull << 29)) {
+    if (h->planes != PlaneKernel::none && (uint64_t)P.halo_off.back() >= (1ull << 29)) {
       set_error("halo buffer too large for 32-bit byte offsets");
       return MFGPU_EUNSUPPORTED;
     }
@@ -298,16 +349,16 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     }
   }
   if ((rc = dev_upload(&t_jxw, d.JxW, ncell * nd * sizeof(T), tmp))) { cleanup(); return rc; }
-  const size_t jac_per_cell = h->gk ? nd * (size_t)(P.dim * P.dim) : 1;  // full J^-1 per point, or one scalar per cell
+  const size_t jac_per_cell = general ? nd * (size_t)(P.dim * P.dim) : 1;  // full J^-1 per point, or one scalar per cell
   if ((rc = dev_upload(&t_j0, d.inv_jac, ncell * jac_per_cell * sizeof(T), tmp))) { cleanup(); return rc; }
   if ((rc = dev_upload(&t_order, P.cell_order.data(), ncell * 4, tmp))) { cleanup(); return rc; }
   // symmetric M = a JxW J^-1 J^-T (6 entries in 3D, 3 in 2D), or the scalar a J0^2 JxW
-  const size_t coef_per_point = h->gk ? (P.dim == 3 ? 6 : 3) : 1;
+  const size_t coef_per_point = general ? (P.dim == 3 ? 6 : 3) : 1;
   hipError_t e = hipMalloc(&h->d_coef, ncell * nd * coef_per_point * sizeof(T));
   if (e == hipSuccess) {
     acct += ncell * nd * coef_per_point * sizeof(T);
-    e = h->gk ? (P.dim == 3 ? fold_general_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr)
-                            : fold_general2_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr))
+    e = general ? (P.dim == 3 ? fold_general_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr)
+                              : fold_general2_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr))
               : fold_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -316,7 +367,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     set_error(std::string("coefficient fold: ") + hipGetErrorString(e));
     return MFGPU_EHIP;
   }
-  if (h->pk) {
+  if (h->planes != PlaneKernel::none) {
     // the folded coefficient again, per batch [row y + n z][task]: the layout of stage B of apply_planes3
     // (d_coef in plan cell order stays: the diagonal kernel reads it)
     const int n = P.n, NT = p_cells_per_wave(n) * n;
@@ -349,70 +400,34 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     hipFree(t_cb);
     hipFree(t_cp);
     if (rc) return rc;
-    ApplyArgs<T> dummy{};
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    size_t lds_p = 0;
-    HIP_TRY(planes_launch<T>(h, dummy, false, 0, nullptr, true, &lds_p, &per_cu));
-    if (P.n_plain_plane_batches < P.n_plane_batches) {  // batches of masked cells: apply_planes3<HN>
-      int per_cu_h = 0;
-      size_t lds_h = 0;
-      HIP_TRY(planes_launch<T>(h, dummy, true, 0, nullptr, true, &lds_h, &per_cu_h));
-      hipDeviceProp_t prop_h;
-      int dev_h = 0;
-      HIP_TRY(hipGetDevice(&dev_h));
-      HIP_TRY(hipGetDeviceProperties(&prop_h, dev_h));
-      h->max_grid_ph = (uint32_t)(per_cu_h < 1 ? 1 : per_cu_h) * (uint32_t)prop_h.multiProcessorCount;
-      if (d.max_workgroups && d.max_workgroups < h->max_grid_ph) h->max_grid_ph = d.max_workgroups;
-      if (lds_h > lds_p) lds_p = lds_h;
-    }
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    h->max_grid_p = (uint32_t)(per_cu < 1 ? 1 : per_cu) * (uint32_t)prop.multiProcessorCount;
-    if (d.max_workgroups && d.max_workgroups < h->max_grid_p) h->max_grid_p = d.max_workgroups;
-    if (!h->xk) {
-      h->lds = lds_p;
-      return 0;
-    }
   }
-  // persistent grid: as many workgroups as fit on the chip (each loops over its batches)
-  ApplyArgs<T> dummy{};
-  dummy.nb_max = P.max_batch_dofs;
-  int per_cu = 0, dev = 0;
+  // persistent grids: as many workgroups as fit on the chip (each loops over its batches)
+  int dev = 0, per_cu = 0;
   hipDeviceProp_t prop;
-  if (h->gk && P.dim == 2) {
-    std::vector<T> sd(2 * (size_t)P.n * P.n);
-    for (int i = 0; i < P.n * P.n; ++i) {
-      sd[i] = (T)h->S[i];
-      sd[P.n * P.n + i] = (T)h->Dt[i];
+  HIP_TRY(hipGetDevice(&dev));
+  HIP_TRY(hipGetDeviceProperties(&prop, dev));
+  auto resident_grid = [&](int blocks_per_cu) {
+    const uint32_t g = (uint32_t)(blocks_per_cu < 1 ? 1 : blocks_per_cu) * (uint32_t)prop.multiProcessorCount;
+    return d.max_workgroups && d.max_workgroups < g ? d.max_workgroups : g;
+  };
+  if (h->planes != PlaneKernel::none) {
+    HIP_TRY(family_configure<T>(h, h->planes, false, &h->lds, &per_cu));
+    h->max_grid_p = resident_grid(per_cu);
+    if (P.n_plain_plane_batches < P.n_plane_batches) {  // batches of masked cells: the <HN> instantiation
+      size_t lds_h = 0;
+      HIP_TRY(family_configure<T>(h, h->planes, true, &lds_h, &per_cu));
+      h->max_grid_ph = resident_grid(per_cu);
+      h->lds = std::max(h->lds, lds_h);
     }
-    if ((rc = dev_upload((T **)&h->d_tabsd, sd.data(), sd.size() * sizeof(T), acct))) return rc;
-    HIP_TRY(g2_launch<T>(P.n, dummy, h->hn, 0, nullptr, true, &h->lds, nullptr));
-  } else if (h->gk) {
-    HIP_TRY(g_launch<T>(P.n, dummy, nullptr, nullptr, h->hn, 0, nullptr, true, &h->lds, nullptr));
-  } else if (h->xk) {
-    HIP_TRY(x_launch<T>(P.n, dummy, nullptr, nullptr, h->hn, 0, nullptr, true, &h->lds, nullptr));
-  } else {
-    h->lds = apply_lds_bytes<T>(P.dim, P.n, P.max_batch_dofs);
   }
-  if (h->lds > 160 * 1024) {
+  if (h->batches == BatchKernel::none) return 0;
+  const hipError_t configure_batch_family = family_configure<T>(h, h->batches, h->hn, &h->lds, &per_cu);
+  if (h->lds > 160 * 1024) {  // (takes precedence over an error of the configure call)
     set_error("batch needs more than 160 KiB of LDS; lower max_dofs_per_batch");
     return MFGPU_EINVAL;
   }
-  if (h->gk && P.dim == 2) {
-    HIP_TRY(g2_launch<T>(P.n, dummy, h->hn, 0, nullptr, true, &h->lds, &per_cu));
-  } else if (h->gk) {
-    HIP_TRY(g_launch<T>(P.n, dummy, nullptr, nullptr, h->hn, 0, nullptr, true, &h->lds, &per_cu));
-  } else if (h->xk) {
-    HIP_TRY(x_launch<T>(P.n, dummy, nullptr, nullptr, h->hn, 0, nullptr, true, &h->lds, &per_cu));
-  } else {
-    HIP_TRY(apply_configure<T>(P.dim, P.n, h->lds));
-    HIP_TRY(apply_occupancy<T>(P.dim, P.n, h->hn, h->twopass, h->lds, &per_cu));
-  }
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipGetDeviceProperties(&prop, dev));
-  h->max_grid = (uint32_t)(per_cu < 1 ? 1 : per_cu) * (uint32_t)prop.multiProcessorCount;
-  if (d.max_workgroups && d.max_workgroups < h->max_grid) h->max_grid = d.max_workgroups;
+  HIP_TRY(configure_batch_family);
+  h->max_grid = resident_grid(per_cu);
   return 0;
 }
 
@@ -429,7 +444,7 @@ void choose_segments(mfgpu_handle *h, uint32_t request) {
   const uint32_t nb = (uint32_t)(P.batch_cell_off.size() - 1);
   h->seg_end.assign(1, nb);
   if (!h->twopass || nb < 2 || request == 1) return;
-  const uint32_t npl = h->pk ? P.n_plane_batches : 0u, nplain = h->pk ? P.n_plain_plane_batches : 0u;
+  const uint32_t npl = P.n_plane_batches, nplain = P.n_plain_plane_batches;
   std::vector<uint32_t> cuts;
   if (npl > 0 && npl < nb) cuts.push_back(npl);
   if (nplain > 0 && nplain < npl) cuts.push_back(nplain);  // plain plane batches | plane batches of masked cells
@@ -440,7 +455,7 @@ void choose_segments(mfgpu_handle *h, uint32_t request) {
   // writes the identity rows of the eliminated hanging-node dofs and is a third of the cell loop's time; its first
   // half beside the second half of the cell loop measures 0.267-0.269 instead of 0.274-0.278 ms on C3 (three segments:
   // 0.280; at p = 3: no difference) -- profiles/r03_notes.md section 8
-  if (request == 0 && h->pk && !P.pr_hn.empty() && nplain == 0 && P.n == 5) cuts.push_back(nb / 2);
+  if (request == 0 && !P.pr_hn.empty() && nplain == 0 && P.n == 5) cuts.push_back(nb / 2);
   std::sort(cuts.begin(), cuts.end());
   h->seg_end.clear();
   for (uint32_t c : cuts)
@@ -489,47 +504,30 @@ int vmult_pass2(mfgpu_handle *h, int phase, void *dst, const void *src, hipStrea
   return rc;
 }
 
-// the plane kernel of this handle
-template <typename T>
-hipError_t planes_launch(mfgpu_handle *h, const ApplyArgs<T> &a0, bool hn, uint32_t grid, hipStream_t st,
-                         bool configure_only, size_t *lds_out, int *occupancy) {
-  const ApplyArgs<T> &a = a0;
-  return h->qk ? q_launch<T>(h->plan.n, a, h->S.data(), h->Dt.data(), hn, grid, st, configure_only, lds_out, occupancy)
-               : p_launch<T>(h->plan.n, a, h->S.data(), h->Dt.data(), hn, grid, st, configure_only, lds_out, occupancy);
-}
-
 // batches [b0, b1) of one scatter pass, each with the kernel family that owns it
 template <typename T>
 int launch_cells(mfgpu_handle *h, ApplyArgs<T> a, uint32_t b0, uint32_t b1, hipStream_t st) {
   const Plan &P = h->plan;
-  const uint32_t npl = h->pk ? P.n_plane_batches : 0u;
-  const uint32_t nplain = h->pk ? P.n_plain_plane_batches : 0u;
+  const uint32_t npl = P.n_plane_batches, nplain = P.n_plain_plane_batches;
   if (b0 < nplain) {  // the batches of cells without a hanging-node mask (all batches on conforming meshes)
     a.batch0 = b0;
     a.batch_end = b1 < nplain ? b1 : nplain;
     const uint32_t nbat = a.batch_end - a.batch0;
-    HIP_TRY(planes_launch<T>(h, a, false, nbat < h->max_grid_p ? nbat : h->max_grid_p, st, false, nullptr, nullptr));
+    HIP_TRY(family_launch<T>(h, h->planes, a, false, nbat < h->max_grid_p ? nbat : h->max_grid_p, st));
     b0 = a.batch_end;
   }
   if (b0 < npl && b0 < b1) {  // plane batches of cells WITH a mask
     a.batch0 = b0;
     a.batch_end = b1 < npl ? b1 : npl;
     const uint32_t nbat = a.batch_end - a.batch0;
-    HIP_TRY(planes_launch<T>(h, a, true, nbat < h->max_grid_ph ? nbat : h->max_grid_ph, st, false, nullptr, nullptr));
+    HIP_TRY(family_launch<T>(h, h->planes, a, true, nbat < h->max_grid_ph ? nbat : h->max_grid_ph, st));
     b0 = a.batch_end;
   }
   if (b0 >= b1) return 0;
   a.batch0 = b0;
   a.batch_end = b1;
   const uint32_t nrest = b1 - b0, grid = nrest < h->max_grid ? nrest : h->max_grid;
-  if (h->gk && P.dim == 2)
-    HIP_TRY(g2_launch<T>(P.n, a, h->hn, grid, st, false, nullptr, nullptr));
-  else if (h->gk)
-    HIP_TRY(g_launch<T>(P.n, a, h->S.data(), h->Dt.data(), h->hn, grid, st, false, nullptr, nullptr));
-  else if (h->xk)
-    HIP_TRY(x_launch<T>(P.n, a, h->S.data(), h->Dt.data(), h->hn, grid, st, false, nullptr, nullptr));
-  else
-    HIP_TRY(apply_launch<T>(P.dim, P.n, a, h->S.data(), h->Dt.data(), h->hn, h->twopass, grid, st));
+  HIP_TRY(family_launch<T>(h, h->batches, a, h->hn, grid, st));
   return 0;
 }
 
@@ -649,12 +647,13 @@ namespace {
 template <typename T>
 int inverse_diagonal_typed(mfgpu_handle *h, void *diag, hipStream_t st) {
   const Plan &P = h->plan;
+  const bool general = h->batches == BatchKernel::g || h->batches == BatchKernel::g2;
   if (!h->d_tab2) {  // 1D tables T[2][n*n]: squared [S.^2 | G.^2], or plain [S | G] for the general-geometry path
     const int nn = h->n * h->n;
     std::vector<T> t2(2 * (size_t)nn);
     for (int i = 0; i < nn; ++i) {
-      t2[i] = (T)(h->gk ? h->sv[i] : h->sv[i] * h->sv[i]);
-      t2[nn + i] = (T)(h->gk ? h->sg[i] : h->sg[i] * h->sg[i]);
+      t2[i] = (T)(general ? h->sv[i] : h->sv[i] * h->sv[i]);
+      t2[nn + i] = (T)(general ? h->sg[i] : h->sg[i] * h->sg[i]);
     }
     int rc = dev_upload(&h->d_tab2, t2.data(), t2.size() * sizeof(T), h->device_bytes);
     if (rc) return rc;
@@ -662,11 +661,11 @@ int inverse_diagonal_typed(mfgpu_handle *h, void *diag, hipStream_t st) {
   // inv_diag.reinit(m()): zero  (laplace_operator_gpu.h:407)
   HIP_TRY(fill_launch<T>((T *)diag, P.n_dofs, T(0), st));
   // data.cell_loop(inv_diag, diag_loc_op)  (:409-410)
-  if (h->gk && P.dim == 2)
+  if (h->batches == BatchKernel::g2)
     HIP_TRY(diag_general2_launch<T>(P.n, (T *)diag, (uint32_t)(P.batch_cell_off.size() - 1), h->d_batch_cell_off,
                                     h->d_batch_dof_off, h->d_bdofs, h->d_lmap, (const T *)h->d_coef, h->d_cmask,
                                     (const T *)h->d_hnw, (const T *)h->d_tab2, st));
-  else if (h->gk)
+  else if (h->batches == BatchKernel::g)
     HIP_TRY(diag_general_launch<T>(P.n, (T *)diag, (uint32_t)(P.batch_cell_off.size() - 1), h->d_batch_cell_off,
                                    h->d_batch_dof_off, h->d_bdofs, h->d_lmap, (const T *)h->d_coef, h->d_cmask,
                                    (const T *)h->d_hnw, (const T *)h->d_tab2, st));
@@ -751,7 +750,7 @@ int handle_cells_range(mfgpu_handle *h, uint32_t b0, uint32_t b1, void *dst, con
 // batches [b0, b1) and [c0, c1), b1 <= c0: one launch with a hole when both lie in the plain plane batches
 int handle_cells_two_ranges(mfgpu_handle *h, uint32_t b0, uint32_t b1, uint32_t c0, uint32_t c1, void *dst,
                             const void *src, void *stream, int add) {
-  const uint32_t nplain = h->pk ? h->plan.n_plain_plane_batches : 0u, npl = h->pk ? h->plan.n_plane_batches : 0u;
+  const uint32_t nplain = h->plan.n_plain_plane_batches, npl = h->plan.n_plane_batches;
   const bool plain = c1 <= nplain, masked = b0 >= nplain && c1 <= npl;  // both ranges in one instantiation's batches
   if (b0 >= b1 || c0 >= c1 || b1 > c0 || !(plain || masked)) {
     const int rc = handle_cells_range(h, b0, b1, dst, src, stream, add);
@@ -766,7 +765,7 @@ int handle_cells_two_ranges(mfgpu_handle *h, uint32_t b0, uint32_t b1, uint32_t 
     const uint32_t nbat = (b1 - b0) + (c1 - c0);
     using T = typename std::remove_const<typename std::remove_pointer<decltype(a.src)>::type>::type;
     const uint32_t cap = plain ? h->max_grid_p : h->max_grid_ph;
-    HIP_TRY(planes_launch<T>(h, a, !plain, nbat < cap ? nbat : cap, st, false, nullptr, nullptr));
+    HIP_TRY(family_launch<T>(h, h->planes, a, !plain, nbat < cap ? nbat : cap, st));
     return 0;
   };
   return h->number_type == MFGPU_F64 ? run(make_args<double>(h, dst, src, add)) : run(make_args<float>(h, dst, src, add));
@@ -813,15 +812,7 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
     return MFGPU_EINVAL;
   }
   mfgpu_handle *h = new mfgpu_handle();
-  KernelChoice kc;
-  int rc = choose_kernel_and_plan(d, kc, h->plan);
-  h->gk = kc.general;
-  h->pk = kc.planes;
-  // which plane kernel: apply_planes4 on request, at p = 5, 6 (the only one that fits), and by default at p = 3 in
-  // double; apply_planes3 otherwise (p = 4: equal in double, faster in float)
-  h->qk = d.kernel == MFGPU_KERNEL_PLANES_2W || d.degree >= 5 ||
-          (d.kernel == MFGPU_KERNEL_AUTO && d.degree == 3 && d.number_type == MFGPU_F64);
-  h->xk = kc.pencils_x;
+  int rc = choose_kernel_and_plan(d, h->planes, h->batches, h->plan);
   if (rc) {
     delete h;
     return rc;
@@ -939,7 +930,7 @@ int mfgpu_plan_stats(const mfgpu_handle *h, uint64_t s[8]) {
   s[7] = P.n_add;
   if (h->twopass) {  // two-pass mode reports shared dofs / halo partial sums instead
     // cell-loop launches per vmult: per segment one for each kernel instantiation that owns batches of it
-    const uint32_t nb = (uint32_t)s[0], npl = h->pk ? P.n_plane_batches : 0u, nplain = h->pk ? P.n_plain_plane_batches : 0u;
+    const uint32_t nb = (uint32_t)s[0], npl = P.n_plane_batches, nplain = P.n_plain_plane_batches;
     const uint32_t edge[4] = {0u, nplain, npl, nb};
     s[1] = 0;
     for (size_t g = 0; g < h->seg_end.size(); ++g) {
@@ -955,9 +946,18 @@ int mfgpu_plan_stats(const mfgpu_handle *h, uint64_t s[8]) {
 
 const char *mfgpu_kernel_name(const mfgpu_handle *h) {
   if (!h) return "";
-  if (h->pk && h->qk) return h->xk ? "apply_planes4+apply_batches_x" : "apply_planes4";
-  return h->pk ? (h->xk ? "apply_planes3+apply_batches_x" : "apply_planes3")
-               : h->gk ? (h->dim == 2 ? "apply_batches_g2" : "apply_batches_g") : h->xk ? "apply_batches_x" : "apply_batches";
+  const bool x = h->batches == BatchKernel::x;
+  switch (h->planes) {
+    case PlaneKernel::planes3: return x ? "apply_planes3+apply_batches_x" : "apply_planes3";
+    case PlaneKernel::planes4: return x ? "apply_planes4+apply_batches_x" : "apply_planes4";
+    default: break;
+  }
+  switch (h->batches) {
+    case BatchKernel::x: return "apply_batches_x";
+    case BatchKernel::g: return "apply_batches_g";
+    case BatchKernel::g2: return "apply_batches_g2";
+    default: return "apply_batches";
+  }
 }
 
 int mfgpu_profile_enable(mfgpu_handle *h, int on) {

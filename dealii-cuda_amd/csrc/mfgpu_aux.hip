@@ -28,31 +28,31 @@ __device__ __forceinline__ void hn_transpose_local(T *loc, const T *Wl, unsigned
     if (on && hn_flag3<n, 0>(mask, pa, pb, type)) {
       lds_load<n>(loc + n * pa + n2 * pb, 1, v);
       hn_pencil<n, T, true>(Wl, type, v);
-      lds_store<n>(loc + n * pa + n2 * pb, 1, v);
+      lds_put<n>(loc + n * pa + n2 * pb, 1, v);
     }
     __syncthreads();
     if (on && hn_flag3<n, 1>(mask, pb, pa, type)) {
       lds_load<n>(loc + pa + n2 * pb, n, v);
       hn_pencil<n, T, true>(Wl, type, v);
-      lds_store<n>(loc + pa + n2 * pb, n, v);
+      lds_put<n>(loc + pa + n2 * pb, n, v);
     }
     __syncthreads();
     if (on && hn_flag3<n, 2>(mask, pa, pb, type)) {
       lds_load<n>(loc + pa + n * pb, n2, v);
       hn_pencil<n, T, true>(Wl, type, v);
-      lds_store<n>(loc + pa + n * pb, n2, v);
+      lds_put<n>(loc + pa + n * pb, n2, v);
     }
   } else {
     if (on && hn_flag2<n, 0>(mask, pa, type)) {
       lds_load<n>(loc + n * pa, 1, v);
       hn_pencil<n, T, true>(Wl, type, v);
-      lds_store<n>(loc + n * pa, 1, v);
+      lds_put<n>(loc + n * pa, 1, v);
     }
     __syncthreads();
     if (on && hn_flag2<n, 1>(mask, pa, type)) {
       lds_load<n>(loc + pa, n, v);
       hn_pencil<n, T, true>(Wl, type, v);
-      lds_store<n>(loc + pa, n, v);
+      lds_put<n>(loc + pa, n, v);
     }
   }
   __syncthreads();

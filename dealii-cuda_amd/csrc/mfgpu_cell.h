@@ -48,7 +48,7 @@ __device__ __forceinline__ void lds_load(const T *p, int stride, T (&v)[n]) {
   for (int i = 0; i < n; ++i) v[i] = p[i * stride];
 }
 template <int n, typename T>
-__device__ __forceinline__ void lds_store(T *p, int stride, const T (&v)[n]) {
+__device__ __forceinline__ void lds_put(T *p, int stride, const T (&v)[n]) {
 #pragma unroll
   for (int i = 0; i < n; ++i) p[i * stride] = v[i];
 }
@@ -224,20 +224,20 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       bool type;
       if (act) {
         if (mask && hn_flag3<n, 0>(mask, pa, pb, type)) hn_pencil<n, T, false>(Wl, type, u);
-        lds_store<n>(Wc + bx, 1, u);
+        lds_put<n>(Wc + bx, 1, u);
       }
       Sync::sync();
       // only the pencils on a constrained face or edge change: everybody else skips the round trip
       if (act && mask && hn_flag3<n, 1>(mask, pb, pa, type)) {
         lds_load<n>(Wc + by, n, u);
         hn_pencil<n, T, false>(Wl, type, u);
-        lds_store<n>(Wc + by, n, u);
+        lds_put<n>(Wc + by, n, u);
       }
       Sync::sync();
       if (act && mask && hn_flag3<n, 2>(mask, pa, pb, type)) {
         lds_load<n>(Wc + bz, n2, u);
         hn_pencil<n, T, false>(Wl, type, u);
-        lds_store<n>(Wc + bz, n2, u);
+        lds_put<n>(Wc + bz, n2, u);
       }
       Sync::sync();
       if (act) lds_load<n>(Wc + bx, 1, u);  // P0 rewrites the same pencil in place
@@ -245,7 +245,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
     // P0: interpolate along x
     if (act) {
       mvt<n, 1>(tab.S, u, v);
-      lds_store<n>(Wc + bx, 1, v);
+      lds_put<n>(Wc + bx, 1, v);
     }
     Sync::sync();
     PSTAMP(1);
@@ -253,7 +253,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
     if (act) {
       lds_load<n>(Wc + by, n, u);
       mvt<n, 1>(tab.S, u, v);
-      lds_store<n>(Wc + by, n, v);
+      lds_put<n>(Wc + by, n, v);
     }
     Sync::sync();
     PSTAMP(2);
@@ -266,8 +266,8 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
 #pragma unroll
       for (int s = 0; s < n; ++s) g[s] *= v[s];
       mvt<n, -1>(tab.Dt, g, r);
-      lds_store<n>(Wc + bz, n2, w);
-      lds_store<n>(Rc + bz, n2, r);
+      lds_put<n>(Wc + bz, n2, w);
+      lds_put<n>(Rc + bz, n2, r);
     }
     Sync::sync();
     PSTAMP(3);
@@ -282,7 +282,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       lds_load<n>(Rc + by, n, v);
 #pragma unroll
       for (int s = 0; s < n; ++s) r[s] += v[s];
-      lds_store<n>(Rc + by, n, r);
+      lds_put<n>(Rc + by, n, r);
     }
     Sync::sync();
     PSTAMP(4);
@@ -298,7 +298,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
 #pragma unroll
       for (int s = 0; s < n; ++s) r[s] += v[s];
       mv<n, 1>(tab.S, r, v);
-      lds_store<n>(Rc + bx, 1, v);
+      lds_put<n>(Rc + bx, 1, v);
     }
     Sync::sync();
     PSTAMP(5);
@@ -307,7 +307,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
     if (act) {
       lds_load<n>(Rc + by, n, u);
       mv<n, 1>(tab.S, u, v);
-      lds_store<n>(Rc + by, n, v);
+      lds_put<n>(Rc + by, n, v);
     }
     stage_next();
     Sync::sync();
@@ -323,13 +323,13 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       bool type;
       if (act) {
         if (mask && hn_flag3<n, 2>(mask, pa, pb, type)) hn_pencil<n, T, true>(Wl, type, v);
-        lds_store<n>(Rc + bz, n2, v);
+        lds_put<n>(Rc + bz, n2, v);
       }
       Sync::sync();
       if (act && mask && hn_flag3<n, 1>(mask, pb, pa, type)) {
         lds_load<n>(Rc + by, n, v);
         hn_pencil<n, T, true>(Wl, type, v);
-        lds_store<n>(Rc + by, n, v);
+        lds_put<n>(Rc + by, n, v);
       }
       Sync::sync();
       if (act) {
@@ -348,13 +348,13 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       bool type;
       if (act) {
         if (mask && hn_flag2<n, 0>(mask, pa, type)) hn_pencil<n, T, false>(Wl, type, u);
-        lds_store<n>(Wc + bx, 1, u);
+        lds_put<n>(Wc + bx, 1, u);
       }
       Sync::sync();
       if (act && mask && hn_flag2<n, 1>(mask, pa, type)) {
         lds_load<n>(Wc + by, n, u);
         hn_pencil<n, T, false>(Wl, type, u);
-        lds_store<n>(Wc + by, n, u);
+        lds_put<n>(Wc + by, n, u);
       }
       Sync::sync();
       if (act) lds_load<n>(Wc + bx, 1, u);
@@ -362,7 +362,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
     // P0: interpolate along x
     if (act) {
       mvt<n, 1>(tab.S, u, v);
-      lds_store<n>(Wc + bx, 1, v);
+      lds_put<n>(Wc + bx, 1, v);
     }
     Sync::sync();
     // P1: interpolate along y; y-derivative part
@@ -374,8 +374,8 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
 #pragma unroll
       for (int s = 0; s < n; ++s) g[s] *= v[s];
       mvt<n, -1>(tab.Dt, g, r);
-      lds_store<n>(Wc + by, n, w);
-      lds_store<n>(Rc + by, n, r);
+      lds_put<n>(Wc + by, n, w);
+      lds_put<n>(Rc + by, n, r);
     }
     Sync::sync();
     // P2: x-derivative part, S^T along x
@@ -390,7 +390,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
 #pragma unroll
       for (int s = 0; s < n; ++s) r[s] += v[s];
       mv<n, 1>(tab.S, r, v);
-      lds_store<n>(Rc + bx, 1, v);
+      lds_put<n>(Rc + bx, 1, v);
     }
     Sync::sync();
     // P3: S^T along y, scatter-add
@@ -402,7 +402,7 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       bool type;
       if (act) {
         if (mask && hn_flag2<n, 1>(mask, pa, type)) hn_pencil<n, T, true>(Wl, type, v);
-        lds_store<n>(Rc + by, n, v);
+        lds_put<n>(Rc + by, n, v);
       }
       Sync::sync();
       if (act) {

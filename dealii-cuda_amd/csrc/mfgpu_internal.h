@@ -138,18 +138,18 @@ struct HnLine {
 };
 void hn_cell_lines(unsigned mask, int n, std::vector<HnLine> (&lines)[3], std::vector<uint16_t> &nodes);
 
-// Which cell-loop kernel family serves a description (mfgpu_desc.kernel; 0 = the library's choice), and the plan
-// built for it -- shared by mfgpu_create and the host-only mfgpu_plan_create:
-//   planes   apply_planes3: 3D, uniform-Jacobian path, two-pass mode, p = 4 by default (p = 2, 3 on request:
-//            mfgpu_desc.kernel = MFGPU_KERNEL_PLANES); on meshes with hanging nodes it takes the batches of cells
-//            without a constraint mask (Plan::n_plane_batches) and pencils_x is set as well for the others
-//   pencils_x apply_batches_x: 3D two-pass otherwise
-//   general  apply_batches_g: no MFGPU_UNIFORM_J0
-//   none of them: apply_batches (2D, coloured-scatter mode)
-struct KernelChoice {
-  bool planes = false, pencils_x = false, general = false;
-};
-int choose_kernel_and_plan(const mfgpu_desc &d, KernelChoice &kc, Plan &plan);
+// Which cell-loop kernel families serve a description (mfgpu_desc.kernel; 0 = the library's choice), and the plan
+// built for them -- shared by mfgpu_create and the host-only mfgpu_plan_create.  The plane family takes the first
+// Plan::n_plane_batches batches (> 0 exactly when it is not none), the batch family the rest:
+//   planes3 / planes4  apply_planes3 / apply_planes4: 3D, uniform-Jacobian path, two-pass mode, by default p >= 4
+//                      and p = 3 in double or with hanging nodes (p = 2, 3 on request: MFGPU_KERNEL_PLANES, _PLANES_2W);
+//                      on meshes with hanging nodes the batches of masked cells may be left to apply_batches_x
+//   x                  apply_batches_x: 3D two-pass otherwise
+//   g / g2             apply_batches_g / apply_batches_g2: no MFGPU_UNIFORM_J0, 3D / 2D
+//   batches            apply_batches: 2D uniform-Jacobian, coloured-scatter mode, MFGPU_KERNEL_PENCILS
+enum class PlaneKernel : uint8_t { none, planes3, planes4 };
+enum class BatchKernel : uint8_t { none, batches, x, g, g2 };
+int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk, Plan &plan);
 int build_plane_records(Plan &plan, const uint32_t *constraint_mask);
 
 // Derive the kernel's 1D tables from the reference-layout tables T[dof*n+q]:

@@ -49,47 +49,67 @@ struct Tables {
   T Dt[((n + 1) / 2) * n];  // Dt[q*n+t] = l_t'(x_q), rows q < (n+1)/2 (rest by antisymmetry)
 };
 
-template <typename T>
-size_t apply_lds_bytes(int dim, int n, uint32_t nb_max);
-template <typename T>
-hipError_t apply_configure(int dim, int n, size_t lds);
-template <typename T>
-hipError_t apply_launch(int dim, int n, const ApplyArgs<T> &a, const double *S, const double *Dt,
-                        bool hn, bool twopass, uint32_t grid, hipStream_t st);
-template <typename T>
-hipError_t apply_occupancy(int dim, int n, bool hn, bool twopass, size_t lds, int *blocks);
+// the kernel-argument tables of the pencil kernels from the host tables S, Dt
+template <typename T, int n>
+inline Tables<T, n> make_tables(const double *S, const double *Dt) {
+  Tables<T, n> tab;
+  for (int i = 0; i < ((n + 1) / 2) * n; ++i) {
+    tab.S[i] = (T)S[i];
+    tab.Dt[i] = (T)Dt[i];
+  }
+  return tab;
+}
+
+// sets a kernel's dynamic LDS size and returns its resident workgroups per CU
+inline hipError_t configure_kernel(const void *kernel, size_t lds, int block, int *blocks) {
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  return e == hipSuccess ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kernel, block, lds) : e;
+}
+
+// The six cell-loop kernel families, one launcher pair each (mfgpu_api.hip family_configure / family_launch):
+// F_configure sets the LDS attribute for (n, hn[, dim, twopass]) and returns the LDS bytes (written first) and the
+// workgroups per CU; F_launch runs batches [a.batch0, a.batch_end).  apply: apply_batches, x: apply_batches_x, g / g2:
+// apply_batches_g / _g2 (g2 reads a.tabS, a.tabDt instead of S, Dt), p / q: apply_planes3 / apply_planes4.
+#define MFGPU_CELL_LOOP_LAUNCHERS(F)                                                                               \
+  template <typename T>                                                                                            \
+  hipError_t F##_configure(int dim, int n, bool hn, bool twopass, uint32_t nb_max, size_t *lds, int *blocks);     \
+  template <typename T>                                                                                            \
+  hipError_t F##_launch(int dim, int n, bool hn, bool twopass, const ApplyArgs<T> &a, const double *S,            \
+                        const double *Dt, uint32_t grid, hipStream_t st);
+MFGPU_CELL_LOOP_LAUNCHERS(apply)
+MFGPU_CELL_LOOP_LAUNCHERS(x)
+MFGPU_CELL_LOOP_LAUNCHERS(g)
+MFGPU_CELL_LOOP_LAUNCHERS(g2)
+MFGPU_CELL_LOOP_LAUNCHERS(p)
+MFGPU_CELL_LOOP_LAUNCHERS(q)
+#undef MFGPU_CELL_LOOP_LAUNCHERS
+// (x, g, g2) dispatch of the run-time degree n = 2 .. 7 and hanging-node switch hn onto FN<n, T, HN>(...)
+#define MFGPU_SWITCH_N_HN(FN, ...)                                                                \
+  switch (n) {                                                                                    \
+    case 2: return hn ? FN<2, T, true>(__VA_ARGS__) : FN<2, T, false>(__VA_ARGS__);               \
+    case 3: return hn ? FN<3, T, true>(__VA_ARGS__) : FN<3, T, false>(__VA_ARGS__);               \
+    case 4: return hn ? FN<4, T, true>(__VA_ARGS__) : FN<4, T, false>(__VA_ARGS__);               \
+    case 5: return hn ? FN<5, T, true>(__VA_ARGS__) : FN<5, T, false>(__VA_ARGS__);               \
+    case 6: return hn ? FN<6, T, true>(__VA_ARGS__) : FN<6, T, false>(__VA_ARGS__);               \
+    case 7: return hn ? FN<7, T, true>(__VA_ARGS__) : FN<7, T, false>(__VA_ARGS__);               \
+    default: return hipErrorInvalidValue;                                                         \
+  }
+
 // pass 2, class-sorted structure-of-arrays form (mfgpu_pass2.hip)
 void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<uint32_t> &s_off,
                          const std::vector<uint32_t> &s_idx, std::vector<uint32_t> &arr, std::vector<uint32_t> &tiles);
 template <typename T>
 hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint32_t *arr, const uint32_t *tiles,
                                  uint32_t n_tiles, int add, hipStream_t st);
-// 3D cell loop for three workgroups per CU (mfgpu_kernels_x.hip; two-pass mode)
-template <typename T>
-hipError_t x_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy);
-// plane-per-thread cell loop (mfgpu_kernels_p.hip; 3D, two-pass mode, uniform-Jacobian path) and its setup relayout
-template <typename T>
-hipError_t p_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy);
-// ... two waves per SIMD (mfgpu_kernels_q.hip): same records, same arguments
-template <typename T>
-hipError_t q_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy);
+// setup relayout of the folded coefficient for the plane kernels (mfgpu_kernels_p.hip)
 template <typename T>
 hipError_t relayout_coef_launch(T *out, const T *in, const uint32_t *cell_batch, const uint32_t *cell_pos,
                                 size_t total, int n, hipStream_t st);
-// general-Jacobian cell loop (mfgpu_kernels_g.hip; 3D, two-pass mode, conforming meshes) and its setup fold
-template <typename T>
-hipError_t g_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy);
+// setup folds of the general-Jacobian kernels: 6 (3D, mfgpu_kernels_g.hip) or 3 (2D, mfgpu_kernels_g2.hip) metric
+// entries per point
 template <typename T>
 hipError_t fold_general_launch(T *M, const T *coef, const T *jxw, const T *jinv, const uint32_t *order,
                                uint32_t n_cells, uint32_t nd, hipStream_t st);
-// general-Jacobian cell loop in 2D (mfgpu_kernels_g2.hip; two-pass mode) and its setup fold (3 metric entries per point)
-template <typename T>
-hipError_t g2_launch(int n, const ApplyArgs<T> &a, bool hn, uint32_t grid, hipStream_t st, bool configure_only,
-                     size_t *lds_out, int *occupancy);
 template <typename T>
 hipError_t fold_general2_launch(T *M, const T *coef, const T *jxw, const T *jinv, const uint32_t *order,
                                 uint32_t n_cells, uint32_t nd, hipStream_t st);

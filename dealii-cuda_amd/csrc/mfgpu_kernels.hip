@@ -375,11 +375,7 @@ static hipError_t launch_k(const ApplyArgs<T> &a, const Tables<T, n> &tab, size_
 template <int dim, int n, typename T>
 static hipError_t launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn,
                            bool twopass, uint32_t grid, hipStream_t st) {
-  Tables<T, n> tab;
-  for (int i = 0; i < ((n + 1) / 2) * n; ++i) {
-    tab.S[i] = (T)S[i];
-    tab.Dt[i] = (T)Dt[i];
-  }
+  const Tables<T, n> tab = make_tables<T, n>(S, Dt);
   const size_t lds = lds_bytes_t<dim, n, T>(a.nb_max);
   return MFGPU_SWITCH(launch_k, a, tab, lds, grid, st);
 }
@@ -390,7 +386,7 @@ static hipError_t configure_k(size_t lds) {
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 template <int dim, int n, typename T>
-static hipError_t configure_t(size_t lds) {
+static hipError_t attributes_t(size_t lds) {
   hipError_t e = hipSuccess;
   for (int hn_ = 0; hn_ < 2 && e == hipSuccess; ++hn_)
     for (int tp_ = 0; tp_ < 2 && e == hipSuccess; ++tp_) {
@@ -404,9 +400,13 @@ template <int dim, int n, typename T, bool HN, bool TP>
 static hipError_t occupancy_k(size_t lds, int *blocks) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, apply_batches<dim, n, T, HN, TP>, 256, lds);
 }
+// the attribute goes to all four instantiations, the occupancy is that of (hn, twopass)
 template <int dim, int n, typename T>
-static hipError_t occupancy_t(bool hn, bool twopass, size_t lds, int *blocks) {
-  return MFGPU_SWITCH(occupancy_k, lds, blocks);
+static hipError_t configure_t(bool hn, bool twopass, uint32_t nb_max, size_t *lds_out, int *blocks) {
+  const size_t lds = lds_bytes_t<dim, n, T>(nb_max);
+  *lds_out = lds;
+  const hipError_t e = attributes_t<dim, n, T>(lds);
+  return e == hipSuccess ? MFGPU_SWITCH(occupancy_k, lds, blocks) : e;
 }
 
 #define MFGPU_DISPATCH(CALL)                                \
@@ -427,43 +427,15 @@ static hipError_t occupancy_t(bool hn, bool twopass, size_t lds, int *blocks) {
   }
 
 template <typename T>
-size_t apply_lds_bytes(int dim, int n, uint32_t nb_max) {
-#define CALL(D, N) lds_bytes_t<D, N, T>(nb_max)
-  switch (dim * 10 + n) {
-    case 22: return CALL(2, 2);
-    case 23: return CALL(2, 3);
-    case 24: return CALL(2, 4);
-    case 25: return CALL(2, 5);
-    case 26: return CALL(2, 6);
-    case 27: return CALL(2, 7);
-    case 32: return CALL(3, 2);
-    case 33: return CALL(3, 3);
-    case 34: return CALL(3, 4);
-    case 35: return CALL(3, 5);
-    case 36: return CALL(3, 6);
-    case 37: return CALL(3, 7);
-    default: return 0;
-  }
-#undef CALL
-}
-
-template <typename T>
-hipError_t apply_configure(int dim, int n, size_t lds) {
-#define CALL(D, N) configure_t<D, N, T>(lds)
+hipError_t apply_configure(int dim, int n, bool hn, bool twopass, uint32_t nb_max, size_t *lds, int *blocks) {
+#define CALL(D, N) configure_t<D, N, T>(hn, twopass, nb_max, lds, blocks)
   MFGPU_DISPATCH(CALL)
 #undef CALL
 }
 
 template <typename T>
-hipError_t apply_occupancy(int dim, int n, bool hn, bool twopass, size_t lds, int *blocks) {
-#define CALL(D, N) occupancy_t<D, N, T>(hn, twopass, lds, blocks)
-  MFGPU_DISPATCH(CALL)
-#undef CALL
-}
-
-template <typename T>
-hipError_t apply_launch(int dim, int n, const ApplyArgs<T> &a, const double *S, const double *Dt,
-                        bool hn, bool twopass, uint32_t grid, hipStream_t st) {
+hipError_t apply_launch(int dim, int n, bool hn, bool twopass, const ApplyArgs<T> &a, const double *S,
+                        const double *Dt, uint32_t grid, hipStream_t st) {
 #define CALL(D, N) launch_t<D, N, T>(a, S, Dt, hn, twopass, grid, st)
   MFGPU_DISPATCH(CALL)
 #undef CALL
@@ -506,11 +478,9 @@ hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
 }
 
 #define INST(T)                                                                                         \
-  template size_t apply_lds_bytes<T>(int, int, uint32_t);                                               \
-  template hipError_t apply_configure<T>(int, int, size_t);                                             \
-  template hipError_t apply_occupancy<T>(int, int, bool, bool, size_t, int *);                          \
-  template hipError_t apply_launch<T>(int, int, const ApplyArgs<T> &, const double *, const double *,   \
-                                      bool, bool, uint32_t, hipStream_t);                               \
+  template hipError_t apply_configure<T>(int, int, bool, bool, uint32_t, size_t *, int *);             \
+  template hipError_t apply_launch<T>(int, int, bool, bool, const ApplyArgs<T> &, const double *,       \
+                                      const double *, uint32_t, hipStream_t);                           \
   template hipError_t orphan_launch<T>(T *, const T *, const uint32_t *, uint32_t, int, hipStream_t);   \
   template hipError_t coefficient_launch<T>(T *, const T *, size_t, int, hipStream_t);                  \
   template hipError_t fold_launch<T>(T *, const T *, const T *, const T *, const uint32_t *, uint32_t,  \

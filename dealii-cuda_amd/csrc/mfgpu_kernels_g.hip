@@ -217,19 +217,19 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
         bool type;
         if (act) {
           if (mask && hn_flag3<n, 0>(mask, pa, pb, type)) hn_pencil<n, T, false, true>(Wl, type, U[k]);
-          lds_store<n>(Wc + bx, 1, U[k]);
+          lds_put<n>(Wc + bx, 1, U[k]);
         }
         __syncthreads();
         if (act && mask && hn_flag3<n, 1>(mask, pb, pa, type)) {
           lds_load<n>(Wc + by, n, u);
           hn_pencil<n, T, false, true>(Wl, type, u);
-          lds_store<n>(Wc + by, n, u);
+          lds_put<n>(Wc + by, n, u);
         }
         __syncthreads();
         if (act && mask && hn_flag3<n, 2>(mask, pa, pb, type)) {
           lds_load<n>(Wc + bz, n2, u);
           hn_pencil<n, T, false, true>(Wl, type, u);
-          lds_store<n>(Wc + bz, n2, u);
+          lds_put<n>(Wc + bz, n2, u);
         }
         __syncthreads();
         if (act) lds_load<n>(Wc + bx, 1, U[k]);
@@ -237,14 +237,14 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
       // P0: interpolate along x
       if (act) {
         mvt<n, 1>(tab.S, U[k], v);
-        lds_store<n>(Wc + bx, 1, v);
+        lds_put<n>(Wc + bx, 1, v);
       }
       __syncthreads();
       // P1: interpolate along y
       if (act) {
         lds_load<n>(Wc + by, n, u);
         mvt<n, 1>(tab.S, u, v);
-        lds_store<n>(Wc + by, n, v);
+        lds_put<n>(Wc + by, n, v);
       }
       __syncthreads();
       // P2: interpolate along z -> values at the quadrature points; z-derivative
@@ -252,22 +252,22 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
         lds_load<n>(Wc + bz, n2, u);
         mvt<n, 1>(tab.S, u, w);
         mv<n, -1>(tab.Dt, w, g);
-        lds_store<n>(Wc + bz, n2, w);
-        lds_store<n>(Gzc + bz, n2, g);
+        lds_put<n>(Wc + bz, n2, w);
+        lds_put<n>(Gzc + bz, n2, g);
       }
       __syncthreads();
       // P3: x-derivative
       if (act) {
         lds_load<n>(Wc + bx, 1, w);
         mv<n, -1>(tab.Dt, w, g);
-        lds_store<n>(Gxc + bx, 1, g);
+        lds_put<n>(Gxc + bx, 1, g);
       }
       __syncthreads();
       // P4: y-derivative (last read of w: the array becomes the result r)
       if (act) {
         lds_load<n>(Wc + by, n, w);
         mv<n, -1>(tab.Dt, w, g);
-        lds_store<n>(Gyc + by, n, g);
+        lds_put<n>(Gyc + by, n, g);
       }
       __syncthreads();
       // P5: quadrature-point operation t = M ghat, points in linear order (the chunk's cells are contiguous)
@@ -289,7 +289,7 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
       if (act) {
         lds_load<n>(Gzc + bz, n2, g);
         mvt<n, -1>(tab.Dt, g, v);
-        lds_store<n>(Wc + bz, n2, v);
+        lds_put<n>(Wc + bz, n2, v);
       }
       __syncthreads();
       // P7: r += D_x^T tx
@@ -299,7 +299,7 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
         mvt<n, -1>(tab.Dt, g, v);
 #pragma unroll
         for (int s = 0; s < n; ++s) v[s] += u[s];
-        lds_store<n>(Wc + bx, 1, v);
+        lds_put<n>(Wc + bx, 1, v);
       }
       __syncthreads();
       // P8: r += D_y^T ty, then S^T along y
@@ -310,14 +310,14 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
 #pragma unroll
         for (int s = 0; s < n; ++s) w[s] += u[s];
         mv<n, 1>(tab.S, w, v);
-        lds_store<n>(Wc + by, n, v);
+        lds_put<n>(Wc + by, n, v);
       }
       __syncthreads();
       // P9: S^T along z
       if (act) {
         lds_load<n>(Wc + bz, n2, u);
         mv<n, 1>(tab.S, u, v);
-        lds_store<n>(Wc + bz, n2, v);
+        lds_put<n>(Wc + bz, n2, v);
       }
       __syncthreads();
       // P10: S^T along x, add into the batch accumulator (each thread re-uses its own pencil of the array in
@@ -329,18 +329,18 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
       if (HN && any_mask) {
         // resolve_hanging_nodes_shmem<TRANSPOSE>: the passes commute; y, z, then x (the index set's pencil)
         bool type;
-        if (act) lds_store<n>(Wc + bx, 1, v);
+        if (act) lds_put<n>(Wc + bx, 1, v);
         __syncthreads();
         if (act && mask && hn_flag3<n, 1>(mask, pb, pa, type)) {
           lds_load<n>(Wc + by, n, v);
           hn_pencil<n, T, true, true>(Wl, type, v);
-          lds_store<n>(Wc + by, n, v);
+          lds_put<n>(Wc + by, n, v);
         }
         __syncthreads();
         if (act && mask && hn_flag3<n, 2>(mask, pa, pb, type)) {
           lds_load<n>(Wc + bz, n2, v);
           hn_pencil<n, T, true, true>(Wl, type, v);
-          lds_store<n>(Wc + bz, n2, v);
+          lds_put<n>(Wc + bz, n2, v);
         }
         __syncthreads();
         if (act) {
@@ -423,38 +423,28 @@ static size_t g_lds_bytes(uint32_t nb_max) {
 }
 
 template <int n, typename T, bool HN>
-static hipError_t g_run(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st,
-                        bool configure_only, size_t *lds_out, int *occupancy) {
+static hipError_t g_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
+  *lds = g_lds_bytes<n, T>(nb_max);
+  return configure_kernel((const void *)apply_batches_g<n, T, HN>, *lds, 256, blocks);
+}
+
+template <int n, typename T, bool HN>
+static hipError_t g_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
+  const Tables<T, n> tab = make_tables<T, n>(S, Dt);
   const size_t lds = g_lds_bytes<n, T>(a.nb_max);
-  if (lds_out) *lds_out = lds;
-  if (configure_only) {
-    hipError_t e = hipFuncSetAttribute((const void *)apply_batches_g<n, T, HN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && occupancy)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_batches_g<n, T, HN>, 256, lds);
-    return e;
-  }
-  Tables<T, n> tab;
-  for (int i = 0; i < ((n + 1) / 2) * n; ++i) {
-    tab.S[i] = (T)S[i];
-    tab.Dt[i] = (T)Dt[i];
-  }
   hipLaunchKernelGGL((apply_batches_g<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t g_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy) {
-#define G_CASE(N)                                                                                 \
-  case N:                                                                                         \
-    return hn ? g_run<N, T, true>(a, S, Dt, grid, st, configure_only, lds_out, occupancy)         \
-              : g_run<N, T, false>(a, S, Dt, grid, st, configure_only, lds_out, occupancy);
-  switch (n) {
-    G_CASE(2) G_CASE(3) G_CASE(4) G_CASE(5) G_CASE(6) G_CASE(7)
-    default: return hipErrorInvalidValue;
-  }
-#undef G_CASE
+hipError_t g_configure(int, int n, bool hn, bool, uint32_t nb_max, size_t *lds, int *blocks) {
+  MFGPU_SWITCH_N_HN(g_configure_t, nb_max, lds, blocks)
+}
+
+template <typename T>
+hipError_t g_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+                    hipStream_t st) {
+  MFGPU_SWITCH_N_HN(g_launch_t, a, S, Dt, grid, st)
 }
 
 template <typename T>
@@ -467,8 +457,9 @@ hipError_t fold_general_launch(T *M, const T *coef, const T *jxw, const T *jinv,
 }
 
 #define INST(T)                                                                                              \
-  template hipError_t g_launch<T>(int, const ApplyArgs<T> &, const double *, const double *, bool, uint32_t,        \
-                                  hipStream_t, bool, size_t *, int *);                                                    \
+  template hipError_t g_configure<T>(int, int, bool, bool, uint32_t, size_t *, int *);                          \
+  template hipError_t g_launch<T>(int, int, bool, bool, const ApplyArgs<T> &, const double *, const double *,    \
+                                  uint32_t, hipStream_t);                                                      \
   template hipError_t fold_general_launch<T>(T *, const T *, const T *, const T *, const uint32_t *, uint32_t, \
                                              uint32_t, hipStream_t);
 INST(double)

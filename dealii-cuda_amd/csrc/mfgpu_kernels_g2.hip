@@ -182,44 +182,38 @@ size_t g2_lds_bytes(uint32_t nb_max) {
   return (size_t)nb_max * sizeof(double) + ((size_t)nb_max + 4 * CH * nd + 3 * nd) * sizeof(T);
 }
 
-template <int n, typename T>
-hipError_t g2_run(const ApplyArgs<T> &a, bool hn, uint32_t grid, hipStream_t st, bool configure_only, size_t *lds_out,
-                  int *occupancy) {
+template <int n, typename T, bool HN>
+hipError_t g2_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
+  *lds = g2_lds_bytes<n, T>(nb_max);
+  return configure_kernel((const void *)apply_batches_g2<n, T, HN>, *lds, 256, blocks);
+}
+
+template <int n, typename T, bool HN>
+hipError_t g2_launch_t(const ApplyArgs<T> &a, uint32_t grid, hipStream_t st) {
   const size_t lds = g2_lds_bytes<n, T>(a.nb_max);
-  if (lds_out) *lds_out = lds;
-  const void *fn = hn ? (const void *)apply_batches_g2<n, T, true> : (const void *)apply_batches_g2<n, T, false>;
-  if (configure_only) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && occupancy) {
-      e = hn ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_batches_g2<n, T, true>, 256, lds)
-             : hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_batches_g2<n, T, false>, 256, lds);
-    }
-    return e;
-  }
-  if (hn)
-    hipLaunchKernelGGL((apply_batches_g2<n, T, true>), dim3(grid), dim3(256), lds, st, a);
-  else
-    hipLaunchKernelGGL((apply_batches_g2<n, T, false>), dim3(grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((apply_batches_g2<n, T, HN>), dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
 }  // namespace
 
 template <typename T>
-hipError_t g2_launch(int n, const ApplyArgs<T> &a, bool hn, uint32_t grid, hipStream_t st, bool configure_only,
-                     size_t *lds_out, int *occupancy) {
-  switch (n) {
-    case 2: return g2_run<2, T>(a, hn, grid, st, configure_only, lds_out, occupancy);
-    case 3: return g2_run<3, T>(a, hn, grid, st, configure_only, lds_out, occupancy);
-    case 4: return g2_run<4, T>(a, hn, grid, st, configure_only, lds_out, occupancy);
-    case 5: return g2_run<5, T>(a, hn, grid, st, configure_only, lds_out, occupancy);
-    case 6: return g2_run<6, T>(a, hn, grid, st, configure_only, lds_out, occupancy);
-    case 7: return g2_run<7, T>(a, hn, grid, st, configure_only, lds_out, occupancy);
-    default: return hipErrorInvalidValue;
-  }
+hipError_t g2_configure(int, int n, bool hn, bool, uint32_t nb_max, size_t *lds, int *blocks) {
+  MFGPU_SWITCH_N_HN(g2_configure_t, nb_max, lds, blocks)
 }
-template hipError_t g2_launch<double>(int, const ApplyArgs<double> &, bool, uint32_t, hipStream_t, bool, size_t *, int *);
-template hipError_t g2_launch<float>(int, const ApplyArgs<float> &, bool, uint32_t, hipStream_t, bool, size_t *, int *);
+
+// (the 1D tables come from a.tabS / a.tabDt on the device, not from S, Dt)
+template <typename T>
+hipError_t g2_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *, const double *, uint32_t grid,
+                     hipStream_t st) {
+  MFGPU_SWITCH_N_HN(g2_launch_t, a, grid, st)
+}
+template hipError_t g2_configure<double>(int, int, bool, bool, uint32_t, size_t *, int *);
+template hipError_t g2_configure<float>(int, int, bool, bool, uint32_t, size_t *, int *);
+template hipError_t g2_launch<double>(int, int, bool, bool, const ApplyArgs<double> &, const double *, const double *,
+                                      uint32_t, hipStream_t);
+template hipError_t g2_launch<float>(int, int, bool, bool, const ApplyArgs<float> &, const double *, const double *,
+                                     uint32_t, hipStream_t);
 
 template <typename T>
 hipError_t fold_general2_launch(T *M, const T *coef, const T *jxw, const T *jinv, const uint32_t *order,

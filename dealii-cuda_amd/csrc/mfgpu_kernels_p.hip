@@ -527,20 +527,18 @@ static size_t p_lds_bytes(bool hn) {
 }
 
 template <int n, typename T>
-static hipError_t p_run(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid, hipStream_t st,
-                        bool configure_only, size_t *lds_out, int *occupancy) {
+static hipError_t p_configure_t(bool hn, size_t *lds, int *blocks) {
+  *lds = p_lds_bytes<n, T>(hn);
+  const void *f0 = hn ? (const void *)apply_planes3<n, T, false, true> : (const void *)apply_planes3<n, T, false, false>;
+  const void *f1 = hn ? (const void *)apply_planes3<n, T, true, true> : (const void *)apply_planes3<n, T, true, false>;
+  const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+  return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
+}
+
+template <int n, typename T>
+static hipError_t p_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
+                             hipStream_t st) {
   const size_t lds = p_lds_bytes<n, T>(hn);
-  if (lds_out) *lds_out = lds;
-  if (configure_only) {
-    const void *f0 = hn ? (const void *)apply_planes3<n, T, false, true> : (const void *)apply_planes3<n, T, false, false>;
-    const void *f1 = hn ? (const void *)apply_planes3<n, T, true, true> : (const void *)apply_planes3<n, T, true, false>;
-    hipError_t e = hipFuncSetAttribute(f0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && occupancy)
-      e = hn ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_planes3<n, T, false, true>, 64, lds)
-             : hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_planes3<n, T, false, false>, 64, lds);
-    return e;
-  }
   const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
   if (hn) {
     if (a.add)
@@ -556,21 +554,30 @@ static hipError_t p_run(const ApplyArgs<T> &a, const double *S, const double *Dt
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t p_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy) {
-  switch (n) {
-    case 3: return p_run<3, T>(a, S, Dt, hn, grid, st, configure_only, lds_out, occupancy);
-    case 4: return p_run<4, T>(a, S, Dt, hn, grid, st, configure_only, lds_out, occupancy);
-    case 5: return p_run<5, T>(a, S, Dt, hn, grid, st, configure_only, lds_out, occupancy);
-    default: return hipErrorInvalidValue;
+#define P_SWITCH(FN, ...)                 \
+  switch (n) {                            \
+    case 3: return FN<3, T>(__VA_ARGS__); \
+    case 4: return FN<4, T>(__VA_ARGS__); \
+    case 5: return FN<5, T>(__VA_ARGS__); \
+    default: return hipErrorInvalidValue; \
   }
+template <typename T>
+hipError_t p_configure(int, int n, bool hn, bool, uint32_t, size_t *lds, int *blocks) {
+  P_SWITCH(p_configure_t, hn, lds, blocks)
 }
+template <typename T>
+hipError_t p_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+                    hipStream_t st) {
+  P_SWITCH(p_launch_t, a, S, Dt, hn, grid, st)
+}
+#undef P_SWITCH
 
-template hipError_t p_launch<double>(int, const ApplyArgs<double> &, const double *, const double *, bool, uint32_t,
-                                     hipStream_t, bool, size_t *, int *);
-template hipError_t p_launch<float>(int, const ApplyArgs<float> &, const double *, const double *, bool, uint32_t,
-                                    hipStream_t, bool, size_t *, int *);
+template hipError_t p_configure<double>(int, int, bool, bool, uint32_t, size_t *, int *);
+template hipError_t p_configure<float>(int, int, bool, bool, uint32_t, size_t *, int *);
+template hipError_t p_launch<double>(int, int, bool, bool, const ApplyArgs<double> &, const double *, const double *,
+                                     uint32_t, hipStream_t);
+template hipError_t p_launch<float>(int, int, bool, bool, const ApplyArgs<float> &, const double *, const double *,
+                                    uint32_t, hipStream_t);
 
 // coefficient in plan cell order [cell][q] -> per batch [row r = y + n z][NT tasks = cell_in_batch * n + x]
 // (fixed record size n*n*NT per batch; the tasks of a ragged batch's missing cells stay zero)

@@ -487,18 +487,16 @@ apply_planes4w(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
 }
 
 template <int n, typename T>
-static hipError_t q_run_w(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st,
-                          bool configure_only, size_t *lds_out, int *occupancy) {
+static hipError_t q_configure_w(size_t *lds, int *blocks) {
+  *lds = q_lds_bytes<T>(n, false);
+  const void *f0 = (const void *)apply_planes4w<n, T, false>, *f1 = (const void *)apply_planes4w<n, T, true>;
+  const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+  return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;
+}
+
+template <int n, typename T>
+static hipError_t q_launch_w(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
   const size_t lds = q_lds_bytes<T>(n, false);
-  if (lds_out) *lds_out = lds;
-  if (configure_only) {
-    hipError_t e = hipFuncSetAttribute((const void *)apply_planes4w<n, T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)apply_planes4w<n, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && occupancy)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_planes4w<n, T, false>, 64, lds);
-    return e;
-  }
   const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
   if (a.add)
     hipLaunchKernelGGL((apply_planes4w<n, T, true>), dim3(grid), dim3(64), lds, st, a, tab);
@@ -508,20 +506,18 @@ static hipError_t q_run_w(const ApplyArgs<T> &a, const double *S, const double *
 }
 
 template <int n, typename T>
-static hipError_t q_run(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid, hipStream_t st,
-                        bool configure_only, size_t *lds_out, int *occupancy) {
+static hipError_t q_configure_t(bool hn, size_t *lds, int *blocks) {
+  *lds = q_lds_bytes<T>(n, hn);
+  const void *f0 = hn ? (const void *)apply_planes4<n, T, false, true> : (const void *)apply_planes4<n, T, false, false>;
+  const void *f1 = hn ? (const void *)apply_planes4<n, T, true, true> : (const void *)apply_planes4<n, T, true, false>;
+  const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+  return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
+}
+
+template <int n, typename T>
+static hipError_t q_launch_t(bool hn, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+                             hipStream_t st) {
   const size_t lds = q_lds_bytes<T>(n, hn);
-  if (lds_out) *lds_out = lds;
-  if (configure_only) {
-    const void *f0 = hn ? (const void *)apply_planes4<n, T, false, true> : (const void *)apply_planes4<n, T, false, false>;
-    const void *f1 = hn ? (const void *)apply_planes4<n, T, true, true> : (const void *)apply_planes4<n, T, true, false>;
-    hipError_t e = hipFuncSetAttribute(f0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && occupancy)
-      e = hn ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_planes4<n, T, false, true>, 64, lds)
-             : hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_planes4<n, T, false, false>, 64, lds);
-    return e;
-  }
   const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
   if (hn) {
     if (a.add)
@@ -537,22 +533,32 @@ static hipError_t q_run(const ApplyArgs<T> &a, const double *S, const double *Dt
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t q_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy) {
-  switch (n) {
-    case 3: return q_run<3, T>(a, S, Dt, hn, grid, st, configure_only, lds_out, occupancy);
-    case 4: return q_run<4, T>(a, S, Dt, hn, grid, st, configure_only, lds_out, occupancy);
-    case 5: return q_run<5, T>(a, S, Dt, hn, grid, st, configure_only, lds_out, occupancy);
-    case 6: return hn ? hipErrorInvalidValue : q_run_w<6, T>(a, S, Dt, grid, st, configure_only, lds_out, occupancy);
-    case 7: return hn ? hipErrorInvalidValue : q_run_w<7, T>(a, S, Dt, grid, st, configure_only, lds_out, occupancy);
-    default: return hipErrorInvalidValue;
+// p = 5, 6: the one-wave-per-SIMD kernel, no <HN> instantiation
+#define Q_SWITCH(FN, ...)                                                     \
+  switch (n) {                                                                \
+    case 3: return FN##_t<3, T>(hn, __VA_ARGS__);                             \
+    case 4: return FN##_t<4, T>(hn, __VA_ARGS__);                             \
+    case 5: return FN##_t<5, T>(hn, __VA_ARGS__);                             \
+    case 6: return hn ? hipErrorInvalidValue : FN##_w<6, T>(__VA_ARGS__);     \
+    case 7: return hn ? hipErrorInvalidValue : FN##_w<7, T>(__VA_ARGS__);     \
+    default: return hipErrorInvalidValue;                                     \
   }
+template <typename T>
+hipError_t q_configure(int, int n, bool hn, bool, uint32_t, size_t *lds, int *blocks) {
+  Q_SWITCH(q_configure, lds, blocks)
 }
+template <typename T>
+hipError_t q_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+                    hipStream_t st) {
+  Q_SWITCH(q_launch, a, S, Dt, grid, st)
+}
+#undef Q_SWITCH
 
-template hipError_t q_launch<double>(int, const ApplyArgs<double> &, const double *, const double *, bool, uint32_t,
-                                     hipStream_t, bool, size_t *, int *);
-template hipError_t q_launch<float>(int, const ApplyArgs<float> &, const double *, const double *, bool, uint32_t,
-                                    hipStream_t, bool, size_t *, int *);
+template hipError_t q_configure<double>(int, int, bool, bool, uint32_t, size_t *, int *);
+template hipError_t q_configure<float>(int, int, bool, bool, uint32_t, size_t *, int *);
+template hipError_t q_launch<double>(int, int, bool, bool, const ApplyArgs<double> &, const double *, const double *,
+                                     uint32_t, hipStream_t);
+template hipError_t q_launch<float>(int, int, bool, bool, const ApplyArgs<float> &, const double *, const double *,
+                                    uint32_t, hipStream_t);
 
 }  // namespace mfgpu

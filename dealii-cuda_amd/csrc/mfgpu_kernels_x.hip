@@ -54,20 +54,20 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
     bool type;
     if (act) {
       if (mask && hn_flag3<n, 0>(mask, pa, pb, type)) hn_pencil<n, T, false, true>(Wl, type, u);
-      lds_store<n>(Wc + bx, 1, u);
+      lds_put<n>(Wc + bx, 1, u);
     }
     __syncthreads();
     // only the pencils on a constrained face or edge change: everybody else skips the round trip
     if (acty && mask && hn_flag3<n, 1>(mask, pb, pa, type)) {
       lds_load<n>(Wy, n, u);
       hn_pencil<n, T, false, true>(Wl, type, u);
-      lds_store<n>(Wy, n, u);
+      lds_put<n>(Wy, n, u);
     }
     __syncthreads();
     if (actz && mask && hn_flag3<n, 2>(mask, pa, pb, type)) {
       lds_load<n>(Wz, n2, u);
       hn_pencil<n, T, false, true>(Wl, type, u);
-      lds_store<n>(Wz, n2, u);
+      lds_put<n>(Wz, n2, u);
     }
     __syncthreads();
     if (act) lds_load<n>(Wc + bx, 1, u);
@@ -75,14 +75,14 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
   // P0: interpolate along x
   if (act) {
     mvt<n, 1>(tab.S, u, v);
-    lds_store<n>(Wc + bx, 1, v);
+    lds_put<n>(Wc + bx, 1, v);
   }
   __syncthreads();
   // P1: interpolate along y
   if (acty) {
     lds_load<n>(Wy, n, u);
     mvt<n, 1>(tab.S, u, v);
-    lds_store<n>(Wy, n, v);
+    lds_put<n>(Wy, n, v);
   }
   __syncthreads();
   // P2: interpolate along z -> values at the quadrature points; z-derivative part
@@ -94,8 +94,8 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
 #pragma unroll
     for (int s = 0; s < n; ++s) g[s] *= v[s];
     mvt<n, -1>(tab.Dt, g, r);
-    lds_store<n>(Wz, n2, w);
-    lds_store<n>(Rz, n2, r);
+    lds_put<n>(Wz, n2, w);
+    lds_put<n>(Rz, n2, r);
   }
   __syncthreads();
   // P3: x-derivative part
@@ -109,7 +109,7 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
     lds_load<n>(Rc + bx, 1, v);
 #pragma unroll
     for (int s = 0; s < n; ++s) r[s] += v[s];
-    lds_store<n>(Rc + bx, 1, r);
+    lds_put<n>(Rc + bx, 1, r);
   }
   __syncthreads();
   // P4: y-derivative part, then S^T along y
@@ -124,14 +124,14 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
 #pragma unroll
     for (int s = 0; s < n; ++s) r[s] += v[s];
     mv<n, 1>(tab.S, r, v);
-    lds_store<n>(Ry, n, v);
+    lds_put<n>(Ry, n, v);
   }
   __syncthreads();
   // P5: S^T along z; the coefficient buffer is free now (last read in P4)
   if (actz) {
     lds_load<n>(Rz, n2, u);
     mv<n, 1>(tab.S, u, v);
-    lds_store<n>(Rz, n2, v);
+    lds_put<n>(Rz, n2, v);
   }
   stage_next();
   __syncthreads();
@@ -144,18 +144,18 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
     // resolve_hanging_nodes_shmem<TRANSPOSE>; the three passes commute: y, z, then x, whose pencil is
     // the one the index set belongs to (reference order x,y,z: hanging_nodes.cuh:767-777)
     bool type;
-    if (act) lds_store<n>(Rc + bx, 1, v);
+    if (act) lds_put<n>(Rc + bx, 1, v);
     __syncthreads();
     if (acty && mask && hn_flag3<n, 1>(mask, pb, pa, type)) {
       lds_load<n>(Ry, n, v);
       hn_pencil<n, T, true, true>(Wl, type, v);
-      lds_store<n>(Ry, n, v);
+      lds_put<n>(Ry, n, v);
     }
     __syncthreads();
     if (actz && mask && hn_flag3<n, 2>(mask, pa, pb, type)) {
       lds_load<n>(Rz, n2, v);
       hn_pencil<n, T, true, true>(Wl, type, v);
-      lds_store<n>(Rz, n2, v);
+      lds_put<n>(Rz, n2, v);
     }
     __syncthreads();
     if (act) {
@@ -482,48 +482,35 @@ static size_t x_lds_bytes(uint32_t nb_max) {
 }
 
 template <int n, typename T, bool HN>
-static hipError_t x_run(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st,
-                        bool configure_only, size_t *lds_out, int *occupancy) {
+static hipError_t x_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
+  *lds = x_lds_bytes<n, T>(nb_max);
+  return configure_kernel((const void *)apply_batches_x<n, T, HN>, *lds, 256, blocks);
+}
+
+template <int n, typename T, bool HN>
+static hipError_t x_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
+  const Tables<T, n> tab = make_tables<T, n>(S, Dt);
   const size_t lds = x_lds_bytes<n, T>(a.nb_max);
-  if (lds_out) *lds_out = lds;
-  if (configure_only) {
-    hipError_t e = hipFuncSetAttribute((const void *)apply_batches_x<n, T, HN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && occupancy)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, apply_batches_x<n, T, HN>, 256, lds);
-    return e;
-  }
-  Tables<T, n> tab;
-  for (int i = 0; i < ((n + 1) / 2) * n; ++i) {
-    tab.S[i] = (T)S[i];
-    tab.Dt[i] = (T)Dt[i];
-  }
   hipLaunchKernelGGL((apply_batches_x<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t x_launch(int n, const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                    hipStream_t st, bool configure_only, size_t *lds_out, int *occupancy) {
-#define X_CASE(N)                                                                                \
-  case N:                                                                                        \
-    return hn ? x_run<N, T, true>(a, S, Dt, grid, st, configure_only, lds_out, occupancy)        \
-              : x_run<N, T, false>(a, S, Dt, grid, st, configure_only, lds_out, occupancy);
-  switch (n) {
-    X_CASE(2)
-    X_CASE(3)
-    X_CASE(4)
-    X_CASE(5)
-    X_CASE(6)
-    X_CASE(7)
-    default: return hipErrorInvalidValue;
-  }
-#undef X_CASE
+hipError_t x_configure(int, int n, bool hn, bool, uint32_t nb_max, size_t *lds, int *blocks) {
+  MFGPU_SWITCH_N_HN(x_configure_t, nb_max, lds, blocks)
 }
 
-template hipError_t x_launch<double>(int, const ApplyArgs<double> &, const double *, const double *, bool, uint32_t,
-                                     hipStream_t, bool, size_t *, int *);
-template hipError_t x_launch<float>(int, const ApplyArgs<float> &, const double *, const double *, bool, uint32_t,
-                                    hipStream_t, bool, size_t *, int *);
+template <typename T>
+hipError_t x_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+                    hipStream_t st) {
+  MFGPU_SWITCH_N_HN(x_launch_t, a, S, Dt, grid, st)
+}
+
+#define INST(T)                                                                                                    \
+  template hipError_t x_configure<T>(int, int, bool, bool, uint32_t, size_t *, int *);                              \
+  template hipError_t x_launch<T>(int, int, bool, bool, const ApplyArgs<T> &, const double *, const double *,        \
+                                  uint32_t, hipStream_t);
+INST(double)
+INST(float)
 
 }  // namespace mfgpu

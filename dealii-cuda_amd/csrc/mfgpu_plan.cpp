@@ -8,6 +8,7 @@
 // (laplace_operator_gpu.h:221) and the save/load constrained-row kernels
 // (constraint_handler_gpu.cu:247-289) from the hot loop.
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -795,7 +796,7 @@ int build_plane_records(Plan &P, const uint32_t *constraint_mask) {
   return 0;
 }
 
-int choose_kernel_and_plan(const mfgpu_desc &d, KernelChoice &kc, Plan &plan) {
+int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk, Plan &plan) {
   const bool general = !(d.flags & MFGPU_UNIFORM_J0), hn = (d.flags & MFGPU_HANGING_NODES) != 0;
   const bool colored = (d.flags & MFGPU_COLORED_SCATTER) != 0;
   if (d.kernel > MFGPU_KERNEL_PLANES_2W) {
@@ -812,18 +813,17 @@ int choose_kernel_and_plan(const mfgpu_desc &d, KernelChoice &kc, Plan &plan) {
     set_error("mfgpu_desc.kernel: this kernel family does not cover the description (see include/mfgpu.h)");
     return MFGPU_EUNSUPPORTED;
   }
-  kc.general = general;
   // by default the plane kernel serves p = 4 only: at p = 2, 3 the pencil kernel measures faster
   // (on meshes with hanging nodes also p = 3: 0.174 instead of 0.256 ms on the bmop ADAPTIVE_GRID mesh, n_ref = 6)
   // p = 5, 6: apply_planes4 with one wave per SIMD (apply_planes3's two transpose arrays do not fit the LDS there)
   // p = 3: apply_planes4 with two waves per SIMD (16 cells per wave) measures 9 % faster than the pencil kernel per
   // vmult (0.222 vs 0.243 ms at 10^7 dofs; profiles/r03_notes.md); p = 2: the pencil kernel stays ahead
   // (in float the pencil kernel is ahead at p = 3 on conforming meshes: 0.152 vs 0.179 ms)
-  kc.planes = pk_ok && (want_planes || (d.kernel == MFGPU_KERNEL_AUTO &&
-                                        (d.degree >= 4 || (d.degree == 3 && (hn || d.number_type == MFGPU_F64)))));
-  kc.pencils_x = xk_ok && !kc.planes && d.kernel != MFGPU_KERNEL_PENCILS;
+  bool planes = pk_ok && (want_planes || (d.kernel == MFGPU_KERNEL_AUTO &&
+                                     (d.degree >= 4 || (d.degree == 3 && (hn || d.number_type == MFGPU_F64)))));
+  bool pencils_x = xk_ok && !planes && d.kernel != MFGPU_KERNEL_PENCILS;
   PlanLimits lim;
-  if (kc.planes) {
+  if (planes) {
     lim.max_cells = (uint32_t)p_cells_per_wave(d.degree + 1);
     lim.max_dofs = (uint32_t)p_kgu(d.degree + 1) * 64u - 1u;
     lim.interior_max = (uint32_t)p_ji(d.degree + 1) * 64u;
@@ -835,20 +835,28 @@ int choose_kernel_and_plan(const mfgpu_desc &d, KernelChoice &kc, Plan &plan) {
     lim.private_max = (uint32_t)p_priv_max(d.degree + 1);
   }
   // apply_batches_x unrolls 4 chunks at p=3 (64-cell batches = 13^3 dofs like p=4); everything else 3
-  int rc = build_plan(d, plan, (kc.pencils_x && d.degree == 3) ? 4u : 3u, kc.planes ? &lim : nullptr);
-  if (rc == MFGPU_EUNSUPPORTED && kc.planes && d.kernel == MFGPU_KERNEL_AUTO && xk_ok) {
+  int rc = build_plan(d, plan, (pencils_x && d.degree == 3) ? 4u : 3u, planes ? &lim : nullptr);
+  if (rc == MFGPU_EUNSUPPORTED && planes && d.kernel == MFGPU_KERNEL_AUTO && xk_ok) {
     // a cell with more surface dofs than the plane kernel's dof-list slots hold (cannot happen on conforming
     // hexahedral meshes): the pencil kernel has no such limit
-    kc.planes = false;
-    kc.pencils_x = true;
+    planes = false;
+    pencils_x = true;
     plan = Plan();
     rc = build_plan(d, plan, d.degree == 3 ? 4u : 3u, nullptr);
   }
-  if (!rc && kc.planes) {
+  if (!rc && planes) {
     const uint32_t nbat = (uint32_t)plan.batch_cell_off.size() - 1;
-    kc.pencils_x = plan.n_plane_batches < nbat;  // the masked cells' batches
-    if (plan.n_plane_batches == 0) kc.planes = false;
+    pencils_x = plan.n_plane_batches < nbat;  // the masked cells' batches
+    if (plan.n_plane_batches == 0) planes = false;
   }
+  // which plane kernel: apply_planes4 on request, at p = 5, 6 (the only one that fits), and by default at p = 3 in
+  // double; apply_planes3 otherwise (p = 4: equal in double, faster in float)
+  const bool planes4 = d.kernel == MFGPU_KERNEL_PLANES_2W || d.degree >= 5 ||
+                       (d.kernel == MFGPU_KERNEL_AUTO && d.degree == 3 && d.number_type == MFGPU_F64);
+  pk = !planes ? PlaneKernel::none : planes4 ? PlaneKernel::planes4 : PlaneKernel::planes3;
+  bk = pencils_x ? BatchKernel::x : general ? (d.dim == 2 ? BatchKernel::g2 : BatchKernel::g)
+                                   : planes ? BatchKernel::none : BatchKernel::batches;
+  assert(rc || (pk != PlaneKernel::none) == (plan.n_plane_batches > 0));
   return rc;
 }
 
@@ -864,9 +872,10 @@ int mfgpu_plan_create(const mfgpu_desc *desc, mfgpu_plan **out) {
     return MFGPU_EINVAL;
   }
   mfgpu_plan *p = new mfgpu_plan();
-  mfgpu::KernelChoice kc;
-  int rc = mfgpu::choose_kernel_and_plan(*desc, kc, p->plan);
-  if (!rc && kc.planes) rc = mfgpu::build_plane_records(p->plan, desc->constraint_mask);
+  mfgpu::PlaneKernel pk;
+  mfgpu::BatchKernel bk;
+  int rc = mfgpu::choose_kernel_and_plan(*desc, pk, bk, p->plan);
+  if (!rc && pk != mfgpu::PlaneKernel::none) rc = mfgpu::build_plane_records(p->plan, desc->constraint_mask);
   if (rc) {
     delete p;
     return rc;
@@ -883,8 +892,9 @@ int mfgpu_suggest_renumbering(const mfgpu_desc *desc, uint32_t *new_index) {
     return MFGPU_EINVAL;
   }
   mfgpu::Plan P;
-  mfgpu::KernelChoice kc;
-  int rc = mfgpu::choose_kernel_and_plan(*desc, kc, P);
+  mfgpu::PlaneKernel pk;
+  mfgpu::BatchKernel bk;
+  int rc = mfgpu::choose_kernel_and_plan(*desc, pk, bk, P);
   if (rc) return rc;
   // batch-major: the dofs a batch owns alone, batch after batch (one contiguous run per batch: coalesced gathers and
   // stores of the cell loop), then the dofs several batches share in the order pass 2 walks them (grouped by the set

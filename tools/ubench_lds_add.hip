@@ -1,7 +1,7 @@
 // Microbenchmark (round 3): cost of LDS f64 atomics (ds_add_f64) against plain LDS stores / loads, per wave, with 1, 2
 // waves per SIMD of single-wave workgroups (as apply_planes4).  Each iteration issues 25 instructions of one kind at
 // conflict-free addresses (lane-contiguous doubles) and then waits for them (s_waitcnt lgkmcnt(0)).
-// Build: hipcc -O3 --offload-arch=gfx950 tools/ubench_lds_atomic.hip -o tools/bin/ubench_lds_atomic
+// Build: hipcc -O3 --offload-arch=gfx950 tools/ubench_lds_add.hip -o tools/bin/ubench_lds_add
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
