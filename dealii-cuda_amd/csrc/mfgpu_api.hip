@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -14,14 +15,43 @@
 
 using namespace mfgpu;
 
-#define HIP_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-      return e_ == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;                      \
-    }                                                                                    \
-  } while (0)
+// start / stop pairs of timing events around a stretch of a stream's work (profiling)
+struct EventTimer {
+  std::vector<Event> ev;
+  size_t used = 0;
+  double ms = 0.0;
+  int begin(hipStream_t st) {
+    if (used + 2 > ev.size()) {
+      Event e0, e1;
+      int rc;
+      if ((rc = e0.create(hipEventDefault)) || (rc = e1.create(hipEventDefault))) return rc;
+      ev.push_back(std::move(e0));
+      ev.push_back(std::move(e1));
+    }
+    HIP_TRY(hipEventRecord(ev[used].get(), st));
+    return 0;
+  }
+  int end(hipStream_t st) {
+    HIP_TRY(hipEventRecord(ev[used + 1].get(), st));
+    used += 2;
+    return 0;
+  }
+  // adds the pairs recorded since the last call (the caller has synchronised) and returns the total
+  int drain(double *total) {
+    for (size_t i = 0; i + 1 < used; i += 2) {
+      float t = 0.f;
+      HIP_TRY(hipEventElapsedTime(&t, ev[i].get(), ev[i + 1].get()));
+      ms += t;
+    }
+    used = 0;
+    *total = ms;
+    return 0;
+  }
+  void reset() {
+    used = 0;
+    ms = 0.0;
+  }
+};
 
 struct mfgpu_handle {
   Plan plan;
@@ -30,26 +60,26 @@ struct mfgpu_handle {
   std::vector<double> S, Dt;
   std::vector<double> sv, sg;  // the caller's 1D tables (diagonal)
   // device arrays
-  uint32_t *d_batch_cell_off = nullptr, *d_batch_dof_off = nullptr, *d_bdofs = nullptr;
-  uint8_t *d_bflags = nullptr;
-  uint16_t *d_lmap = nullptr;
-  uint16_t *d_lmapx = nullptr;
-  uint16_t *d_perm = nullptr;  // apply_batches_x: bank-conflict-free lane -> pencil maps of the y- and z-stage
+  DeviceArray<uint32_t> d_batch_cell_off, d_batch_dof_off, d_bdofs;
+  DeviceArray<uint8_t> d_bflags;
+  DeviceArray<uint16_t> d_lmap;
+  DeviceArray<uint16_t> d_lmapx;
+  DeviceArray<uint16_t> d_perm;  // apply_batches_x: bank-conflict-free lane -> pencil maps of the y- and z-stage
   // apply_planes3: fixed-size per-batch records (see ApplyArgs)
-  uint32_t *d_bdofsp = nullptr, *d_idxp = nullptr;
-  uint32_t *d_hnrec = nullptr;  // apply_planes3<HN>: per-batch records of the hanging-node line operations
-  uint32_t *d_hn_slot = nullptr;  // ... and per plane batch the index of its record (0xffffffff: none)
-  void *d_coefp = nullptr;
-  void *d_coef = nullptr;
-  uint32_t *d_cmask = nullptr, *d_orphans = nullptr;
-  void *d_hnw = nullptr;
-  uint32_t *d_constrained = nullptr;  // constrained dof list (set_constrained_values)
+  DeviceArray<uint32_t> d_bdofsp, d_idxp;
+  DeviceArray<uint32_t> d_hnrec;  // apply_planes3<HN>: per-batch records of the hanging-node line operations
+  DeviceArray<uint32_t> d_hn_slot;  // ... and per plane batch the index of its record (0xffffffff: none)
+  DeviceArray<void> d_coefp;
+  DeviceArray<void> d_coef;
+  DeviceArray<uint32_t> d_cmask, d_orphans;
+  DeviceArray<void> d_hnw;
+  DeviceArray<uint32_t> d_constrained;  // constrained dof list (set_constrained_values)
   uint32_t n_constrained = 0;
-  void *d_tabsd = nullptr;  // apply_batches_g2: [S | Dt] full 1D tables in the operator's number type
-  void *d_tab2 = nullptr;  // [2][n*n] squared 1D tables of the diagonal kernel, built on first use
+  DeviceArray<void> d_tabsd;  // apply_batches_g2: [S | Dt] full 1D tables in the operator's number type
+  DeviceArray<void> d_tab2;  // [2][n*n] squared 1D tables of the diagonal kernel, built on first use
   // two-pass mode
   bool twopass = true;
-  uint32_t *d_batch_nint = nullptr, *d_halo_off = nullptr;
+  DeviceArray<uint32_t> d_batch_nint, d_halo_off;
   // The cell loop runs in SEGMENTS of consecutive batches, one launch each (seg_end[s] = one past the segment's last
   // batch).  Pass 2, class-sorted form (mfgpu_pass2.hip), in 1 + n_segments groups: [0] the priority dofs (mfgpu_dist:
   // the slab's interface planes, reduced first after the whole cell loop so that their exchange overlaps the rest),
@@ -57,14 +87,14 @@ struct mfgpu_handle {
   // s < last it runs on the handle's side stream while the next segment's cells are computed (a latency-bound kernel
   // next to an issue-bound one); the last group and the priority group run on the caller's stream.
   std::vector<uint32_t> seg_end;
-  std::vector<uint32_t *> d_p2arr, d_p2tiles;
+  std::vector<DeviceArray<uint32_t>> d_p2arr, d_p2tiles;
   std::vector<uint32_t> n_p2tiles;
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> ev_seg;  // [s]: segment s done (recorded on the caller's stream)
-  hipEvent_t ev_side = nullptr;    // the side stream's pass-2 launches of this vmult done
-  bool side_pending = false;       // the caller's stream has not joined the side stream yet
-  void *d_halo = nullptr;
-  unsigned long long *d_stamps = nullptr;  // diagnostic build only
+  Stream side;
+  std::vector<Event> ev_seg;  // [s]: segment s done (recorded on the caller's stream)
+  Event ev_side;              // the side stream's pass-2 launches of this vmult done
+  bool side_pending = false;  // the caller's stream has not joined the side stream yet
+  DeviceArray<void> d_halo;
+  DeviceArray<unsigned long long> d_stamps;  // diagnostic build only
   size_t lds = 0, device_bytes = 0;
   // the cell-loop kernel families (choose_kernel_and_plan): `planes` takes the first plan.n_plane_batches batches,
   // `batches` the rest
@@ -75,13 +105,9 @@ struct mfgpu_handle {
   uint32_t max_grid_ph = 0;  // ... of its <HN> instantiation (the plane batches of cells with a hanging-node mask)
   // profiling
   bool prof = false;
-  std::vector<hipEvent_t> ev;  // start/stop pairs
-  size_t ev_used = 0;
-  double prof_ms = 0.0;
+  EventTimer t_cells;  // around the cell loop
+  EventTimer t_pass2;  // around pass 2 (mfgpu_vmult / mfgpu_vmult_add only)
   uint64_t prof_vmults = 0;
-  std::vector<hipEvent_t> ev2;  // start/stop pairs around pass 2 (mfgpu_vmult / mfgpu_vmult_add only)
-  size_t ev2_used = 0;
-  double prof2_ms = 0.0;
 };
 
 namespace {
@@ -130,16 +156,6 @@ hipError_t family_launch(const mfgpu_handle *h, BatchKernel k, const ApplyArgs<T
     case BatchKernel::g2: return g2_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
     default: return hipErrorInvalidValue;
   }
-}
-
-template <typename P>
-int dev_upload(P **dst, const void *src, size_t bytes, size_t &acct) {
-  *dst = nullptr;
-  if (bytes == 0) return 0;
-  HIP_TRY(hipMalloc((void **)dst, bytes));
-  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  acct += bytes;
-  return 0;
 }
 
 // symmetry of the 1D tables (see mfgpu_kernels.hip tab_at); also makes mirrored entries bit-equal
@@ -207,33 +223,31 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
   }
   const uint32_t zero_slot = P.halo_off.empty() ? 0u : P.halo_off.back();
   for (uint32_t orph : P.orphans) add(orph, &zero_slot, 1, 0);  // depend on no batch
-  for (size_t g = 0; g < h->d_p2arr.size(); ++g) {
-    hipFree(h->d_p2arr[g]);
-    hipFree(h->d_p2tiles[g]);
-  }
-  h->d_p2arr.assign(ng, nullptr);
-  h->d_p2tiles.assign(ng, nullptr);
-  h->n_p2tiles.assign(ng, 0u);
+  // built aside and moved into the handle when every group is on the device: a failure leaves the handle's arrays
+  // as they were.  (These arrays are not counted in device_bytes.)
+  std::vector<DeviceArray<uint32_t>> d_arr(ng), d_tiles(ng);
+  std::vector<uint32_t> n_tiles(ng, 0u);
   for (size_t g = 0; g < ng; ++g) {
     std::vector<uint32_t> arr, tiles;
     build_pass2_classes(sd[g], so[g], si[g], arr, tiles);
-    h->n_p2tiles[g] = (uint32_t)(tiles.size() / 4);
+    n_tiles[g] = (uint32_t)(tiles.size() / 4);
     // Tile order = the order the workgroups of pass 2 are dispatched in.  The builder's order is ascending in the
     // position of a dof's first toucher; while the halo buffer fits the 256 MB Infinity Cache the REVERSE is faster --
     // the partial sums the cell loop wrote last are read first, from cache: pass 2 42.4 -> 41.3 us on C2, 38.9 -> 35.3
     // on C5, -1 .. -3 % per vmult up to 38 M dofs; beyond (n = 96: 57 M dofs, 340 MB of partial sums) it is slower, at
     // 81 M dofs by 10 % (profiles/r03_notes.md section 13)
-    const size_t esz = h->number_type == MFGPU_F64 ? 8 : 4;
-    if ((size_t)P.halo_off.back() * esz <= ((size_t)256 << 20)) {
+    if ((size_t)P.halo_off.back() * esize(h->number_type) <= ((size_t)256 << 20)) {
       const size_t nt = tiles.size() / 4;
       for (size_t a = 0, b = nt ? nt - 1 : 0; a < b; ++a, --b)
         for (int w = 0; w < 4; ++w) std::swap(tiles[4 * a + w], tiles[4 * b + w]);
     }
-    size_t acct = 0;
     int rc;
-    if ((rc = dev_upload(&h->d_p2arr[g], arr.data(), arr.size() * 4, acct))) return rc;
-    if ((rc = dev_upload(&h->d_p2tiles[g], tiles.data(), tiles.size() * 4, acct))) return rc;
+    if ((rc = d_arr[g].upload(arr.data(), arr.size()))) return rc;
+    if ((rc = d_tiles[g].upload(tiles.data(), tiles.size()))) return rc;
   }
+  h->d_p2arr = std::move(d_arr);
+  h->d_p2tiles = std::move(d_tiles);
+  h->n_p2tiles = std::move(n_tiles);
   return 0;
 }
 
@@ -242,12 +256,18 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
   const Plan &P = h->plan;
   const size_t ncell = P.n_cells, nd = (size_t)P.nd;
   size_t &acct = h->device_bytes;
+  // n elements (DeviceArray<void>: bytes) to the device, counted in mfgpu_memory_consumption
+  auto up = [&](auto &arr, const void *src, size_t n) {
+    const int rc = arr.upload(src, n);
+    acct += arr.bytes();
+    return rc;
+  };
   int rc;
-  if ((rc = dev_upload(&h->d_batch_cell_off, P.batch_cell_off.data(), P.batch_cell_off.size() * 4, acct))) return rc;
-  if ((rc = dev_upload(&h->d_batch_dof_off, P.batch_dof_off.data(), P.batch_dof_off.size() * 4, acct))) return rc;
-  if ((rc = dev_upload(&h->d_bdofs, P.bdofs.data(), P.bdofs.size() * 4, acct))) return rc;
-  if ((rc = dev_upload(&h->d_bflags, P.bflags.data(), P.bflags.size(), acct))) return rc;
-  if ((rc = dev_upload(&h->d_lmap, P.lmap.data(), P.lmap.size() * 2, acct))) return rc;
+  if ((rc = up(h->d_batch_cell_off, P.batch_cell_off.data(), P.batch_cell_off.size()))) return rc;
+  if ((rc = up(h->d_batch_dof_off, P.batch_dof_off.data(), P.batch_dof_off.size()))) return rc;
+  if ((rc = up(h->d_bdofs, P.bdofs.data(), P.bdofs.size()))) return rc;
+  if ((rc = up(h->d_bflags, P.bflags.data(), P.bflags.size()))) return rc;
+  if ((rc = up(h->d_lmap, P.lmap.data(), P.lmap.size()))) return rc;
   const bool general = h->batches == BatchKernel::g || h->batches == BatchKernel::g2;
   if (h->batches == BatchKernel::x && !h->hn) {
     // Lane -> pencil maps of the y- and z-stage (see apply_batches_x).  LDS rules (MI355X_MICROARCH.md): a
@@ -275,7 +295,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
           overflow.pop_back();
         }
     }
-    if ((rc = dev_upload(&h->d_perm, perm.data(), perm.size() * 2, acct))) return rc;
+    if ((rc = up(h->d_perm, perm.data(), perm.size()))) return rc;
   }
   if (h->batches == BatchKernel::x || general) {
     // x-pencil index runs (n contiguous entries of lmap) padded to whole 32-bit words
@@ -283,7 +303,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     std::vector<uint16_t> lx(runs * np, 0);
     for (size_t r = 0; r < runs; ++r)
       for (size_t i = 0; i < n; ++i) lx[r * np + i] = P.lmap[r * n + i];
-    if ((rc = dev_upload(&h->d_lmapx, lx.data(), lx.size() * 2, acct))) return rc;
+    if ((rc = up(h->d_lmapx, lx.data(), lx.size()))) return rc;
   }
   if (h->batches == BatchKernel::g2) {  // apply_batches_g2: the full 1D tables [S | Dt]
     std::vector<T> sd(2 * (size_t)P.n * P.n);
@@ -291,82 +311,44 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
       sd[i] = (T)h->S[i];
       sd[P.n * P.n + i] = (T)h->Dt[i];
     }
-    if ((rc = dev_upload((T **)&h->d_tabsd, sd.data(), sd.size() * sizeof(T), acct))) return rc;
+    if ((rc = up(h->d_tabsd, sd.data(), sd.size() * sizeof(T)))) return rc;
   }
   if (h->planes != PlaneKernel::none) {
     if ((rc = build_plane_records(h->plan, d.constraint_mask))) return rc;
     if (!P.pr_hn.empty()) {
-      if ((rc = dev_upload(&h->d_hnrec, P.pr_hn.data(), P.pr_hn.size() * 4, acct))) return rc;
-      if ((rc = dev_upload(&h->d_hn_slot, P.pr_hn_slot.data(), P.pr_hn_slot.size() * 4, acct))) return rc;
+      if ((rc = up(h->d_hnrec, P.pr_hn.data(), P.pr_hn.size()))) return rc;
+      if ((rc = up(h->d_hn_slot, P.pr_hn_slot.data(), P.pr_hn_slot.size()))) return rc;
     }
-    if ((rc = dev_upload(&h->d_bdofsp, P.pr_dofs.data(), P.pr_dofs.size() * 4, acct))) return rc;
-    if ((rc = dev_upload(&h->d_idxp, P.pr_idx.data(), P.pr_idx.size() * 4, acct))) return rc;
+    if ((rc = up(h->d_bdofsp, P.pr_dofs.data(), P.pr_dofs.size()))) return rc;
+    if ((rc = up(h->d_idxp, P.pr_idx.data(), P.pr_idx.size()))) return rc;
   }
-  if ((rc = dev_upload(&h->d_orphans, P.orphans.data(), P.orphans.size() * 4, acct))) return rc;
+  if ((rc = up(h->d_orphans, P.orphans.data(), P.orphans.size()))) return rc;
   if (h->twopass) {
-    if ((rc = dev_upload(&h->d_batch_nint, P.batch_nint.data(), P.batch_nint.size() * 4, acct))) return rc;
-    if ((rc = dev_upload(&h->d_halo_off, P.halo_off.data(), P.halo_off.size() * 4, acct))) return rc;
+    if ((rc = up(h->d_batch_nint, P.batch_nint.data(), P.batch_nint.size()))) return rc;
+    if ((rc = up(h->d_halo_off, P.halo_off.data(), P.halo_off.size()))) return rc;
     if (h->planes != PlaneKernel::none && (uint64_t)P.halo_off.back() >= (1ull << 29)) {
       set_error("halo buffer too large for 32-bit byte offsets");
       return MFGPU_EUNSUPPORTED;
     }
     const size_t hb = ((size_t)P.halo_off.back() + 1) * sizeof(T);  // + the always-zero slot of the untouched dofs
-    if (hb) {
-      HIP_TRY(hipMalloc(&h->d_halo, hb));
-      HIP_TRY(hipMemset(h->d_halo, 0, hb));
-      acct += hb;
-    }
+    if ((rc = h->d_halo.alloc(hb, true))) return rc;
+    acct += hb;
   }
   if (h->hn) {
     std::vector<uint32_t> cm(ncell);
     for (size_t i = 0; i < ncell; ++i) cm[i] = d.constraint_mask[P.cell_order[i]];
-    if ((rc = dev_upload(&h->d_cmask, cm.data(), ncell * 4, acct))) return rc;
+    if ((rc = up(h->d_cmask, cm.data(), ncell))) return rc;
     std::vector<T> w((size_t)h->n * h->n);
     for (size_t i = 0; i < w.size(); ++i) w[i] = (T)d.constraint_weights[i];
-    if ((rc = dev_upload((T **)&h->d_hnw, w.data(), w.size() * sizeof(T), acct))) return rc;
+    if ((rc = up(h->d_hnw, w.data(), w.size() * sizeof(T)))) return rc;
   }
   // coefficient (given, or evaluated on the device from the quadrature points), then folded
-  size_t tmp = 0;
-  T *t_coef = nullptr, *t_jxw = nullptr, *t_j0 = nullptr, *t_q = nullptr;
-  uint32_t *t_order = nullptr;
-  auto cleanup = [&]() {
-    hipFree(t_coef);
-    hipFree(t_jxw);
-    hipFree(t_j0);
-    hipFree(t_q);
-    hipFree(t_order);
-  };
-  if (d.coefficient) {
-    if ((rc = dev_upload(&t_coef, d.coefficient, ncell * nd * sizeof(T), tmp))) { cleanup(); return rc; }
-  } else {
-    if ((rc = dev_upload(&t_q, d.quadrature_points, ncell * nd * P.dim * sizeof(T), tmp))) { cleanup(); return rc; }
-    hipError_t e = hipMalloc((void **)&t_coef, ncell * nd * sizeof(T));
-    if (e == hipSuccess) e = coefficient_launch<T>(t_coef, t_q, ncell * nd, P.dim, nullptr);
-    if (e != hipSuccess) {
-      set_error(std::string("coefficient evaluation: ") + hipGetErrorString(e));
-      cleanup();
-      return MFGPU_EHIP;
-    }
-  }
-  if ((rc = dev_upload(&t_jxw, d.JxW, ncell * nd * sizeof(T), tmp))) { cleanup(); return rc; }
-  const size_t jac_per_cell = general ? nd * (size_t)(P.dim * P.dim) : 1;  // full J^-1 per point, or one scalar per cell
-  if ((rc = dev_upload(&t_j0, d.inv_jac, ncell * jac_per_cell * sizeof(T), tmp))) { cleanup(); return rc; }
-  if ((rc = dev_upload(&t_order, P.cell_order.data(), ncell * 4, tmp))) { cleanup(); return rc; }
-  // symmetric M = a JxW J^-1 J^-T (6 entries in 3D, 3 in 2D), or the scalar a J0^2 JxW
-  const size_t coef_per_point = general ? (P.dim == 3 ? 6 : 3) : 1;
-  hipError_t e = hipMalloc(&h->d_coef, ncell * nd * coef_per_point * sizeof(T));
-  if (e == hipSuccess) {
-    acct += ncell * nd * coef_per_point * sizeof(T);
-    e = general ? (P.dim == 3 ? fold_general_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr)
-                              : fold_general2_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr))
-              : fold_launch<T>((T *)h->d_coef, t_coef, t_jxw, t_j0, t_order, (uint32_t)ncell, (uint32_t)nd, nullptr);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  cleanup();
-  if (e != hipSuccess) {
-    set_error(std::string("coefficient fold: ") + hipGetErrorString(e));
-    return MFGPU_EHIP;
-  }
+  DeviceArray<T> metric;
+  if ((rc = fold_coefficient<T>(metric, d.coefficient, d.quadrature_points, d.JxW, d.inv_jac, P.cell_order.data(), P.dim,
+                                (uint32_t)ncell, (uint32_t)nd, general)))
+    return rc;
+  h->d_coef = std::move(metric);
+  acct += h->d_coef.bytes();
   if (h->planes != PlaneKernel::none) {
     // the folded coefficient again, per batch [row y + n z][task]: the layout of stage B of apply_planes3
     // (d_coef in plan cell order stays: the diagonal kernel reads it)
@@ -379,27 +361,14 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
         cb[c] = (uint32_t)b;
         cp[c] = c - P.batch_cell_off[b];
       }
-    uint32_t *t_cb = nullptr, *t_cp = nullptr;
-    size_t tmp2 = 0;
-    rc = dev_upload(&t_cb, cb.data(), ncell_p * 4, tmp2);
-    if (!rc) rc = dev_upload(&t_cp, cp.data(), ncell_p * 4, tmp2);
-    if (!rc) {
-      hipError_t e2 = hipMalloc(&h->d_coefp, total * sizeof(T));
-      if (e2 == hipSuccess) {
-        acct += total * sizeof(T);
-        e2 = hipMemset(h->d_coefp, 0, total * sizeof(T));
-      }
-      if (e2 == hipSuccess)
-        e2 = relayout_coef_launch<T>((T *)h->d_coefp, (const T *)h->d_coef, t_cb, t_cp, ncell_p * nd, n, nullptr);
-      if (e2 == hipSuccess) e2 = hipDeviceSynchronize();
-      if (e2 != hipSuccess) {
-        set_error(std::string("coefficient relayout: ") + hipGetErrorString(e2));
-        rc = e2 == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;
-      }
-    }
-    hipFree(t_cb);
-    hipFree(t_cp);
-    if (rc) return rc;
+    DeviceArray<uint32_t> t_cb, t_cp;
+    if ((rc = t_cb.upload(cb.data(), ncell_p))) return rc;
+    if ((rc = t_cp.upload(cp.data(), ncell_p))) return rc;
+    if ((rc = h->d_coefp.alloc(total * sizeof(T), true))) return rc;
+    acct += h->d_coefp.bytes();
+    HIP_TRY(relayout_coef_launch<T>(h->d_coefp.as<T>(), h->d_coef.as<const T>(), t_cb.get(), t_cp.get(), ncell_p * nd, n,
+                                    nullptr));
+    HIP_TRY(hipDeviceSynchronize());
   }
   // persistent grids: as many workgroups as fit on the chip (each loops over its batches)
   int dev = 0, per_cu = 0;
@@ -474,10 +443,11 @@ int create_typed(mfgpu_handle *h, const mfgpu_desc &d) {
     // which fill the remaining wave slots
     int prio_least = 0, prio_greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    HIP_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_least));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming));
-    h->ev_seg.assign(h->seg_end.size() - 1, nullptr);
-    for (hipEvent_t &e : h->ev_seg) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if ((rc = h->side.create(hipStreamNonBlocking, prio_least))) return rc;
+    if ((rc = h->ev_side.create(hipEventDisableTiming))) return rc;
+    h->ev_seg.resize(h->seg_end.size() - 1);
+    for (Event &e : h->ev_seg)
+      if ((rc = e.create(hipEventDisableTiming))) return rc;
   }
   return upload_pass2(h, nullptr, 0);
 }
@@ -487,8 +457,8 @@ int create_typed(mfgpu_handle *h, const mfgpu_desc &d) {
 // to back; mfgpu_vmult_dist_begin starts the exchange of the slab's interface planes between the last two.
 template <typename T>
 int launch_pass2_group(mfgpu_handle *h, size_t group, void *dst, const void *src, hipStream_t st, int add) {
-  HIP_TRY(reduce_classes_launch<T>((T *)dst, (const T *)src, (const T *)h->d_halo, h->d_p2arr[group], h->d_p2tiles[group],
-                                   h->n_p2tiles[group], add, st));
+  HIP_TRY(reduce_classes_launch<T>((T *)dst, (const T *)src, h->d_halo.as<const T>(), h->d_p2arr[group].get(),
+                                   h->d_p2tiles[group].get(), h->n_p2tiles[group], add, st));
   return 0;
 }
 
@@ -498,7 +468,7 @@ int vmult_pass2(mfgpu_handle *h, int phase, void *dst, const void *src, hipStrea
   if (phase == 0) return launch_pass2_group<T>(h, 0, dst, src, st, add);
   int rc = launch_pass2_group<T>(h, h->seg_end.size(), dst, src, st, add);
   if (!rc && h->side_pending) {
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_side, 0));
+    HIP_TRY(hipStreamWaitEvent(st, h->ev_side.get(), 0));
     h->side_pending = false;
   }
   return rc;
@@ -535,31 +505,31 @@ template <typename T>
 ApplyArgs<T> make_args(mfgpu_handle *h, void *dst, const void *src, int add) {
   const Plan &P = h->plan;
   ApplyArgs<T> a;
-  a.batch_cell_off = h->d_batch_cell_off;
-  a.batch_dof_off = h->d_batch_dof_off;
-  a.bdofs = h->d_bdofs;
-  a.bflags = h->d_bflags;
-  a.lmap = h->d_lmap;
-  a.lmapx = h->d_lmapx;
-  a.perm = h->d_perm;
-  a.bdofsp = h->d_bdofsp;
-  a.idxp = h->d_idxp;
-  a.hnrec = h->d_hnrec;
-  a.hn_slot = h->d_hn_slot;
-  a.coefp = (const T *)h->d_coefp;
-  a.coef = (const T *)h->d_coef;
-  a.cmask = h->d_cmask;
-  a.hn_weights = (const T *)h->d_hnw;
-  a.tabS = (const T *)h->d_tabsd;
-  a.tabDt = h->d_tabsd ? (const T *)h->d_tabsd + (size_t)P.n * P.n : nullptr;
-  a.batch_nint = h->d_batch_nint;
-  a.halo_off = h->d_halo_off;
-  a.halo = (T *)h->d_halo;
+  a.batch_cell_off = h->d_batch_cell_off.get();
+  a.batch_dof_off = h->d_batch_dof_off.get();
+  a.bdofs = h->d_bdofs.get();
+  a.bflags = h->d_bflags.get();
+  a.lmap = h->d_lmap.get();
+  a.lmapx = h->d_lmapx.get();
+  a.perm = h->d_perm.get();
+  a.bdofsp = h->d_bdofsp.get();
+  a.idxp = h->d_idxp.get();
+  a.hnrec = h->d_hnrec.get();
+  a.hn_slot = h->d_hn_slot.get();
+  a.coefp = h->d_coefp.as<const T>();
+  a.coef = h->d_coef.as<const T>();
+  a.cmask = h->d_cmask.get();
+  a.hn_weights = h->d_hnw.as<const T>();
+  a.tabS = h->d_tabsd.as<const T>();
+  a.tabDt = a.tabS ? a.tabS + (size_t)P.n * P.n : nullptr;
+  a.batch_nint = h->d_batch_nint.get();
+  a.halo_off = h->d_halo_off.get();
+  a.halo = h->d_halo.as<T>();
   a.dst = (T *)dst;
   a.src = (const T *)src;
   a.nb_max = P.max_batch_dofs;
   a.add = add;
-  a.stamps = h->d_stamps;
+  a.stamps = h->d_stamps.get();
   a.dbg = 0;
   return a;
 }
@@ -568,51 +538,38 @@ template <typename T>
 int vmult_main(mfgpu_handle *h, void *dst, const void *src, hipStream_t st, int add) {
   const Plan &P = h->plan;
   ApplyArgs<T> a = make_args<T>(h, dst, src, add);
-  if (h->prof) {
-    if (h->ev_used + 2 > h->ev.size()) {
-      hipEvent_t e0, e1;
-      HIP_TRY(hipEventCreate(&e0));
-      HIP_TRY(hipEventCreate(&e1));
-      h->ev.push_back(e0);
-      h->ev.push_back(e1);
-    }
-    HIP_TRY(hipEventRecord(h->ev[h->ev_used], st));
-  }
+  int rc;
+  if (h->prof && (rc = h->t_cells.begin(st))) return rc;
   if (h->twopass) {
     // ONE sweep over all batches (no inter-batch dependency) in segments; after every segment but the last, the
     // shared-dof sums that are complete by then start on the side stream
     const size_t nseg = h->seg_end.size();
     if (h->side_pending) {  // (a caller that ran phase 0 twice without the closing phase)
-      HIP_TRY(hipStreamWaitEvent(st, h->ev_side, 0));
+      HIP_TRY(hipStreamWaitEvent(st, h->ev_side.get(), 0));
       h->side_pending = false;
     }
     for (size_t s = 0; s < nseg; ++s) {
-      int rc = launch_cells<T>(h, a, s ? h->seg_end[s - 1] : 0u, h->seg_end[s], st);
-      if (rc) return rc;
+      if ((rc = launch_cells<T>(h, a, s ? h->seg_end[s - 1] : 0u, h->seg_end[s], st))) return rc;
       if (s + 1 < nseg) {
-        HIP_TRY(hipEventRecord(h->ev_seg[s], st));
-        HIP_TRY(hipStreamWaitEvent(h->side, h->ev_seg[s], 0));
-        if ((rc = launch_pass2_group<T>(h, 1 + s, dst, src, h->side, add))) return rc;
+        HIP_TRY(hipEventRecord(h->ev_seg[s].get(), st));
+        HIP_TRY(hipStreamWaitEvent(h->side.get(), h->ev_seg[s].get(), 0));
+        if ((rc = launch_pass2_group<T>(h, 1 + s, dst, src, h->side.get(), add))) return rc;
       }
     }
     if (nseg > 1) {
-      HIP_TRY(hipEventRecord(h->ev_side, h->side));
+      HIP_TRY(hipEventRecord(h->ev_side.get(), h->side.get()));
       h->side_pending = true;
     }
   } else {
     // coloured mode: one launch per batch colour (first toucher stores, later colours add)
     for (size_t c = 0; c + 1 < P.color_batch_off.size(); ++c) {
       if (P.color_batch_off[c + 1] == P.color_batch_off[c]) continue;
-      int rc = launch_cells<T>(h, a, P.color_batch_off[c], P.color_batch_off[c + 1], st);
-      if (rc) return rc;
+      if ((rc = launch_cells<T>(h, a, P.color_batch_off[c], P.color_batch_off[c + 1], st))) return rc;
     }
   }
-  if (h->prof) {
-    HIP_TRY(hipEventRecord(h->ev[h->ev_used + 1], st));
-    h->ev_used += 2;
-  }
+  if (h->prof && (rc = h->t_cells.end(st))) return rc;
   if (!h->twopass)  // coloured mode has no pass 2: the dofs no cell touches get their own small kernel
-    HIP_TRY(orphan_launch<T>((T *)dst, (const T *)src, h->d_orphans, (uint32_t)P.orphans.size(), add, st));
+    HIP_TRY(orphan_launch<T>((T *)dst, (const T *)src, h->d_orphans.get(), (uint32_t)P.orphans.size(), add, st));
   if (h->prof) h->prof_vmults++;
   return 0;
 }
@@ -621,22 +578,11 @@ template <typename T>
 int vmult_typed(mfgpu_handle *h, void *dst, const void *src, hipStream_t st, int add) {
   int rc = vmult_main<T>(h, dst, src, st, add);
   if (rc) return rc;
-  if (h->prof && h->twopass) {
-    if (h->ev2_used + 2 > h->ev2.size()) {
-      hipEvent_t e0, e1;
-      HIP_TRY(hipEventCreate(&e0));
-      HIP_TRY(hipEventCreate(&e1));
-      h->ev2.push_back(e0);
-      h->ev2.push_back(e1);
-    }
-    HIP_TRY(hipEventRecord(h->ev2[h->ev2_used], st));
-  }
+  const bool timed = h->prof && h->twopass;
+  if (timed && (rc = h->t_pass2.begin(st))) return rc;
   rc = vmult_pass2<T>(h, 0, dst, src, st, add);
   if (!rc) rc = vmult_pass2<T>(h, 1, dst, src, st, add);
-  if (!rc && h->prof && h->twopass) {
-    HIP_TRY(hipEventRecord(h->ev2[h->ev2_used + 1], st));
-    h->ev2_used += 2;
-  }
+  if (!rc && timed) rc = h->t_pass2.end(st);
   return rc;
 }
 
@@ -648,33 +594,31 @@ template <typename T>
 int inverse_diagonal_typed(mfgpu_handle *h, void *diag, hipStream_t st) {
   const Plan &P = h->plan;
   const bool general = h->batches == BatchKernel::g || h->batches == BatchKernel::g2;
-  if (!h->d_tab2) {  // 1D tables T[2][n*n]: squared [S.^2 | G.^2], or plain [S | G] for the general-geometry path
+  if (!h->d_tab2.get()) {  // 1D tables T[2][n*n]: squared [S.^2 | G.^2], or plain [S | G] for the general-geometry path
     const int nn = h->n * h->n;
     std::vector<T> t2(2 * (size_t)nn);
     for (int i = 0; i < nn; ++i) {
       t2[i] = (T)(general ? h->sv[i] : h->sv[i] * h->sv[i]);
       t2[nn + i] = (T)(general ? h->sg[i] : h->sg[i] * h->sg[i]);
     }
-    int rc = dev_upload(&h->d_tab2, t2.data(), t2.size() * sizeof(T), h->device_bytes);
-    if (rc) return rc;
+    if (const int rc = h->d_tab2.upload(t2.data(), t2.size() * sizeof(T))) return rc;
+    h->device_bytes += h->d_tab2.bytes();
   }
   // inv_diag.reinit(m()): zero  (laplace_operator_gpu.h:407)
   HIP_TRY(fill_launch<T>((T *)diag, P.n_dofs, T(0), st));
   // data.cell_loop(inv_diag, diag_loc_op)  (:409-410)
+  const uint32_t nb = (uint32_t)(P.batch_cell_off.size() - 1), *cell_off = h->d_batch_cell_off.get();
+  const uint32_t *dof_off = h->d_batch_dof_off.get(), *bdofs = h->d_bdofs.get(), *cmask = h->d_cmask.get();
+  const uint16_t *lmap = h->d_lmap.get();
+  const T *coef = h->d_coef.as<const T>(), *hnw = h->d_hnw.as<const T>(), *tab2 = h->d_tab2.as<const T>();
   if (h->batches == BatchKernel::g2)
-    HIP_TRY(diag_general2_launch<T>(P.n, (T *)diag, (uint32_t)(P.batch_cell_off.size() - 1), h->d_batch_cell_off,
-                                    h->d_batch_dof_off, h->d_bdofs, h->d_lmap, (const T *)h->d_coef, h->d_cmask,
-                                    (const T *)h->d_hnw, (const T *)h->d_tab2, st));
+    HIP_TRY(diag_general2_launch<T>(P.n, (T *)diag, nb, cell_off, dof_off, bdofs, lmap, coef, cmask, hnw, tab2, st));
   else if (h->batches == BatchKernel::g)
-    HIP_TRY(diag_general_launch<T>(P.n, (T *)diag, (uint32_t)(P.batch_cell_off.size() - 1), h->d_batch_cell_off,
-                                   h->d_batch_dof_off, h->d_bdofs, h->d_lmap, (const T *)h->d_coef, h->d_cmask,
-                                   (const T *)h->d_hnw, (const T *)h->d_tab2, st));
+    HIP_TRY(diag_general_launch<T>(P.n, (T *)diag, nb, cell_off, dof_off, bdofs, lmap, coef, cmask, hnw, tab2, st));
   else
-    HIP_TRY(diag_launch<T>(P.dim, P.n, (T *)diag, (uint32_t)(P.batch_cell_off.size() - 1), h->d_batch_cell_off,
-                           h->d_batch_dof_off, h->d_bdofs, h->d_lmap, (const T *)h->d_coef, h->d_cmask,
-                           (const T *)h->d_hnw, (const T *)h->d_tab2, st));
+    HIP_TRY(diag_launch<T>(P.dim, P.n, (T *)diag, nb, cell_off, dof_off, bdofs, lmap, coef, cmask, hnw, tab2, st));
   // constraint_handler.set_constrained_values(inv_diag, 1.0)  (:412)
-  HIP_TRY(set_values_launch<T>((T *)diag, h->d_constrained, h->n_constrained, T(1), st));
+  HIP_TRY(set_values_launch<T>((T *)diag, h->d_constrained.get(), h->n_constrained, T(1), st));
   // inv_diag.invert()  (:414)
   HIP_TRY(vec_map_launch<T>(4, (T *)diag, nullptr, T(0), T(0), P.n_dofs, st));
   return 0;
@@ -792,7 +736,7 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
     return MFGPU_EINVAL;
   }
   const mfgpu_desc &d = *desc;
-  if (d.number_type != MFGPU_F64 && d.number_type != MFGPU_F32) {
+  if (!valid_number_type(d.number_type)) {
     set_error("number_type must be MFGPU_F64 or MFGPU_F32");
     return MFGPU_EINVAL;
   }
@@ -811,12 +755,9 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
     set_error("MFGPU_HANGING_NODES needs constraint_mask and constraint_weights");
     return MFGPU_EINVAL;
   }
-  mfgpu_handle *h = new mfgpu_handle();
+  std::unique_ptr<mfgpu_handle, decltype(&mfgpu_destroy)> h(new mfgpu_handle(), mfgpu_destroy);
   int rc = choose_kernel_and_plan(d, h->planes, h->batches, h->plan);
-  if (rc) {
-    delete h;
-    return rc;
-  }
+  if (rc) return rc;
   h->dim = d.dim;
   h->n = d.degree + 1;
   h->nd = h->plan.nd;
@@ -833,57 +774,20 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
   h->sg = sg;
   rc = derive_tables(h->n, sv.data(), sg.data(), h->S, h->Dt);
   if (!rc) rc = check_symmetrize(h->n, h->S, h->Dt);
-  if (!rc) rc = d.number_type == MFGPU_F64 ? create_typed<double>(h, d) : create_typed<float>(h, d);
+  if (!rc) rc = d.number_type == MFGPU_F64 ? create_typed<double>(h.get(), d) : create_typed<float>(h.get(), d);
   if (!rc && d.n_constrained) {
     h->n_constrained = d.n_constrained;
-    rc = dev_upload(&h->d_constrained, d.constrained_dofs, (size_t)d.n_constrained * 4, h->device_bytes);
+    rc = h->d_constrained.upload(d.constrained_dofs, d.n_constrained);
+    h->device_bytes += h->d_constrained.bytes();
   }
-  if (rc) {
-    mfgpu_destroy(h);
-    return rc;
-  }
-  *out = h;
+  if (rc) return rc;
+  *out = h.release();
   return 0;
 }
 
 void mfgpu_destroy(mfgpu_handle *h) {
   if (!h) return;
-  hipFree(h->d_batch_cell_off);
-  hipFree(h->d_batch_dof_off);
-  hipFree(h->d_bdofs);
-  hipFree(h->d_bflags);
-  hipFree(h->d_lmap);
-  hipFree(h->d_lmapx);
-  hipFree(h->d_perm);
-  hipFree(h->d_bdofsp);
-  hipFree(h->d_idxp);
-  hipFree(h->d_hnrec);
-  hipFree(h->d_hn_slot);
-  hipFree(h->d_coefp);
-  hipFree(h->d_constrained);
-  hipFree(h->d_tab2);
-  hipFree(h->d_tabsd);
-  hipFree(h->d_coef);
-  hipFree(h->d_cmask);
-  hipFree(h->d_orphans);
-  hipFree(h->d_hnw);
-  hipFree(h->d_batch_nint);
-  hipFree(h->d_halo_off);
-  for (size_t g = 0; g < h->d_p2arr.size(); ++g) {
-    hipFree(h->d_p2arr[g]);
-    hipFree(h->d_p2tiles[g]);
-  }
-  if (h->side) {
-    hipStreamSynchronize(h->side);
-    hipStreamDestroy(h->side);
-  }
-  for (hipEvent_t e : h->ev_seg)
-    if (e) hipEventDestroy(e);
-  if (h->ev_side) hipEventDestroy(h->ev_side);
-  hipFree(h->d_halo);
-  hipFree(h->d_stamps);
-  for (hipEvent_t e : h->ev) hipEventDestroy(e);
-  for (hipEvent_t e : h->ev2) hipEventDestroy(e);
+  if (h->side.get()) hipStreamSynchronize(h->side.get());  // before any of the arrays it reads is released
   delete h;
 }
 
@@ -963,37 +867,22 @@ const char *mfgpu_kernel_name(const mfgpu_handle *h) {
 int mfgpu_profile_enable(mfgpu_handle *h, int on) {
   if (!h) return MFGPU_EINVAL;
   h->prof = on != 0;
-  h->ev_used = 0;
-  h->prof_ms = 0.0;
+  h->t_cells.reset();
+  h->t_pass2.reset();
   h->prof_vmults = 0;
-  h->ev2_used = 0;
-  h->prof2_ms = 0.0;
   return 0;
 }
 
 int mfgpu_profile_read_pass2(mfgpu_handle *h, double *ms) {
   if (!h || !ms) return MFGPU_EINVAL;
   HIP_TRY(hipDeviceSynchronize());
-  for (size_t i = 0; i + 1 < h->ev2_used; i += 2) {
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, h->ev2[i], h->ev2[i + 1]));
-    h->prof2_ms += t;
-  }
-  h->ev2_used = 0;
-  *ms = h->prof2_ms;
-  return 0;
+  return h->t_pass2.drain(ms);
 }
 
 int mfgpu_profile_read(mfgpu_handle *h, double *ms, uint64_t *nv) {
   if (!h || !ms || !nv) return MFGPU_EINVAL;
   HIP_TRY(hipDeviceSynchronize());
-  for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-    float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-    h->prof_ms += t;
-  }
-  h->ev_used = 0;
-  *ms = h->prof_ms;
+  if (const int rc = h->t_cells.drain(ms)) return rc;
   *nv = h->prof_vmults;
   return 0;
 }
@@ -1003,22 +892,16 @@ int mfgpu_profile_read(mfgpu_handle *h, double *ms, uint64_t *nv) {
 int mfgpu_debug_stamps(mfgpu_handle *h, unsigned long long *out, size_t n_batches) {
   if (!h) return MFGPU_EINVAL;
   const size_t nbt = h->plan.batch_cell_off.size() - 1;
-  if (!h->d_stamps) {
-    HIP_TRY(hipMalloc((void **)&h->d_stamps, 2 * nbt * 16 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(h->d_stamps, 0, 2 * nbt * 16 * sizeof(unsigned long long)));
-    return 0;
-  }
+  if (!h->d_stamps.get()) return h->d_stamps.alloc(2 * nbt * 16, true);
   if (out && n_batches == nbt) {
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, h->d_stamps, 2 * nbt * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, h->d_stamps.get(), 2 * nbt * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   }
   return 0;
 }
 #endif
 
 // ---- GpuVector pieces -----------------------------------------------------------------------
-
-static size_t esize(int nt) { return nt == MFGPU_F32 ? 4 : 8; }
 
 // ---- diagonal, set_constrained_values
 int mfgpu_compute_inverse_diagonal(mfgpu_handle *h, void *inv_diag, void *stream) {
@@ -1036,9 +919,10 @@ int mfgpu_set_constrained_values(mfgpu_handle *h, void *vec, double value, void 
     return MFGPU_EINVAL;
   }
   if (h->number_type == MFGPU_F64)
-    HIP_TRY(set_values_launch<double>((double *)vec, h->d_constrained, h->n_constrained, value, (hipStream_t)stream));
+    HIP_TRY(set_values_launch<double>((double *)vec, h->d_constrained.get(), h->n_constrained, value, (hipStream_t)stream));
   else
-    HIP_TRY(set_values_launch<float>((float *)vec, h->d_constrained, h->n_constrained, (float)value, (hipStream_t)stream));
+    HIP_TRY(set_values_launch<float>((float *)vec, h->d_constrained.get(), h->n_constrained, (float)value,
+                                     (hipStream_t)stream));
   return 0;
 }
 

@@ -26,21 +26,14 @@
 #include <rccl/rccl.h>
 
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "mfgpu_internal.h"
+#include "mfgpu_device.h"
 
 using namespace mfgpu;
 
-#define HIP_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-      return e_ == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;                      \
-    }                                                                                    \
-  } while (0)
 #define NCCL_TRY(expr)                                                                   \
   do {                                                                                   \
     ncclResult_t r_ = (expr);                                                            \
@@ -57,13 +50,15 @@ struct mfgpu_dist {
   uint32_t n_if[2] = {0, 0};            // interface dofs on the lower / upper plane
   std::vector<uint32_t> ids[2];         // their local dof ids (host copy: priority dofs of the operator)
   // device copies: ONE allocation each for both planes ([lower | upper]: one pack and one add launch per apply, a tiny
-  // launch costs ~5 us on the stream it sits in); [w] points at plane w's part
+  // launch costs ~5 us on the stream it sits in); d_*[w] points at plane w's part
+  DeviceArray<uint32_t> ids_all;
+  DeviceArray<uint8_t> free_all;        // 1: summed with the neighbour, 0: constrained (identity row)
+  DeviceArray<void> send_all, recv_all;
   uint32_t *d_ids[2] = {};
-  uint8_t *d_free[2] = {};              // 1: summed with the neighbour, 0: constrained (identity row)
+  uint8_t *d_free[2] = {};
   void *d_send[2] = {}, *d_recv[2] = {};
-  void *d_base[4] = {};                 // the four allocations (ids, free, send, recv)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_packed = nullptr, ev_done = nullptr, ev_if = nullptr;
+  Stream side;
+  Event ev_packed, ev_done, ev_if;
   bool in_flight = false;
   // interface-first schedule (set by mfgpu_dist_attach): batches [0, r1_end) and [r2_begin, n_batches) touch an
   // interface plane, [r1_end, r2_begin) is the interior
@@ -83,18 +78,17 @@ __global__ void add_kernel(T *vec, const T *in, const uint32_t *ids, const uint8
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && free_[i]) vec[ids[i]] += in[i];
 }
-size_t esize(int nt) { return nt == MFGPU_F32 ? 4 : 8; }
 
 int pack_planes(mfgpu_dist *d, const void *vec, hipStream_t st) {
   const uint32_t n = d->n_if[0] + d->n_if[1];  // both planes in one launch (contiguous [lower | upper])
   if (!n) return 0;
   const unsigned grid = (n + 255) / 256;
   if (d->number_type == MFGPU_F64)
-    hipLaunchKernelGGL(pack_kernel<double>, dim3(grid), dim3(256), 0, st, (double *)d->d_base[2], (const double *)vec,
-                       (const uint32_t *)d->d_base[0], n);
+    hipLaunchKernelGGL(pack_kernel<double>, dim3(grid), dim3(256), 0, st, d->send_all.as<double>(), (const double *)vec,
+                       d->ids_all.get(), n);
   else
-    hipLaunchKernelGGL(pack_kernel<float>, dim3(grid), dim3(256), 0, st, (float *)d->d_base[2], (const float *)vec,
-                       (const uint32_t *)d->d_base[0], n);
+    hipLaunchKernelGGL(pack_kernel<float>, dim3(grid), dim3(256), 0, st, d->send_all.as<float>(), (const float *)vec,
+                       d->ids_all.get(), n);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -102,10 +96,11 @@ int pack_planes(mfgpu_dist *d, const void *vec, hipStream_t st) {
 // grouped send / recv with both neighbours on the side stream, behind the pack (which ran on `st`: the launch stream,
 // or the side stream itself)
 int start_exchange(mfgpu_dist *d, hipStream_t st) {
-  HIP_TRY(hipEventRecord(d->ev_packed, st));
+  HIP_TRY(hipEventRecord(d->ev_packed.get(), st));
   d->in_flight = true;
   if (!d->comm) return 0;  // in-process transport: the copies happen in finish_exchange, when every peer has packed
-  if (st != d->side) HIP_TRY(hipStreamWaitEvent(d->side, d->ev_packed, 0));
+  const hipStream_t side = d->side.get();
+  if (st != side) HIP_TRY(hipStreamWaitEvent(side, d->ev_packed.get(), 0));
   const ncclDataType_t dt = d->number_type == MFGPU_F64 ? ncclDouble : ncclFloat;
   NCCL_TRY(ncclGroupStart());
   // (a failing call must not leave the group open: the group depth is state of the calling thread, and an open group
@@ -114,8 +109,8 @@ int start_exchange(mfgpu_dist *d, hipStream_t st) {
   for (int w = 0; w < 2 && bad == ncclSuccess; ++w) {
     if (!d->n_if[w]) continue;
     const int peer = w == 0 ? d->rank - 1 : d->rank + 1;
-    bad = ncclSend(d->d_send[w], d->n_if[w], dt, peer, d->comm, d->side);
-    if (bad == ncclSuccess) bad = ncclRecv(d->d_recv[w], d->n_if[w], dt, peer, d->comm, d->side);
+    bad = ncclSend(d->d_send[w], d->n_if[w], dt, peer, d->comm, side);
+    if (bad == ncclSuccess) bad = ncclRecv(d->d_recv[w], d->n_if[w], dt, peer, d->comm, side);
   }
   const ncclResult_t end = ncclGroupEnd();
   if (bad != ncclSuccess || end != ncclSuccess) {
@@ -124,7 +119,7 @@ int start_exchange(mfgpu_dist *d, hipStream_t st) {
     d->in_flight = false;
     return MFGPU_EHIP;
   }
-  HIP_TRY(hipEventRecord(d->ev_done, d->side));
+  HIP_TRY(hipEventRecord(d->ev_done.get(), side));
   return 0;
 }
 
@@ -135,9 +130,9 @@ int finish_exchange(mfgpu_dist *d, void *vec, hipStream_t st) {
   }
   d->in_flight = false;
   if (d->comm) {
-    HIP_TRY(hipStreamWaitEvent(st, d->ev_done, 0));
+    HIP_TRY(hipStreamWaitEvent(st, d->ev_done.get(), 0));
   } else {
-    HIP_TRY(hipStreamWaitEvent(st, d->ev_packed, 0));  // this slab's own planes are complete (side stream)
+    HIP_TRY(hipStreamWaitEvent(st, d->ev_packed.get(), 0));  // this slab's own planes are complete (side stream)
     for (int w = 0; w < 2; ++w) {
       if (!d->n_if[w]) continue;
       mfgpu_dist *p = d->local_peer[w];
@@ -146,7 +141,7 @@ int finish_exchange(mfgpu_dist *d, void *vec, hipStream_t st) {
         return MFGPU_EINVAL;
       }
       // my lower plane is the neighbour's upper plane and vice versa
-      HIP_TRY(hipStreamWaitEvent(st, p->ev_packed, 0));
+      HIP_TRY(hipStreamWaitEvent(st, p->ev_packed.get(), 0));
       HIP_TRY(hipMemcpyAsync(d->d_recv[w], p->d_send[1 - w], (size_t)d->n_if[w] * esize(d->number_type),
                              hipMemcpyDeviceToDevice, st));
     }
@@ -155,11 +150,11 @@ int finish_exchange(mfgpu_dist *d, void *vec, hipStream_t st) {
   if (n) {
     const unsigned grid = (n + 255) / 256;
     if (d->number_type == MFGPU_F64)
-      hipLaunchKernelGGL(add_kernel<double>, dim3(grid), dim3(256), 0, st, (double *)vec, (const double *)d->d_base[3],
-                         (const uint32_t *)d->d_base[0], (const uint8_t *)d->d_base[1], n);
+      hipLaunchKernelGGL(add_kernel<double>, dim3(grid), dim3(256), 0, st, (double *)vec,
+                         d->recv_all.as<const double>(), d->ids_all.get(), d->free_all.get(), n);
     else
-      hipLaunchKernelGGL(add_kernel<float>, dim3(grid), dim3(256), 0, st, (float *)vec, (const float *)d->d_base[3],
-                         (const uint32_t *)d->d_base[0], (const uint8_t *)d->d_base[1], n);
+      hipLaunchKernelGGL(add_kernel<float>, dim3(grid), dim3(256), 0, st, (float *)vec,
+                         d->recv_all.as<const float>(), d->ids_all.get(), d->free_all.get(), n);
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -182,7 +177,7 @@ int mfgpu_dist_create(const void *id128, int rank, int world, const uint32_t *lo
                       const uint32_t *upper_ids, uint32_t n_upper, const uint32_t *constrained, uint32_t n_constrained,
                       uint32_t n_dofs, int number_type, mfgpu_dist **out) {
   if (!out || world < 1 || rank < 0 || rank >= world || (n_lower && !lower_ids) || (n_upper && !upper_ids) ||
-      (n_constrained && !constrained) || (number_type != MFGPU_F64 && number_type != MFGPU_F32)) {
+      (n_constrained && !constrained) || !valid_number_type(number_type)) {
     set_error("mfgpu_dist_create: bad argument");
     return MFGPU_EINVAL;
   }
@@ -190,7 +185,7 @@ int mfgpu_dist_create(const void *id128, int rank, int world, const uint32_t *lo
     set_error("mfgpu_dist_create: the first / last slab has no lower / upper neighbour");
     return MFGPU_EINVAL;
   }
-  mfgpu_dist *d = new mfgpu_dist();
+  std::unique_ptr<mfgpu_dist, decltype(&mfgpu_dist_destroy)> d(new mfgpu_dist(), mfgpu_dist_destroy);
   d->rank = rank;
   d->world = world;
   d->number_type = number_type;
@@ -199,10 +194,6 @@ int mfgpu_dist_create(const void *id128, int rank, int world, const uint32_t *lo
     if (constrained[i] < n_dofs) con[constrained[i]] = 1;
   const uint32_t *src_ids[2] = {lower_ids, upper_ids};
   const uint32_t cnt[2] = {n_lower, n_upper};
-  auto fail = [&](int rc) {
-    mfgpu_dist_destroy(d);
-    return rc;
-  };
   std::vector<uint32_t> ids_all;
   std::vector<uint8_t> free_all;
   for (int w = 0; w < 2; ++w) {
@@ -212,51 +203,39 @@ int mfgpu_dist_create(const void *id128, int rank, int world, const uint32_t *lo
     for (uint32_t i = 0; i < cnt[w]; ++i) {
       if (src_ids[w][i] >= n_dofs) {
         set_error("mfgpu_dist_create: interface dof out of range");
-        return fail(MFGPU_EINVAL);
+        return MFGPU_EINVAL;
       }
       ids_all.push_back(src_ids[w][i]);
       free_all.push_back(con[src_ids[w][i]] ? 0 : 1);
     }
   }
   const size_t n_all = ids_all.size(), es = esize(number_type);
-  if (n_all) {
-    if (hipMalloc(&d->d_base[0], n_all * 4) != hipSuccess || hipMalloc(&d->d_base[1], n_all) != hipSuccess ||
-        hipMalloc(&d->d_base[2], n_all * es) != hipSuccess || hipMalloc(&d->d_base[3], n_all * es) != hipSuccess ||
-        hipMemcpy(d->d_base[0], ids_all.data(), n_all * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d->d_base[1], free_all.data(), n_all, hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("mfgpu_dist_create: device allocation failed");
-      return fail(MFGPU_ENOMEM);
-    }
-    for (int w = 0; w < 2; ++w) {
-      const size_t off = w ? cnt[0] : 0;
-      d->d_ids[w] = (uint32_t *)d->d_base[0] + off;
-      d->d_free[w] = (uint8_t *)d->d_base[1] + off;
-      d->d_send[w] = (char *)d->d_base[2] + off * es;
-      d->d_recv[w] = (char *)d->d_base[3] + off * es;
-    }
+  int rc;
+  if ((rc = d->ids_all.upload(ids_all.data(), n_all)) || (rc = d->free_all.upload(free_all.data(), n_all)) ||
+      (rc = d->send_all.alloc(n_all * es)) || (rc = d->recv_all.alloc(n_all * es)))
+    return rc;
+  for (int w = 0; w < 2; ++w) {
+    const size_t off = w ? cnt[0] : 0;
+    d->d_ids[w] = d->ids_all.get() + off;
+    d->d_free[w] = d->free_all.get() + off;
+    d->d_send[w] = d->send_all.as<char>() + off * es;
+    d->d_recv[w] = d->recv_all.as<char>() + off * es;
   }
   // highest priority: the exchange's short kernels (pass 2 of the planes, pack, RCCL's send / recv) should get wave
   // slots ahead of the interior cell loop that runs beside them
   int prio_least = 0, prio_greatest = 0;
-  if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
-  if (hipStreamCreateWithPriority(&d->side, hipStreamNonBlocking, prio_greatest) != hipSuccess ||
-      hipEventCreateWithFlags(&d->ev_packed, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&d->ev_if, hipEventDisableTiming) != hipSuccess) {
-    set_error("mfgpu_dist_create: stream / event creation failed");
-    return fail(MFGPU_EHIP);
-  }
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  if ((rc = d->side.create(hipStreamNonBlocking, prio_greatest)) || (rc = d->ev_packed.create(hipEventDisableTiming)) ||
+      (rc = d->ev_done.create(hipEventDisableTiming)) || (rc = d->ev_if.create(hipEventDisableTiming)))
+    return rc;
   if (id128 && world > 1) {
     ncclUniqueId id;
     std::memcpy(&id, id128, sizeof(id));
-    ncclResult_t r = ncclCommInitRank(&d->comm, world, id, rank);
-    if (r != ncclSuccess) {
-      set_error(std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-      d->comm = nullptr;
-      return fail(MFGPU_EHIP);
-    }
+    ncclComm_t comm = nullptr;  // (what a failed call leaves in it is not for ncclCommDestroy)
+    NCCL_TRY(ncclCommInitRank(&comm, world, id, rank));
+    d->comm = comm;
   }
-  *out = d;
+  *out = d.release();
   return 0;
 }
 
@@ -323,11 +302,11 @@ int mfgpu_vmult_dist_begin(mfgpu_handle *h, mfgpu_dist *d, void *dst, const void
     // the interior batches and the rest of pass 2 write every other entry: no two streams touch the same entry.
     int rc = handle_cells_two_ranges(h, 0, d->r1_end, d->r2_begin, d->n_batches, dst, src, stream, 0);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(d->ev_if, st));
-    HIP_TRY(hipStreamWaitEvent(d->side, d->ev_if, 0));
-    rc = handle_pass2_group(h, 0, dst, src, d->side, 0);  // the interface planes hold the slab's sums
-    if (!rc) rc = pack_planes(d, dst, d->side);
-    if (!rc) rc = start_exchange(d, d->side);
+    HIP_TRY(hipEventRecord(d->ev_if.get(), st));
+    HIP_TRY(hipStreamWaitEvent(d->side.get(), d->ev_if.get(), 0));
+    rc = handle_pass2_group(h, 0, dst, src, d->side.get(), 0);  // the interface planes hold the slab's sums
+    if (!rc) rc = pack_planes(d, dst, d->side.get());
+    if (!rc) rc = start_exchange(d, d->side.get());
     if (!rc) rc = handle_cells_range(h, d->r1_end, d->r2_begin, dst, src, stream, 0);  // overlaps the exchange
     if (!rc) rc = handle_pass2_group(h, 1, dst, src, stream, 0);
     return rc;
@@ -365,11 +344,6 @@ void mfgpu_dist_destroy(mfgpu_dist *d) {
   if (d->comm) ncclCommDestroy(d->comm);
   for (int w = 0; w < 2; ++w)
     if (d->local_peer[w]) d->local_peer[w]->local_peer[1 - w] = nullptr;
-  for (void *p : d->d_base) hipFree(p);
-  if (d->side) hipStreamDestroy(d->side);
-  if (d->ev_packed) hipEventDestroy(d->ev_packed);
-  if (d->ev_done) hipEventDestroy(d->ev_done);
-  if (d->ev_if) hipEventDestroy(d->ev_if);
   delete d;
 }
 

@@ -16,6 +16,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -446,50 +447,18 @@ void lagrange(const std::vector<double> &nodes, double y, std::vector<double> &l
   }
 }
 
-#define HIP_TRY(expr)                                                  \
-  do {                                                                 \
-    hipError_t e_ = (expr);                                            \
-    if (e_ != hipSuccess) {                                            \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));    \
-      return e_ == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;    \
-    }                                                                  \
-  } while (0)
-
-template <typename P>
-int upload(P **dst, const void *src, size_t bytes) {
-  *dst = nullptr;
-  if (!bytes) return 0;
-  HIP_TRY(hipMalloc((void **)dst, bytes));
-  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
 }  // namespace
 
 struct mfgpu_integrator {
   int dim = 0, n = 0;
   bool general = false;
   uint32_t n_cells = 0, n_dofs = 0;
-  uint32_t *d_l2g = nullptr, *d_cmask = nullptr, *d_off = nullptr, *d_idx = nullptr;
-  double *d_tab = nullptr, *d_qpts = nullptr, *d_jxw = nullptr, *d_metric = nullptr;
-  double *d_local = nullptr, *d_err = nullptr, *d_ones = nullptr;
+  DeviceArray<uint32_t> d_l2g, d_cmask, d_off, d_idx;
+  DeviceArray<double> d_tab, d_qpts, d_jxw, d_metric;
+  DeviceArray<double> d_local, d_err, d_ones;
 };
 
-void mfgpu_integrator_destroy(mfgpu_integrator *it) {
-  if (!it) return;
-  hipFree(it->d_l2g);
-  hipFree(it->d_cmask);
-  hipFree(it->d_off);
-  hipFree(it->d_idx);
-  hipFree(it->d_tab);
-  hipFree(it->d_qpts);
-  hipFree(it->d_jxw);
-  hipFree(it->d_metric);
-  hipFree(it->d_local);
-  hipFree(it->d_err);
-  hipFree(it->d_ones);
-  delete it;
-}
+void mfgpu_integrator_destroy(mfgpu_integrator *it) { delete it; }
 
 static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
   const int dim = d.dim, n = d.degree + 1, m = n + 1;
@@ -525,11 +494,11 @@ static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
   tab.insert(tab.end(), wm.begin(), wm.end());
   for (int i = 0; i < n * n; ++i) tab.push_back(hn ? d.constraint_weights[i] : 0.0);
   int rc;
-  if ((rc = upload(&it->d_tab, tab.data(), tab.size() * 8))) return rc;
-  if ((rc = upload(&it->d_l2g, d.loc2glob, nc * nd * 4))) return rc;
-  if (hn && (rc = upload(&it->d_cmask, d.constraint_mask, nc * 4))) return rc;
-  if ((rc = upload(&it->d_qpts, d.quadrature_points, nc * nd * dim * 8))) return rc;
-  if ((rc = upload(&it->d_jxw, d.JxW, nc * nd * 8))) return rc;
+  if ((rc = it->d_tab.upload(tab.data(), tab.size()))) return rc;
+  if ((rc = it->d_l2g.upload(d.loc2glob, nc * nd))) return rc;
+  if (hn && (rc = it->d_cmask.upload(d.constraint_mask, nc))) return rc;
+  if ((rc = it->d_qpts.upload(d.quadrature_points, nc * nd * dim))) return rc;
+  if ((rc = it->d_jxw.upload(d.JxW, nc * nd))) return rc;
   // dof -> (cell, local index) CSR, constrained dofs left empty
   std::vector<uint8_t> con(d.n_dofs, 0);
   for (uint32_t i = 0; i < d.n_constrained; ++i) con[d.constrained_dofs[i]] = 1;
@@ -540,49 +509,19 @@ static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
   std::vector<uint32_t> idx(off[d.n_dofs]), pos(off.begin(), off.end() - 1);
   for (size_t j = 0; j < nc * nd; ++j)
     if (!con[d.loc2glob[j]]) idx[pos[d.loc2glob[j]]++] = (uint32_t)j;
-  if ((rc = upload(&it->d_off, off.data(), off.size() * 4))) return rc;
-  if ((rc = upload(&it->d_idx, idx.data(), idx.size() * 4))) return rc;
-  HIP_TRY(hipMalloc((void **)&it->d_local, nc * nd * 8));
-  HIP_TRY(hipMalloc((void **)&it->d_err, nc * 8));
+  if ((rc = it->d_off.upload(off.data(), off.size()))) return rc;
+  if ((rc = it->d_idx.upload(idx.data(), idx.size()))) return rc;
+  if ((rc = it->d_local.alloc(nc * nd))) return rc;
+  if ((rc = it->d_err.alloc(nc))) return rc;
   std::vector<double> ones(nc, 1.0);
-  if ((rc = upload(&it->d_ones, ones.data(), nc * 8))) return rc;
+  if ((rc = it->d_ones.upload(ones.data(), nc))) return rc;
   // coefficient (given, or evaluated from the quadrature points) folded with JxW and the inverse Jacobian by the
-  // operator's own setup kernels (cell order = identity)
-  double *t_coef = nullptr, *t_j = nullptr;
-  uint32_t *t_order = nullptr;
-  auto cleanup = [&]() {
-    hipFree(t_coef);
-    hipFree(t_j);
-    hipFree(t_order);
-  };
+  // operator's own set-up (cell order = identity); it uploads the quadrature points and JxW again as its temporaries
+  // rather than take the resident d_qpts / d_jxw
   std::vector<uint32_t> order(nc);
   for (size_t c = 0; c < nc; ++c) order[c] = (uint32_t)c;
-  const size_t jac = it->general ? nd * dim * dim : 1;
-  const size_t mper = it->general ? (dim == 3 ? 6 : 3) : 1;
-  rc = upload(&t_order, order.data(), nc * 4);
-  if (!rc) rc = upload(&t_j, d.inv_jac, nc * jac * 8);
-  if (!rc && d.coefficient) rc = upload(&t_coef, d.coefficient, nc * nd * 8);
-  if (rc) {
-    cleanup();
-    return rc;
-  }
-  hipError_t e = hipSuccess;
-  if (!d.coefficient) {
-    e = hipMalloc((void **)&t_coef, nc * nd * 8);
-    if (e == hipSuccess) e = coefficient_launch<double>(t_coef, it->d_qpts, nc * nd, dim, nullptr);
-  }
-  if (e == hipSuccess) e = hipMalloc((void **)&it->d_metric, nc * nd * mper * 8);
-  if (e == hipSuccess)
-    e = !it->general ? fold_launch<double>(it->d_metric, t_coef, it->d_jxw, t_j, t_order, (uint32_t)nc, (uint32_t)nd, nullptr)
-        : dim == 3   ? fold_general_launch<double>(it->d_metric, t_coef, it->d_jxw, t_j, t_order, (uint32_t)nc, (uint32_t)nd, nullptr)
-                     : fold_general2_launch<double>(it->d_metric, t_coef, it->d_jxw, t_j, t_order, (uint32_t)nc, (uint32_t)nd, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  cleanup();
-  if (e != hipSuccess) {
-    set_error(std::string("integrator coefficient fold: ") + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;
-  }
-  return 0;
+  return fold_coefficient<double>(it->d_metric, d.coefficient, d.quadrature_points, d.JxW, d.inv_jac, order.data(), dim,
+                                  (uint32_t)nc, (uint32_t)nd, it->general);
 }
 
 int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out) {
@@ -628,24 +567,20 @@ int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out) {
       set_error("constrained dof out of range");
       return MFGPU_EINVAL;
     }
-  mfgpu_integrator *it = new mfgpu_integrator();
-  const int rc = integrator_setup(it, d);
-  if (rc) {
-    mfgpu_integrator_destroy(it);
-    return rc;
-  }
-  *out = it;
+  std::unique_ptr<mfgpu_integrator> it(new mfgpu_integrator());
+  if (const int rc = integrator_setup(it.get(), d)) return rc;
+  *out = it.release();
   return 0;
 }
 
 static IntArgs base_args(const mfgpu_integrator *it) {
   IntArgs a{};
-  a.loc2glob = it->d_l2g;
-  a.cmask = it->d_cmask;
-  a.tab = it->d_tab;
-  a.qpts = it->d_qpts;
-  a.jxw = it->d_jxw;
-  a.metric = it->d_metric;
+  a.loc2glob = it->d_l2g.get();
+  a.cmask = it->d_cmask.get();
+  a.tab = it->d_tab.get();
+  a.qpts = it->d_qpts.get();
+  a.jxw = it->d_jxw.get();
+  a.metric = it->d_metric.get();
   a.general = it->general ? 1 : 0;
   a.n_cells = it->n_cells;
   return a;
@@ -660,10 +595,10 @@ int mfgpu_integrator_rhs(mfgpu_integrator *it, void *rhs, const void *f_qp, cons
   IntArgs a = base_args(it);
   a.f_qp = (const double *)f_qp;
   a.u_b = (const double *)u_b;
-  a.local = it->d_local;
+  a.local = it->d_local.get();
   HIP_TRY(launch(it->dim, it->n, RHS, a, st));
   hipLaunchKernelGGL(rhs_gather_kernel, dim3((it->n_dofs + 255) / 256), dim3(256), 0, st, (double *)rhs,
-                     (const double *)it->d_local, it->d_off, it->d_idx, it->n_dofs);
+                     (const double *)it->d_local.get(), it->d_off.get(), it->d_idx.get(), it->n_dofs);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -678,10 +613,10 @@ int mfgpu_integrator_l2_error(mfgpu_integrator *it, const void *u, const void *e
   IntArgs a = base_args(it);
   a.u = (const double *)u;
   a.exact = (const double *)exact;
-  a.per_cell = per_cell ? (double *)per_cell : it->d_err;
+  a.per_cell = per_cell ? (double *)per_cell : it->d_err.get();
   HIP_TRY(launch(it->dim, it->n, L2, a, st));
   double sum = 0;
-  HIP_TRY(vec_reduce_launch<double>(0, a.per_cell, nullptr, it->d_ones, 0.0, it->n_cells, st, &sum));
+  HIP_TRY(vec_reduce_launch<double>(0, a.per_cell, nullptr, it->d_ones.get(), 0.0, it->n_cells, st, &sum));
   *l2 = std::sqrt(sum);
   return 0;
 }

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "mfgpu_device.h"
 #include "mfgpu_internal.h"
 
 namespace mfgpu {
@@ -122,6 +123,14 @@ hipError_t fold_launch(T *c, const T *coef, const T *jxw, const T *j0, const uin
                        uint32_t n_cells, uint32_t nd, hipStream_t st);
 template <typename T>
 hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st);
+// Set-up of the folded metric, synchronised on return: the description's coefficient (or, if NULL, the coefficient
+// evaluated from its quadrature_points), JxW and inv_jac go to the device as temporaries and are folded into `out`,
+// nd points per cell in the order cell_order[0 .. n_cells).  Per point the scalar a J0^2 JxW, or with `general` the
+// symmetric a JxW J^-1 J^-T (6 entries in 3D, 3 in 2D) from the full J^-1 per point.
+template <typename T>
+int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *quadrature_points, const void *JxW,
+                     const void *inv_jac, const uint32_t *cell_order, int dim, uint32_t n_cells, uint32_t nd,
+                     bool general);
 
 // ---- SURVEY.md 8(f) N1 / N2 (mfgpu_aux.hip)
 template <typename T>

@@ -469,6 +469,34 @@ hipError_t fold_launch(T *c, const T *coef, const T *jxw, const T *j0, const uin
 }
 
 template <typename T>
+int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *quadrature_points, const void *JxW,
+                     const void *inv_jac, const uint32_t *cell_order, int dim, uint32_t n_cells, uint32_t nd,
+                     bool general) {
+  const size_t np = (size_t)n_cells * nd;
+  DeviceArray<T> coef, qpts, jxw, jinv;
+  DeviceArray<uint32_t> order;
+  int rc;
+  if (coefficient) {
+    if ((rc = coef.upload(coefficient, np))) return rc;
+  } else {
+    if ((rc = qpts.upload(quadrature_points, np * dim))) return rc;
+    if ((rc = coef.alloc(np))) return rc;
+    if ((rc = hip_check(coefficient_launch<T>(coef.get(), qpts.get(), np, dim, nullptr), "coefficient evaluation")))
+      return rc;
+  }
+  if ((rc = jxw.upload(JxW, np))) return rc;
+  // full J^-1 per point, or one scalar per cell
+  if ((rc = jinv.upload(inv_jac, general ? np * (size_t)(dim * dim) : n_cells))) return rc;
+  if ((rc = order.upload(cell_order, n_cells))) return rc;
+  if ((rc = out.alloc(np * (general ? (dim == 3 ? 6 : 3) : 1)))) return rc;
+  const auto fold = !general ? fold_launch<T> : dim == 3 ? fold_general_launch<T> : fold_general2_launch<T>;
+  if ((rc = hip_check(fold(out.get(), coef.get(), jxw.get(), jinv.get(), order.get(), n_cells, nd, nullptr),
+                      "coefficient fold")))
+    return rc;
+  return hip_check(hipDeviceSynchronize(), "coefficient fold");
+}
+
+template <typename T>
 hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
   if (n == 0) return hipSuccess;
   size_t blocks = (n + 255) / 256;
@@ -485,6 +513,8 @@ hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
   template hipError_t coefficient_launch<T>(T *, const T *, size_t, int, hipStream_t);                  \
   template hipError_t fold_launch<T>(T *, const T *, const T *, const T *, const uint32_t *, uint32_t,  \
                                      uint32_t, hipStream_t);                                            \
+  template int fold_coefficient<T>(DeviceArray<T> &, const void *, const void *, const void *, const void *,       \
+                                   const uint32_t *, int, uint32_t, uint32_t, bool);                    \
   template hipError_t fill_launch<T>(T *, size_t, T, hipStream_t);
 INST(double)
 INST(float)

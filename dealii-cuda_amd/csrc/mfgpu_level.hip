@@ -17,22 +17,25 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "mfgpu_internal.h"
+#include "mfgpu_device.h"
+
+using namespace mfgpu;
 
 struct mfgpu_level {
   mfgpu_handle *A = nullptr, *Ab = nullptr;
-  uint32_t *d_c = nullptr, *d_e = nullptr;  // C = Dirichlet + edge, E = edge (device index lists)
+  DeviceArray<uint32_t> d_c, d_e;  // C = Dirichlet + edge, E = edge (device index lists)
   uint32_t n_c = 0, n_e = 0, n_dofs = 0;
   int number_type = MFGPU_F64;
-  void *tmp_x = nullptr, *tmp_y = nullptr;
+  DeviceArray<void> tmp_x, tmp_y;
 };
 
 // index pairs on the device: copy_to_mg / copy_from_mg (mg_transfer_matrix_free_gpu.cu:690-760, copy_indices)
 struct mfgpu_index_pairs {
-  uint32_t *d_dst = nullptr, *d_src = nullptr;
+  DeviceArray<uint32_t> d_dst, d_src;
   uint32_t n = 0;
 };
 
@@ -66,29 +69,28 @@ __global__ void copy_indexed_kernel(T *dst, const T *src, const uint32_t *idx, u
 template <typename T>
 int interface_typed(mfgpu_level *L, bool down, T *dst, const T *src, hipStream_t st) {
   const size_t bytes = (size_t)L->n_dofs * sizeof(T);
-  T *x = (T *)L->tmp_x, *y = (T *)L->tmp_y;
+  T *x = L->tmp_x.as<T>(), *y = L->tmp_y.as<T>();
+  const uint32_t *c = L->d_c.get(), *e = L->d_e.get();
   const unsigned gc = (L->n_c + 255) / 256, ge = (L->n_e + 255) / 256;
   if (L->n_e == 0) {  // no refinement edge on this level: both matrices are zero
-    if (hipMemsetAsync(dst, 0, bytes, st) != hipSuccess) return MFGPU_EHIP;
+    HIP_TRY(hipMemsetAsync(dst, 0, bytes, st));
     return 0;
   }
   if (down) {
     // x = src with C zeroed (constraint_handler.save_constrained_values, :315); y = K x; dst = 0, dst[E] = y[E]
-    if (hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return MFGPU_EHIP;
-    hipLaunchKernelGGL(set_indexed_kernel<T>, dim3(gc), dim3(256), 0, st, x, L->d_c, L->n_c, T(0));
-    int rc = mfgpu_vmult(L->Ab, y, x, st);
-    if (rc) return rc;
-    if (hipMemsetAsync(dst, 0, bytes, st) != hipSuccess) return MFGPU_EHIP;
-    hipLaunchKernelGGL(copy_indexed_kernel<T>, dim3(ge), dim3(256), 0, st, dst, (const T *)y, L->d_e, L->n_e);
+    HIP_TRY(hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(set_indexed_kernel<T>, dim3(gc), dim3(256), 0, st, x, c, L->n_c, T(0));
+    if (const int rc = mfgpu_vmult(L->Ab, y, x, st)) return rc;
+    HIP_TRY(hipMemsetAsync(dst, 0, bytes, st));
+    hipLaunchKernelGGL(copy_indexed_kernel<T>, dim3(ge), dim3(256), 0, st, dst, (const T *)y, e, L->n_e);
   } else {
     // x = 0 except the edge values of src (copy_edge_values, :343); dst = K x; dst[C] = 0 (:351)
-    if (hipMemsetAsync(x, 0, bytes, st) != hipSuccess) return MFGPU_EHIP;
-    hipLaunchKernelGGL(copy_indexed_kernel<T>, dim3(ge), dim3(256), 0, st, x, src, L->d_e, L->n_e);
-    int rc = mfgpu_vmult(L->Ab, dst, x, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(set_indexed_kernel<T>, dim3(gc), dim3(256), 0, st, dst, L->d_c, L->n_c, T(0));
+    HIP_TRY(hipMemsetAsync(x, 0, bytes, st));
+    hipLaunchKernelGGL(copy_indexed_kernel<T>, dim3(ge), dim3(256), 0, st, x, src, e, L->n_e);
+    if (const int rc = mfgpu_vmult(L->Ab, dst, x, st)) return rc;
+    hipLaunchKernelGGL(set_indexed_kernel<T>, dim3(gc), dim3(256), 0, st, dst, c, L->n_c, T(0));
   }
-  return hipGetLastError() == hipSuccess ? 0 : MFGPU_EHIP;
+  return hip_check(hipGetLastError(), "level interface kernels");
 }
 
 }  // namespace
@@ -96,7 +98,6 @@ int interface_typed(mfgpu_level *L, bool down, T *dst, const T *src, hipStream_t
 extern "C" {
 
 int mfgpu_level_create(const mfgpu_desc *desc, const uint32_t *edge_dofs, uint32_t n_edge, mfgpu_level **out) {
-  using mfgpu::set_error;
   if (!desc || !out || (n_edge && !edge_dofs)) {
     set_error("mfgpu_level_create: null argument");
     return MFGPU_EINVAL;
@@ -116,35 +117,27 @@ int mfgpu_level_create(const mfgpu_desc *desc, const uint32_t *edge_dofs, uint32
   c.insert(c.end(), e.begin(), e.end());
   std::sort(c.begin(), c.end());
   c.erase(std::unique(c.begin(), c.end()), c.end());
-  mfgpu_level *L = new mfgpu_level();
+  std::unique_ptr<mfgpu_level, decltype(&mfgpu_level_destroy)> L(new mfgpu_level(), mfgpu_level_destroy);
   L->n_dofs = desc->n_dofs;
   L->number_type = desc->number_type;
   L->n_e = (uint32_t)e.size();
   L->n_c = (uint32_t)c.size();
-  auto fail = [&](int rc) {
-    mfgpu_level_destroy(L);
-    return rc;
-  };
   mfgpu_desc da = *desc;
   da.constrained_dofs = c.data();
   da.n_constrained = (uint32_t)c.size();
   int rc = mfgpu_create(&da, &L->A);
-  if (rc) return fail(rc);
+  if (rc) return rc;
   if (L->n_e) {
     mfgpu_desc db = *desc;
     db.constrained_dofs = nullptr;
     db.n_constrained = 0;
-    if ((rc = mfgpu_create(&db, &L->Ab))) return fail(rc);
-    const size_t es = desc->number_type == MFGPU_F64 ? 8 : 4;
-    if (hipMalloc((void **)&L->d_c, c.size() * 4) != hipSuccess || hipMalloc((void **)&L->d_e, e.size() * 4) != hipSuccess ||
-        hipMalloc(&L->tmp_x, (size_t)L->n_dofs * es) != hipSuccess || hipMalloc(&L->tmp_y, (size_t)L->n_dofs * es) != hipSuccess ||
-        hipMemcpy(L->d_c, c.data(), c.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(L->d_e, e.data(), e.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("mfgpu_level_create: device allocation failed");
-      return fail(MFGPU_ENOMEM);
-    }
+    if ((rc = mfgpu_create(&db, &L->Ab))) return rc;
+    const size_t vec_bytes = (size_t)L->n_dofs * esize(desc->number_type);
+    if ((rc = L->d_c.upload(c.data(), c.size())) || (rc = L->d_e.upload(e.data(), e.size())) ||
+        (rc = L->tmp_x.alloc(vec_bytes)) || (rc = L->tmp_y.alloc(vec_bytes)))
+      return rc;
   }
-  *out = L;
+  *out = L.release();
   return 0;
 }
 
@@ -152,7 +145,7 @@ mfgpu_handle *mfgpu_level_operator(mfgpu_level *L) { return L ? L->A : nullptr; 
 
 int mfgpu_level_vmult_interface_down(mfgpu_level *L, void *dst, const void *src, void *stream) {
   if (!L || !dst || !src || dst == src) {
-    mfgpu::set_error("mfgpu_level_vmult_interface_down: null or aliasing argument");
+    set_error("mfgpu_level_vmult_interface_down: null or aliasing argument");
     return MFGPU_EINVAL;
   }
   return L->number_type == MFGPU_F64 ? interface_typed<double>(L, true, (double *)dst, (const double *)src, (hipStream_t)stream)
@@ -161,7 +154,7 @@ int mfgpu_level_vmult_interface_down(mfgpu_level *L, void *dst, const void *src,
 
 int mfgpu_level_vmult_interface_up(mfgpu_level *L, void *dst, const void *src, void *stream) {
   if (!L || !dst || !src || dst == src) {
-    mfgpu::set_error("mfgpu_level_vmult_interface_up: null or aliasing argument");
+    set_error("mfgpu_level_vmult_interface_up: null or aliasing argument");
     return MFGPU_EINVAL;
   }
   return L->number_type == MFGPU_F64 ? interface_typed<double>(L, false, (double *)dst, (const double *)src, (hipStream_t)stream)
@@ -170,46 +163,41 @@ int mfgpu_level_vmult_interface_up(mfgpu_level *L, void *dst, const void *src, v
 
 int mfgpu_index_pairs_create(const uint32_t *dst_idx, const uint32_t *src_idx, uint32_t n, mfgpu_index_pairs **out) {
   if (!out || (n && (!dst_idx || !src_idx))) {
-    mfgpu::set_error("mfgpu_index_pairs_create: null argument");
+    set_error("mfgpu_index_pairs_create: null argument");
     return MFGPU_EINVAL;
   }
-  mfgpu_index_pairs *p = new mfgpu_index_pairs();
+  std::unique_ptr<mfgpu_index_pairs> p(new mfgpu_index_pairs());
   p->n = n;
-  if (n && (hipMalloc((void **)&p->d_dst, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&p->d_src, (size_t)n * 4) != hipSuccess ||
-            hipMemcpy(p->d_dst, dst_idx, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->d_src, src_idx, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess)) {
-    mfgpu::set_error("mfgpu_index_pairs_create: device allocation failed");
-    mfgpu_index_pairs_destroy(p);
-    return MFGPU_ENOMEM;
-  }
-  *out = p;
+  int rc;
+  if ((rc = p->d_dst.upload(dst_idx, n)) || (rc = p->d_src.upload(src_idx, n))) return rc;
+  *out = p.release();
   return 0;
 }
 
 int mfgpu_vec_copy_pairs(const mfgpu_index_pairs *p, void *dst, const void *src, int number_type, void *stream) {
   if (!p || !dst || !src) {
-    mfgpu::set_error("mfgpu_vec_copy_pairs: null argument");
+    set_error("mfgpu_vec_copy_pairs: null argument");
     return MFGPU_EINVAL;
   }
   if (p->n == 0) return 0;
   const unsigned grid = (p->n + 255) / 256;
   if (number_type == MFGPU_F64)
     hipLaunchKernelGGL(copy_pairs_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (double *)dst,
-                       (const double *)src, p->d_dst, p->d_src, p->n);
+                       (const double *)src, p->d_dst.get(), p->d_src.get(), p->n);
   else
     hipLaunchKernelGGL(copy_pairs_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float *)dst,
-                       (const float *)src, p->d_dst, p->d_src, p->n);
-  return hipGetLastError() == hipSuccess ? 0 : MFGPU_EHIP;
+                       (const float *)src, p->d_dst.get(), p->d_src.get(), p->n);
+  return hip_check(hipGetLastError(), "copy_pairs_kernel");
 }
 
 int mfgpu_vec_copy_pairs_convert(const mfgpu_index_pairs *p, void *dst, int dst_type, const void *src, int src_type,
                                  void *stream) {
-  if ((dst_type != MFGPU_F64 && dst_type != MFGPU_F32) || (src_type != MFGPU_F64 && src_type != MFGPU_F32)) {
-    mfgpu::set_error("mfgpu_vec_copy_pairs_convert: number type must be MFGPU_F64 or MFGPU_F32");
+  if (!valid_number_type(dst_type) || !valid_number_type(src_type)) {
+    set_error("mfgpu_vec_copy_pairs_convert: number type must be MFGPU_F64 or MFGPU_F32");
     return MFGPU_EINVAL;
   }
   if (!p || !dst || !src) {
-    mfgpu::set_error("mfgpu_vec_copy_pairs_convert: null argument");
+    set_error("mfgpu_vec_copy_pairs_convert: null argument");
     return MFGPU_EINVAL;
   }
   if (p->n == 0) return 0;
@@ -217,7 +205,7 @@ int mfgpu_vec_copy_pairs_convert(const mfgpu_index_pairs *p, void *dst, int dst_
   const hipStream_t st = (hipStream_t)stream;
 #define CPC(D, S)                                                                                                  \
   hipLaunchKernelGGL((copy_pairs_convert_kernel<D, S>), dim3(grid), dim3(256), 0, st, (D *)dst, (const S *)src, \
-                     p->d_dst, p->d_src, p->n)
+                     p->d_dst.get(), p->d_src.get(), p->n)
   if (dst_type == MFGPU_F64 && src_type == MFGPU_F64)
     CPC(double, double);
   else if (dst_type == MFGPU_F64)
@@ -227,24 +215,15 @@ int mfgpu_vec_copy_pairs_convert(const mfgpu_index_pairs *p, void *dst, int dst_
   else
     CPC(float, float);
 #undef CPC
-  return hipGetLastError() == hipSuccess ? 0 : MFGPU_EHIP;
+  return hip_check(hipGetLastError(), "copy_pairs_convert_kernel");
 }
 
-void mfgpu_index_pairs_destroy(mfgpu_index_pairs *p) {
-  if (!p) return;
-  hipFree(p->d_dst);
-  hipFree(p->d_src);
-  delete p;
-}
+void mfgpu_index_pairs_destroy(mfgpu_index_pairs *p) { delete p; }
 
 void mfgpu_level_destroy(mfgpu_level *L) {
   if (!L) return;
   mfgpu_destroy(L->A);
   mfgpu_destroy(L->Ab);
-  hipFree(L->d_c);
-  hipFree(L->d_e);
-  hipFree(L->tmp_x);
-  hipFree(L->tmp_y);
   delete L;
 }
 

@@ -11,7 +11,7 @@
 
 #include <cstdint>
 
-#include "mfgpu_internal.h"
+#include "mfgpu_device.h"
 
 namespace {
 
@@ -181,15 +181,6 @@ unsigned grid_for(size_t work) {
 
 bool aligned16(const void *p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
-bool valid_type(int nt) { return nt == MFGPU_F64 || nt == MFGPU_F32; }
-
-int hip_status(const char *what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return MFGPU_OK;
-  mfgpu::set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return MFGPU_EHIP;
-}
-
 int einval(const char *msg) {
   mfgpu::set_error(msg);
   return MFGPU_EINVAL;
@@ -251,30 +242,26 @@ bool outputs_alias(const void *x, const void *upd, const void *r, const void *a,
 extern "C" {
 
 int mfgpu_vec_convert(void *dst, int dst_type, const void *src, int src_type, size_t n, void *stream) {
-  if (!valid_type(dst_type) || !valid_type(src_type)) return einval("mfgpu_vec_convert: number type must be MFGPU_F64 or MFGPU_F32");
+  if (!mfgpu::valid_number_type(dst_type) || !mfgpu::valid_number_type(src_type)) return einval("mfgpu_vec_convert: number type must be MFGPU_F64 or MFGPU_F32");
   if (n == 0) return MFGPU_OK;
   if (!dst || !src) return einval("mfgpu_vec_convert: null vector");
   const hipStream_t st = (hipStream_t)stream;
   if (dst_type == src_type) {
     if (dst == src) return MFGPU_OK;
-    const hipError_t e = hipMemcpyAsync(dst, src, n * (dst_type == MFGPU_F64 ? 8 : 4), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) {
-      mfgpu::set_error(std::string("mfgpu_vec_convert: ") + hipGetErrorString(e));
-      return MFGPU_EHIP;
-    }
-    return MFGPU_OK;
+    return mfgpu::hip_check(hipMemcpyAsync(dst, src, n * mfgpu::esize(dst_type), hipMemcpyDeviceToDevice, st),
+                            "mfgpu_vec_convert");
   }
   if (dst == src) return einval("mfgpu_vec_convert: dst and src must not alias");
   if (dst_type == MFGPU_F32)
     convert_launch<float, double>((float *)dst, (const double *)src, n, st);
   else
     convert_launch<double, float>((double *)dst, (const float *)src, n, st);
-  return hip_status("mfgpu_vec_convert");
+  return mfgpu::hip_check(hipGetLastError(), "mfgpu_vec_convert");
 }
 
 int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const void *t, const void *dinv, double f,
                               int zero_start, size_t n, int number_type, void *stream) {
-  if (!valid_type(number_type)) return einval("mfgpu_vec_chebyshev_start: number type must be MFGPU_F64 or MFGPU_F32");
+  if (!mfgpu::valid_number_type(number_type)) return einval("mfgpu_vec_chebyshev_start: number type must be MFGPU_F64 or MFGPU_F32");
   if (n == 0) return MFGPU_OK;
   if (!x || !upd || !r || !b || !dinv) return einval("mfgpu_vec_chebyshev_start: null vector");
   if (outputs_alias(x, upd, r, b, t, dinv)) return einval("mfgpu_vec_chebyshev_start: x, upd and r must not alias each other or an input");
@@ -285,12 +272,12 @@ int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const 
   else
     cheb_start_launch<float>((float *)x, (float *)upd, (float *)r, (const float *)b, (const float *)t,
                              (const float *)dinv, (float)f, zero_start != 0, n, st);
-  return hip_status("mfgpu_vec_chebyshev_start");
+  return mfgpu::hip_check(hipGetLastError(), "mfgpu_vec_chebyshev_start");
 }
 
 int mfgpu_vec_chebyshev_update(void *x, void *upd, void *r, const void *t, const void *dinv, double f1, double f2,
                                size_t n, int number_type, void *stream) {
-  if (!valid_type(number_type)) return einval("mfgpu_vec_chebyshev_update: number type must be MFGPU_F64 or MFGPU_F32");
+  if (!mfgpu::valid_number_type(number_type)) return einval("mfgpu_vec_chebyshev_update: number type must be MFGPU_F64 or MFGPU_F32");
   if (n == 0) return MFGPU_OK;
   if (!x || !upd || !r || !t || !dinv) return einval("mfgpu_vec_chebyshev_update: null vector");
   if (outputs_alias(x, upd, r, t, dinv, nullptr)) return einval("mfgpu_vec_chebyshev_update: x, upd and r must not alias each other or an input");
@@ -301,7 +288,7 @@ int mfgpu_vec_chebyshev_update(void *x, void *upd, void *r, const void *t, const
   else
     cheb_update_launch<float>((float *)x, (float *)upd, (float *)r, (const float *)t, (const float *)dinv, (float)f1,
                               (float)f2, n, st);
-  return hip_status("mfgpu_vec_chebyshev_update");
+  return mfgpu::hip_check(hipGetLastError(), "mfgpu_vec_chebyshev_update");
 }
 
 }  // extern "C"

@@ -22,33 +22,25 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "mfgpu_internal.h"
+#include "mfgpu_device.h"
 #include "mfgpu_mesh.h"
 
 struct mfgpu_transfer {
   int dim = 0, degree = 0, number_type = MFGPU_F64;
   uint32_t n_coarse_cells = 0, n_coarse_dofs = 0, n_fine_dofs = 0;
-  uint32_t *d_coarse = nullptr, *d_fine = nullptr;  // [cells][(p+1)^dim], [cells][(2p+1)^dim]
-  void *d_p1 = nullptr;                             // P1[(2p+1) * (p+1)], X-major
-  bool covers_all = true;                           // every fine dof is listed by some patch
+  mfgpu::DeviceArray<uint32_t> d_coarse, d_fine;  // [cells][(p+1)^dim], [cells][(2p+1)^dim]
+  mfgpu::DeviceArray<void> d_p1;                  // P1[(2p+1) * (p+1)], X-major
+  bool covers_all = true;                         // every fine dof is listed by some patch
   size_t device_bytes = 0;
 };
 
 namespace mfgpu {
 
 namespace {
-
-#define HIP_TRY_T(expr)                                                            \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                \
-      return e_ == hipErrorOutOfMemory ? MFGPU_ENOMEM : MFGPU_EHIP;                \
-    }                                                                              \
-  } while (0)
 
 constexpr int ipow_c(int a, int e) { return e == 0 ? 1 : a * ipow_c(a, e - 1); }
 
@@ -119,8 +111,8 @@ hipError_t launch(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t st)
   const unsigned grid = n < 8192u ? n : 8192u;
 #define TR_CASE(D, PP)                                                                                           \
   case D * 10 + PP:                                                                                              \
-    hipLaunchKernelGGL((transfer_kernel<D, PP, T, RESTRICT>), dim3(grid), dim3(256), 0, st, dst, src, t->d_coarse, \
-                       t->d_fine, (const T *)t->d_p1, n);                                                         \
+    hipLaunchKernelGGL((transfer_kernel<D, PP, T, RESTRICT>), dim3(grid), dim3(256), 0, st, dst, src,           \
+                       t->d_coarse.get(), t->d_fine.get(), t->d_p1.as<const T>(), n);                            \
     break;
   switch (t->dim * 10 + t->degree) {
     TR_CASE(2, 1) TR_CASE(2, 2) TR_CASE(2, 3) TR_CASE(2, 4) TR_CASE(2, 5) TR_CASE(2, 6)
@@ -166,7 +158,7 @@ int mfgpu_transfer_create(int dim, int degree, int number_type, uint32_t n_coars
                           mfgpu_transfer **out) {
   using namespace mfgpu;
   if (!out || (dim != 2 && dim != 3) || degree < 1 || degree > 6 || (n_coarse_cells && (!coarse_cell_dofs || !fine_patch_dofs)) ||
-      (n_coarse_dirichlet && !coarse_dirichlet) || (number_type != MFGPU_F64 && number_type != MFGPU_F32) ||
+      (n_coarse_dirichlet && !coarse_dirichlet) || !valid_number_type(number_type) ||
       n_coarse_dofs >= (1u << 31) || n_fine_dofs >= (1u << 31)) {
     set_error("mfgpu_transfer_create: bad argument");
     return MFGPU_EINVAL;
@@ -206,7 +198,7 @@ int mfgpu_transfer_create(int dim, int degree, int number_type, uint32_t n_coars
     P1.assign(prolongation_1d, prolongation_1d + (size_t)nf * nc);
   else
     default_prolongation_1d(degree, P1);
-  mfgpu_transfer *t = new mfgpu_transfer();
+  std::unique_ptr<mfgpu_transfer> t(new mfgpu_transfer());
   t->dim = dim;
   t->degree = degree;
   t->number_type = number_type;
@@ -214,26 +206,14 @@ int mfgpu_transfer_create(int dim, int degree, int number_type, uint32_t n_coars
   t->n_coarse_dofs = n_coarse_dofs;
   t->n_fine_dofs = n_fine_dofs;
   t->covers_all = covered == n_fine_dofs;
-  auto fail = [&](int rc) {
-    mfgpu_transfer_destroy(t);
-    return rc;
-  };
   std::vector<float> P1f(P1.begin(), P1.end());
   const void *p1src = number_type == MFGPU_F64 ? (const void *)P1.data() : (const void *)P1f.data();
-  const size_t p1b = P1.size() * (number_type == MFGPU_F64 ? 8 : 4);
-  if ((cd.size() && hipMalloc((void **)&t->d_coarse, cd.size() * 4) != hipSuccess) ||
-      (fd.size() && hipMalloc((void **)&t->d_fine, fd.size() * 4) != hipSuccess) || hipMalloc(&t->d_p1, p1b) != hipSuccess) {
-    set_error("mfgpu_transfer_create: device allocation failed");
-    return fail(MFGPU_ENOMEM);
-  }
-  if ((cd.size() && hipMemcpy(t->d_coarse, cd.data(), cd.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-      (fd.size() && hipMemcpy(t->d_fine, fd.data(), fd.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(t->d_p1, p1src, p1b, hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("mfgpu_transfer_create: upload failed");
-    return fail(MFGPU_EHIP);
-  }
-  t->device_bytes = (cd.size() + fd.size()) * 4 + p1b;
-  *out = t;
+  int rc;
+  if ((rc = t->d_coarse.upload(cd.data(), cd.size())) || (rc = t->d_fine.upload(fd.data(), fd.size())) ||
+      (rc = t->d_p1.upload(p1src, P1.size() * esize(number_type))))
+    return rc;
+  t->device_bytes = t->d_coarse.bytes() + t->d_fine.bytes() + t->d_p1.bytes();
+  *out = t.release();
   return 0;
 }
 
@@ -260,10 +240,10 @@ int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src
   hipStream_t st = (hipStream_t)stream;
   if (t->number_type == MFGPU_F64) {
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<double>, dim3(2048), dim3(256), 0, st, (double *)dst_fine, (size_t)t->n_fine_dofs);
-    HIP_TRY_T((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
+    HIP_TRY((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
   } else {
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst_fine, (size_t)t->n_fine_dofs);
-    HIP_TRY_T((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
+    HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
   }
   return 0;
 }
@@ -276,20 +256,14 @@ int mfgpu_transfer_restrict_and_add(mfgpu_transfer *t, void *dst_coarse, const v
   }
   hipStream_t st = (hipStream_t)stream;
   if (t->number_type == MFGPU_F64)
-    HIP_TRY_T((launch<double, true>(t, (double *)dst_coarse, (const double *)src_fine, st)));
+    HIP_TRY((launch<double, true>(t, (double *)dst_coarse, (const double *)src_fine, st)));
   else
-    HIP_TRY_T((launch<float, true>(t, (float *)dst_coarse, (const float *)src_fine, st)));
+    HIP_TRY((launch<float, true>(t, (float *)dst_coarse, (const float *)src_fine, st)));
   return 0;
 }
 
 size_t mfgpu_transfer_memory_consumption(const mfgpu_transfer *t) { return t ? t->device_bytes : 0; }
 
-void mfgpu_transfer_destroy(mfgpu_transfer *t) {
-  if (!t) return;
-  hipFree(t->d_coarse);
-  hipFree(t->d_fine);
-  hipFree(t->d_p1);
-  delete t;
-}
+void mfgpu_transfer_destroy(mfgpu_transfer *t) { delete t; }
 
 }  // extern "C"

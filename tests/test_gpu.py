@@ -557,8 +557,9 @@ def test_cxx_slab_exchange_in_process(p, n, world, first, nt):
 
 def test_create_destroy_returns_all_device_memory():
     """mfgpu_destroy / mfgpu_vec_free give back everything mfgpu_create / mfgpu_vec_alloc / the first vmult,
-    diagonal and reduction took: repeated set-up and tear-down of operators of every kernel family must not
-    shrink the free device memory (hipMemGetInfo)."""
+    diagonal and reduction took, and so do the destroy functions of the other handle kinds (level, transfer,
+    integrator, index pairs, slab exchange): repeated set-up and tear-down of operators of every kernel family
+    and of those handles must not shrink the free device memory (hipMemGetInfo)."""
     from util import deformed_oracle_desc
 
     def cycle():
@@ -581,6 +582,63 @@ def test_create_destroy_returns_all_device_memory():
             mf.synchronize()
             op.clear()
             del a, b, op
+        other_handles()
+
+    def other_handles():
+        """the handle kinds besides the operator, each created, used once and destroyed"""
+        mesh = mf.Mesh.uniform(3, 2, 4)
+        n = mesh.n_dofs
+        a, b = mf.DeviceVector(n), mf.DeviceVector(n)
+        a.fill(1.0)
+        # level operator with a refinement edge: two child operators + the interface matrices' temporaries
+        x = mesh.dof_coords()
+        edge = np.nonzero(np.abs(x[:, 0]) < 1e-12)[0].astype(np.uint32)
+        assert 0 < len(edge) < n
+        lev = mf.Level(mesh.desc, edge, mesh)
+        lev.vmult(b, a)
+        lev.vmult_interface_down(b, a)
+        lev.vmult_interface_up(b, a)
+        # level transfer
+        coarse = mf.Mesh.uniform(3, 2, 2)
+        tr = mf.Transfer.from_meshes(coarse, mesh)
+        c = mf.DeviceVector(coarse.n_dofs)
+        c.fill(1.0)
+        tr.prolongate(b, c)
+        # integrator
+        it = mf.Integrator(mesh.desc, mesh)
+        it.rhs(b)
+        assert np.isfinite(it.l2_error(a))
+        # index pairs
+        idx = np.arange(n, dtype=np.uint32)
+        pairs = mf.IndexPairs(idx, idx[::-1].copy())
+        pairs.copy(b, a)
+        mf.synchronize()
+        del lev, tr, it, pairs, c
+        # two slabs on the in-process transport; attach rebuilds the live operators' pass-2 arrays
+        slabs = []
+        for r, (zb, ze) in enumerate(((0, 3), (3, 6))):
+            sm = mf.Mesh.uniform(3, 4, 6, slab=(zb, ze))
+            op, dist = mf.Operator(sm.desc, sm), mf.Dist(sm, r, 2)
+            u, v = mf.DeviceVector(sm.n_dofs), mf.DeviceVector(sm.n_dofs)
+            u.fill(1.0)
+            op.vmult(v, u)
+            dist.attach(op)
+            slabs.append((op, dist, u, v))
+        slabs[0][1].connect_local(slabs[1][1])
+        for op, dist, u, v in slabs:
+            dist.vmult_begin(op, v, u)
+        for op, dist, u, v in slabs:
+            dist.vmult_end(op, v)
+        mf.synchronize()
+        del slabs, op, dist, u, v
+        # an operator with profiling on: the timing events are the handle's too
+        op = mf.Operator(mesh.desc, mesh)
+        op.profile_enable(True)
+        for _ in range(3):
+            op.vmult(b, a)
+        ms, nv = op.profile_read()
+        assert nv == 3 and ms > 0.0 and op.profile_read_pass2() > 0.0
+        del op, a, b
 
     cycle()                       # first use allocates the per-device reduction scratch (kept by design)
     mf.synchronize()
