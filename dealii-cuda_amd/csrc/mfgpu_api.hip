@@ -67,6 +67,10 @@ struct mfgpu_handle {
   DeviceArray<uint16_t> d_perm;  // apply_batches_x: bank-conflict-free lane -> pencil maps of the y- and z-stage
   // apply_planes3: fixed-size per-batch records (see ApplyArgs)
   DeviceArray<uint32_t> d_bdofsp, d_idxp;
+  // ... or their shared form (Plan::sh_*): d_bdofsp / d_idxp then hold the distinct records, d_shtab the per-batch table
+  DeviceArray<uint32_t> d_shtab;
+  bool shared_records = false;
+  size_t record_bytes = 0;  // bytes of d_bdofsp + d_idxp + d_shtab
   DeviceArray<uint32_t> d_hnrec;  // apply_planes3<HN>: per-batch records of the hanging-node line operations
   DeviceArray<uint32_t> d_hn_slot;  // ... and per plane batch the index of its record (0xffffffff: none)
   DeviceArray<void> d_coefp;
@@ -89,6 +93,11 @@ struct mfgpu_handle {
   std::vector<uint32_t> seg_end;
   std::vector<DeviceArray<uint32_t>> d_p2arr, d_p2tiles;
   std::vector<uint32_t> n_p2tiles;
+  // ... or, for the last group of a one-segment plan without priority dofs, the shared form (Plan::sh_p2rec / sh_p2tab):
+  // one workgroup per owner batch (reduce_owner_batches); the group's class arrays then hold only the dofs without a
+  // partial sum and the orphans
+  DeviceArray<uint32_t> d_p2rec, d_p2tab;
+  bool p2_shared = false, p2_reverse = false, no_shared_records = false;
   Stream side;
   std::vector<Event> ev_seg;  // [s]: segment s done (recorded on the caller's stream)
   Event ev_side;              // the side stream's pass-2 launches of this vmult done
@@ -203,6 +212,8 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
     prio[priority[i]] = 1;
   }
   const size_t ng = 1 + h->seg_end.size();
+  // the shared form serves the one group that matters: everything, on a one-segment plan without priority dofs
+  const bool shared = P.sh_p2_use && !h->no_shared_records && n_priority == 0 && ng == 2;
   std::vector<std::vector<uint32_t>> sd(ng), so(ng, std::vector<uint32_t>(1, 0u)), si(ng);
   auto add = [&](uint32_t dof, const uint32_t *slots, uint32_t k, size_t seg) {
     const size_t g = prio[dof & 0x7fffffffu] ? 0 : 1 + seg;
@@ -213,6 +224,7 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
   for (size_t i = 0; i < P.sdofs.size(); ++i) {
     // the slots of a dof are listed in ascending batch order: the last one belongs to its last toucher
     size_t seg = 0;
+    if (shared && P.s_off[i + 1] > P.s_off[i]) continue;  // (in its owner batch's record)
     if (P.s_off[i + 1] > P.s_off[i]) {
       const uint32_t slot = P.s_idx[P.s_off[i + 1] - 1];
       const uint32_t batch = (uint32_t)(std::upper_bound(P.halo_off.begin(), P.halo_off.end(), slot) - P.halo_off.begin()) - 1;
@@ -227,6 +239,13 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
   // as they were.  (These arrays are not counted in device_bytes.)
   std::vector<DeviceArray<uint32_t>> d_arr(ng), d_tiles(ng);
   std::vector<uint32_t> n_tiles(ng, 0u);
+  const bool reverse = (size_t)P.halo_off.back() * esize(h->number_type) <= ((size_t)256 << 20);  // (see below)
+  DeviceArray<uint32_t> d_rec, d_tab;
+  if (shared) {
+    int rc;
+    if ((rc = d_rec.upload(P.sh_p2rec.data(), P.sh_p2rec.size()))) return rc;
+    if ((rc = d_tab.upload(P.sh_p2tab.data(), P.sh_p2tab.size()))) return rc;
+  }
   for (size_t g = 0; g < ng; ++g) {
     std::vector<uint32_t> arr, tiles;
     build_pass2_classes(sd[g], so[g], si[g], arr, tiles);
@@ -236,7 +255,7 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
     // the partial sums the cell loop wrote last are read first, from cache: pass 2 42.4 -> 41.3 us on C2, 38.9 -> 35.3
     // on C5, -1 .. -3 % per vmult up to 38 M dofs; beyond (n = 96: 57 M dofs, 340 MB of partial sums) it is slower, at
     // 81 M dofs by 10 % (profiles/r03_notes.md section 13)
-    if ((size_t)P.halo_off.back() * esize(h->number_type) <= ((size_t)256 << 20)) {
+    if (reverse) {
       const size_t nt = tiles.size() / 4;
       for (size_t a = 0, b = nt ? nt - 1 : 0; a < b; ++a, --b)
         for (int w = 0; w < 4; ++w) std::swap(tiles[4 * a + w], tiles[4 * b + w]);
@@ -248,6 +267,10 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
   h->d_p2arr = std::move(d_arr);
   h->d_p2tiles = std::move(d_tiles);
   h->n_p2tiles = std::move(n_tiles);
+  h->d_p2rec = std::move(d_rec);
+  h->d_p2tab = std::move(d_tab);
+  h->p2_shared = shared;
+  h->p2_reverse = reverse;
   return 0;
 }
 
@@ -319,8 +342,15 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
       if ((rc = up(h->d_hnrec, P.pr_hn.data(), P.pr_hn.size()))) return rc;
       if ((rc = up(h->d_hn_slot, P.pr_hn_slot.data(), P.pr_hn_slot.size()))) return rc;
     }
-    if ((rc = up(h->d_bdofsp, P.pr_dofs.data(), P.pr_dofs.size()))) return rc;
-    if ((rc = up(h->d_idxp, P.pr_idx.data(), P.pr_idx.size()))) return rc;
+    // The shared form where the plan chose it (by bytes) and the kernel family has the instantiation: apply_planes3.
+    // The expanded arrays are then not uploaded at all.
+    h->shared_records = P.sh_use && h->planes == PlaneKernel::planes3 && !(d.flags & MFGPU_NO_SHARED_RECORDS);
+    const std::vector<uint32_t> &rd = h->shared_records ? P.sh_dofs : P.pr_dofs;
+    const std::vector<uint32_t> &rx = h->shared_records ? P.sh_idx : P.pr_idx;
+    if ((rc = up(h->d_bdofsp, rd.data(), rd.size()))) return rc;
+    if ((rc = up(h->d_idxp, rx.data(), rx.size()))) return rc;
+    if (h->shared_records && (rc = up(h->d_shtab, P.sh_batch.data(), P.sh_batch.size()))) return rc;
+    h->record_bytes = h->d_bdofsp.bytes() + h->d_idxp.bytes() + h->d_shtab.bytes();
   }
   if ((rc = up(h->d_orphans, P.orphans.data(), P.orphans.size()))) return rc;
   if (h->twopass) {
@@ -457,6 +487,10 @@ int create_typed(mfgpu_handle *h, const mfgpu_desc &d) {
 // to back; mfgpu_vmult_dist_begin starts the exchange of the slab's interface planes between the last two.
 template <typename T>
 int launch_pass2_group(mfgpu_handle *h, size_t group, void *dst, const void *src, hipStream_t st, int add) {
+  if (h->p2_shared && group == 1)  // owner batches in reverse execution order while the halo buffer fits the cache
+    HIP_TRY(reduce_owner_batches_launch<T>((T *)dst, (const T *)src, h->d_halo.as<const T>(), h->d_p2rec.get(),
+                                           h->d_p2tab.get(), (uint32_t)(h->plan.batch_cell_off.size() - 1),
+                                           (uint32_t)p_hs(h->plan.n) * 64u, h->p2_reverse ? 1 : 0, add, st));
   HIP_TRY(reduce_classes_launch<T>((T *)dst, (const T *)src, h->d_halo.as<const T>(), h->d_p2arr[group].get(),
                                    h->d_p2tiles[group].get(), h->n_p2tiles[group], add, st));
   return 0;
@@ -514,6 +548,7 @@ ApplyArgs<T> make_args(mfgpu_handle *h, void *dst, const void *src, int add) {
   a.perm = h->d_perm.get();
   a.bdofsp = h->d_bdofsp.get();
   a.idxp = h->d_idxp.get();
+  a.shtab = h->shared_records ? h->d_shtab.get() : nullptr;
   a.hnrec = h->d_hnrec.get();
   a.hn_slot = h->d_hn_slot.get();
   a.coefp = h->d_coefp.as<const T>();
@@ -764,6 +799,7 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
   h->number_type = d.number_type;
   h->hn = hn;
   h->twopass = !(d.flags & MFGPU_COLORED_SCATTER);
+  h->no_shared_records = (d.flags & MFGPU_NO_SHARED_RECORDS) != 0;
   const int nn = h->n * h->n;
   std::vector<double> sv(nn), sg(nn);
   for (int i = 0; i < nn; ++i) {
@@ -845,6 +881,18 @@ int mfgpu_plan_stats(const mfgpu_handle *h, uint64_t s[8]) {
     s[6] = P.sdofs.size();
     s[7] = P.halo_off.back();
   }
+  return 0;
+}
+
+int mfgpu_record_stats(const mfgpu_handle *h, uint64_t s[4]) {
+  if (!h || !s) return MFGPU_EINVAL;
+  const Plan &P = h->plan;
+  const size_t n = (size_t)P.n, nb = (size_t)p_kgu((int)n) * 64, nx = ((n * n + 1) / 2) * (p_cells_per_wave((int)n) * n);
+  const bool planes = h->planes != PlaneKernel::none;
+  s[0] = (h->shared_records ? 1 : 0) | (h->p2_shared ? 2 : 0);
+  s[1] = planes ? P.sh_dofs.size() / nb : 0;
+  s[2] = planes ? P.sh_idx.size() / nx : 0;
+  s[3] = h->record_bytes;
   return 0;
 }
 

@@ -103,6 +103,24 @@ struct Plan {
   // plane kernels (build_plane_records): fixed-size per-batch records -- dof lists, index runs, and for the batches
   // of masked cells the hanging-node records; pr_hn_slot[b] = index of batch b's record in pr_hn, or 0xffffffff
   std::vector<uint32_t> pr_dofs, pr_idx, pr_hn, pr_hn_slot;
+  // SHARED form of pr_dofs / pr_idx (share_plane_records): the same records, each distinct one stored once.
+  // sh_dofs: the distinct dof lists with the batch's smallest dof id subtracted from every entry (bit 31 kept);
+  // sh_idx: the distinct index-run records; sh_batch: per plane batch kShBatchWords words {that smallest dof id,
+  // number of its record in sh_dofs, number of its record in sh_idx, 0}.  Found by comparing contents: a numbering
+  // that repeats from batch to batch gives a handful of records, any other one record per batch.  sh_use: the shared
+  // form is clearly smaller than the expanded one (kShareMaxFraction) and the plan has no hanging-node records.
+  std::vector<uint32_t> sh_dofs, sh_idx, sh_batch;
+  bool sh_use = false;
+  // SHARED form of pass 2 (share_pass2_records): the pass-2 dofs with at least one partial sum, grouped by the batch of
+  // their FIRST partial sum (the owner batch).  sh_p2tab: per batch {its smallest dof id, word offset of its record in
+  // sh_p2rec}; a record (distinct ones stored once) is kP2Header words {entries, entries padded to 64, largest k,
+  // word offsets of the slot rows 0 .. kP2MaxK-1}, then rows padded to 64 words: the dofs (id minus the batch's smallest
+  // dof id, bit 31 kept; padding 0xffffffff) sorted by k descending (stable: otherwise in today's order), their k, and
+  // row t for the entries with k > t: toucher batch minus owner batch << kP2SlotBits | halo slot minus the toucher's
+  // first.  sh_p2_use: every batch is a plane batch (fixed halo stride), the packed words fit, and the shared form
+  // is clearly smaller (kShareMaxFraction).  Dofs listed without a partial sum and the orphans stay with reduce_classes.
+  std::vector<uint32_t> sh_p2rec, sh_p2tab;
+  bool sh_p2_use = false;
   uint64_t n_first = 0, n_add = 0;
 };
 
@@ -151,6 +169,15 @@ enum class PlaneKernel : uint8_t { none, planes3, planes4 };
 enum class BatchKernel : uint8_t { none, batches, x, g, g2 };
 int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk, Plan &plan);
 int build_plane_records(Plan &plan, const uint32_t *constraint_mask);
+// The shared form of the plane records (Plan::sh_*), derived from pr_dofs / pr_idx at the end of build_plane_records.
+// It is used when its bytes (distinct records + per-batch table) are at most kShareMaxFraction of the expanded
+// arrays' bytes: below that the records fit the L2 next to the streams; a plan that shares little keeps the fixed
+// strides and read-once hints of the expanded form.
+constexpr int kShBatchWords = 4;
+constexpr double kShareMaxFraction = 0.5;
+void share_plane_records(Plan &plan);
+constexpr int kP2Header = 16, kP2MaxK = 12, kP2SlotBits = 12;
+void share_pass2_records(Plan &plan);
 
 // Derive the kernel's 1D tables from the reference-layout tables T[dof*n+q]:
 //   S[i*n+q]  = shape_values (interpolation nodal -> quadrature points)

@@ -41,6 +41,10 @@ struct ApplyArgs {
   int add;          // vmult_add semantics
   unsigned long long *stamps;  // diagnostic build only (MFGPU_STAMPS), else nullptr
   int dbg;                     // diagnostic build only: ablation bits (1 cells, 2 gather, 4 scatter, 8 prefetch)
+  // plane kernels, SHARED form of the index records (Plan::sh_*; nullptr: the expanded form): per plane batch
+  // kShBatchWords words {dof base, dof-list record, index-run record, 0}; bdofsp / idxp then hold every DISTINCT
+  // record once, the dof lists relative to the batch's dof base
+  const uint32_t *shtab = nullptr;
 };
 
 // 1D tables, passed by value as kernel arguments (=> scalar registers).
@@ -102,6 +106,10 @@ void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<u
 template <typename T>
 hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint32_t *arr, const uint32_t *tiles,
                                  uint32_t n_tiles, int add, hipStream_t st);
+// pass 2, shared form: one workgroup per owner batch (Plan::sh_p2rec / sh_p2tab); reverse: last batch first
+template <typename T>
+hipError_t reduce_owner_batches_launch(T *dst, const T *src, const T *halo, const uint32_t *rec, const uint32_t *tab,
+                                       uint32_t n_batches, uint32_t hstride, int reverse, int add, hipStream_t st);
 // setup relayout of the folded coefficient for the plane kernels (mfgpu_kernels_p.hip)
 template <typename T>
 hipError_t relayout_coef_launch(T *out, const T *in, const uint32_t *cell_batch, const uint32_t *cell_pos,

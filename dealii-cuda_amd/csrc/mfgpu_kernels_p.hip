@@ -43,7 +43,16 @@ namespace mfgpu {
 // transposed passes in reverse order (the exact adjoint) after stage C, each line as a plain n x n mat-vec with the
 // weight matrix W (a line of a cell whose type bit is clear is listed in reverse, which mirrors W).  The cell stages
 // themselves do not know about hanging nodes.
-template <int n, typename T, bool ADD, bool HN>
+//
+// SH: the SHARED form of the dof lists and index runs (Plan::sh_*).  On a numbering that repeats from batch to batch
+// the expanded records are a handful of distinct ones repeated (27 on a cube the box batches tile); the shared form
+// stores each once -- L2-resident, read with ordinary cached loads -- and per batch {dof base, record numbers}
+// (A.shtab): ~100 MB of read-once index stream less per vmult on C2.  The dof base goes into the UNIFORM part of the
+// vector addresses (src / dst advanced by base), so the lanes' 32-bit byte offsets, the test on bit 31 and the halo
+// addressing are what they are in the expanded form, and so are the arithmetic and its order.  A batch's table entry
+// is fetched THREE batches ahead (one before the dof list it addresses) with one coalesced vector load that joins the
+// iteration's other loads under the same vmcnt wait; its words become scalars at the iteration boundary.
+template <int n, typename T, bool ADD, bool HN, bool SH = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   constexpr int n2 = n * n;
@@ -101,26 +110,42 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     return l < bend ? (l >= hole0 ? l + hole_len : l) : x;
   };
   if (b >= hole0) b += hole_len;
+  static_assert(!(SH && HN), "hanging-node batches keep the expanded records");
+  // SH: {dof base, dof-list record, index-run record} of a batch
+  struct Meta {
+    uint32_t base, drec, irec;
+  };
+  auto meta_request = [&](uint32_t bb) -> uint32_t {  // lanes 0 .. 3 hold the batch's four words
+    return A.shtab[(size_t)bb * kShBatchWords + (lane & (kShBatchWords - 1))];
+  };
+  auto meta_of = [&](uint32_t v) -> Meta {
+    return Meta{(uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 1),
+                (uint32_t)__builtin_amdgcn_readlane((int)v, 2)};
+  };
 
   // Per-batch records have FIXED sizes and a fixed structure (mfgpu_api.hip): every address below is a uniform base
   // (scalar arithmetic on the batch index) plus a lane offset plus an immediate; nothing is clamped per batch and
-  // there is no per-batch metadata at all.  Vectors and the halo buffer are addressed base + 32-bit byte offset
+  // there is no per-batch metadata at all (expanded form; SH: one table entry per batch, below).  Vectors and the halo buffer are addressed base + 32-bit byte offset
   // (the plan guarantees n_dofs < 2^29; shifting a dof-list entry left by 3 also drops its flag bit 31).
-  auto load_dofs = [&](uint32_t bb, uint32_t (&g)[KGU]) {
-    const uint32_t *p = A.bdofsp + (size_t)bb * (KGU * 64) + lane;
+  // (SH: `rec` is the record's number in the table of distinct records, `base` the batch's dof base; the records
+  // are shared by many batches and must stay in L2: no read-once hint)
+  auto load_dofs = [&](uint32_t rec, uint32_t (&g)[KGU]) {
+    const uint32_t *p = A.bdofsp + (size_t)rec * (KGU * 64) + lane;
 #pragma unroll
-    for (int j = 0; j < KGU; ++j) g[j] = nt_load(p + j * 64);
+    for (int j = 0; j < KGU; ++j) g[j] = SH ? p[j * 64] : nt_load(p + j * 64);
   };
-  auto src_at = [&](uint32_t g) -> T {
-    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(A.src) + (uint32_t)(g * (uint32_t)sizeof(T)));
+  auto src_at = [&](uint32_t base, uint32_t g) -> T {
+    const T *const sp = SH ? A.src + base : A.src;
+    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(sp) + (uint32_t)(g * (uint32_t)sizeof(T)));
   };
-  auto dst_at = [&](uint32_t g) -> T * {
-    return reinterpret_cast<T *>(reinterpret_cast<char *>(A.dst) + (uint32_t)(g * (uint32_t)sizeof(T)));
+  auto dst_at = [&](uint32_t base, uint32_t g) -> T * {
+    T *const dp = SH ? A.dst + base : A.dst;
+    return reinterpret_cast<T *>(reinterpret_cast<char *>(dp) + (uint32_t)(g * (uint32_t)sizeof(T)));
   };
-  auto load_ix = [&](uint32_t bb, uint32_t (&ix)[NIW]) {
-    const uint32_t *p = A.idxp + (size_t)bb * (NIW * NT) + tk;
+  auto load_ix = [&](uint32_t rec, uint32_t (&ix)[NIW]) {
+    const uint32_t *p = A.idxp + (size_t)rec * (NIW * NT) + tk;
 #pragma unroll
-    for (int w = 0; w < NIW; ++w) ix[w] = nt_load(p + w * NT);
+    for (int w = 0; w < NIW; ++w) ix[w] = SH ? p[w * NT] : nt_load(p + w * NT);
   };
   // gathered values -> LDS (read_dof_values, fee_gpu.cuh:323-331, once per batch dof).  bdofs bit 31 = constrained
   // row: reads as 0 (constraint_handler_gpu.cu:258-259).  All KGU * 64 slots are written (the padding of the dof
@@ -147,9 +172,9 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   // and go to dst (padding lanes store the 0 of their untouched accumulator slot, or old + 0, to a pass-2 dof of the
   // batch, which pass 2 rewrites); the other HS slots are partial sums for pass 2 and go to the batch's HS * 64 halo
   // slots (padding lanes: unused halo slots).
-  auto scatter_slot = [&](int j, uint32_t bb, uint32_t g, T r, T oldv) {
+  auto scatter_slot = [&](int j, uint32_t bb, uint32_t base, uint32_t g, T r, T oldv) {
     if (j < JI) {
-      *dst_at(g) = ADD ? oldv + r : r;
+      *dst_at(base, g) = ADD ? oldv + r : r;
     } else {
       T *const hp = A.halo + (size_t)bb * (HS * 64) + lane;
       hp[(j - JI) * 64] = r;  // (constrained dofs: value ignored by pass 2)
@@ -174,9 +199,19 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   };
   T Cc[n2];
   T SVn[KGU], R[KGU], old[KGU];
-  load_dofs(b, Gc);
-  load_dofs(b1, Gn);
-  load_ix(b, IXc);
+  // SH: the table entries of the previous batch (deferred scatter), this one, the next two; Mv: the third ahead, in
+  // flight.  Expanded form: all zero and unused.
+  Meta Mp{0u, 0u, 0u}, Mc = Mp, M1 = Mp, M2 = Mp;
+  uint32_t Mv = 0u;
+  if (SH) {
+    Mc = meta_of(meta_request(b));
+    M1 = meta_of(meta_request(b1));
+    M2 = meta_of(meta_request(b2));
+    Mp = Mc;
+  }
+  load_dofs(SH ? Mc.drec : b, Gc);
+  load_dofs(SH ? M1.drec : b1, Gn);
+  load_ix(SH ? Mc.irec : b, IXc);
   if (HN) load_hn(b, Hc);
   // the idle lanes add into the batch array's last slot, which is never a dof
   constexpr uint32_t kDummyIx = 8u * (uint32_t)(KGU * 64 - 1) * 0x10001u;
@@ -189,7 +224,7 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   }
 #pragma unroll
   for (int j = 0; j < KGU; ++j) {
-    SVn[j] = src_at(Gc[j]);
+    SVn[j] = src_at(Mc.base, Gc[j]);
     Gp[j] = Gc[j];
     R[j] = T(0);
     old[j] = T(0);
@@ -269,12 +304,13 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     RSTAMP(8);
     WGSTAMP(10);
     // ---- coalesced loads of the coming batches: dof list two ahead, index runs one ahead
-    load_dofs(b2, Gnn);
-    load_ix(b1, IXn);
+    load_dofs(SH ? M2.drec : b2, Gnn);
+    load_ix(SH ? M1.irec : b1, IXn);
+    if (SH) Mv = meta_request(next_of(b2));
     if (HN) load_hn(b1, Hn);
     if (ADD) {
 #pragma unroll
-      for (int j = 0; j < JI; ++j) old[j] = *dst_at(Gp[j]);
+      for (int j = 0; j < JI; ++j) old[j] = *dst_at(Mp.base, Gp[j]);
     }
     STAMP(1);
     // The scattered accesses (gather of the next batch's source values, stores of the PREVIOUS batch's results) and
@@ -288,10 +324,10 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
       MFGPU_PIN_VMEM();
 #pragma unroll
       for (int j = (KGU * s) / (5 * n); j < (KGU * (s + 1)) / (5 * n); ++j)
-        scatter_slot(j, bp, Gp[j], R[j], old[j]);
+        scatter_slot(j, bp, Mp.base, Gp[j], R[j], old[j]);
 #pragma unroll
       for (int j = (KGU * s) / (5 * n); j < (KGU * (s + 1)) / (5 * n); ++j)
-        SVn[j] = src_at(Gn[j]);
+        SVn[j] = src_at(M1.base, Gn[j]);
       MFGPU_PIN_VMEM();
     };
     const T *const cnext = A.coefp + (size_t)b1 * (n2 * NT) + tk;
@@ -490,6 +526,7 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     stage_src(Gn, SVn);  // (after the last batch: its own values again, unused)
     STAMP(6);
     bp = b;
+    if (SH) Mp = Mc;
 #pragma unroll
     for (int j = 0; j < KGU; ++j) Gp[j] = Gc[j];
     STAMP(7);
@@ -499,6 +536,11 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     b = b1;
     b1 = b2;
     b2 = next_of(b2);
+    if (SH) {  // (Mv arrived with the gather: the wait above)
+      Mc = M1;
+      M1 = M2;
+      M2 = meta_of(Mv);
+    }
 #pragma unroll
     for (int j = 0; j < KGU; ++j) {
       Gc[j] = Gn[j];
@@ -514,10 +556,10 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   // the last batch's results
   if (ADD) {
 #pragma unroll
-    for (int j = 0; j < JI; ++j) old[j] = *dst_at(Gp[j]);
+    for (int j = 0; j < JI; ++j) old[j] = *dst_at(Mp.base, Gp[j]);
   }
 #pragma unroll
-  for (int j = 0; j < KGU; ++j) scatter_slot(j, bp, Gp[j], R[j], old[j]);
+  for (int j = 0; j < KGU; ++j) scatter_slot(j, bp, Mp.base, Gp[j], R[j], old[j]);
 }
 
 template <int n, typename T>
@@ -531,7 +573,14 @@ static hipError_t p_configure_t(bool hn, size_t *lds, int *blocks) {
   *lds = p_lds_bytes<n, T>(hn);
   const void *f0 = hn ? (const void *)apply_planes3<n, T, false, true> : (const void *)apply_planes3<n, T, false, false>;
   const void *f1 = hn ? (const void *)apply_planes3<n, T, true, true> : (const void *)apply_planes3<n, T, true, false>;
-  const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+  hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+  if (e == hipSuccess && !hn) {  // the shared-record instantiations (same LDS; same occupancy, checked at build time)
+    e = hipFuncSetAttribute((const void *)apply_planes3<n, T, true, false, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void *)apply_planes3<n, T, false, false, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
+  }
   return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
 }
 
@@ -545,6 +594,11 @@ static hipError_t p_launch_t(const ApplyArgs<T> &a, const double *S, const doubl
       hipLaunchKernelGGL((apply_planes3<n, T, true, true>), dim3(grid), dim3(64), lds, st, a, tab);
     else
       hipLaunchKernelGGL((apply_planes3<n, T, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
+  } else if (a.shtab) {  // shared form of the index records (chosen per plan: Plan::sh_use)
+    if (a.add)
+      hipLaunchKernelGGL((apply_planes3<n, T, true, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
+    else
+      hipLaunchKernelGGL((apply_planes3<n, T, false, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
   } else {
     if (a.add)
       hipLaunchKernelGGL((apply_planes3<n, T, true, false>), dim3(grid), dim3(64), lds, st, a, tab);

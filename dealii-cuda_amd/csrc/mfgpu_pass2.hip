@@ -87,6 +87,74 @@ reduce_classes(T *__restrict__ dst, const T *__restrict__ src, const T *__restri
   }
 }
 
+// ---- Shared form (Plan::sh_p2rec / sh_p2tab, mfgpu_plan.cpp share_pass2_records): one workgroup per OWNER batch (the
+// batch of a dof's first partial sum).  Where the numbering repeats from batch to batch the per-dof index words of
+// reduce_classes (42 MB read once per vmult on the 54^3 mesh at p = 4) are 27 distinct records: the record is read from
+// L2, and only the partial sums, src at identity rows and dst move through the fabric.  A record lists the batch's dofs
+// sorted by k descending, so a wave's largest k is its first lane's; the lanes sum their own k <= that many partial sums
+// in ascending toucher order -- the order, and hence the bits, of reduce_classes.
+template <typename T, int K>
+__device__ __forceinline__ void reduce_owned(T *__restrict__ dst, const T *__restrict__ src,
+                                             const T *__restrict__ halo, const uint32_t *__restrict__ r, uint32_t e,
+                                             uint32_t d, uint32_t kk, uint32_t kw, uint32_t hslot0, uint32_t hstride,
+                                             int add) {
+  // K > 0: compile-time bound of the wave's largest k; K == 0: run-time bound kw
+  const T *const hb = halo + hslot0;  // the owner batch's first halo slot
+  auto partial = [&](uint32_t w) -> T {
+    return hb[(w >> kP2SlotBits) * hstride + (w & ((1u << kP2SlotBits) - 1u))];
+  };
+  constexpr int KU = K > 0 ? K : 1;
+  uint32_t w[KU];
+#pragma unroll
+  for (int t = 0; t < KU; ++t) w[t] = (uint32_t)t < kk ? r[r[3 + t] + e] : 0u;
+  if (d == 0xffffffffu) return;  // padding of the record's last wave
+  T v;
+  if (d >> 31) {
+    v = src[d & 0x7fffffffu];
+  } else {
+    T q[KU];
+#pragma unroll
+    for (int t = 0; t < KU; ++t) q[t] = (uint32_t)t < kk ? partial(w[t]) : T(0);
+    v = q[0];
+#pragma unroll
+    for (int t = 1; t < KU; ++t)
+      if ((uint32_t)t < kk) v += q[t];
+    if (K == 0)
+      for (uint32_t t = 1; t < kw; ++t)
+        if (t < kk) v += partial(r[r[3 + t] + e]);
+  }
+  T *const out = dst + (d & 0x7fffffffu);
+  *out = add ? *out + v : v;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+reduce_owner_batches(T *__restrict__ dst, const T *__restrict__ src, const T *__restrict__ halo,
+                     const uint32_t *__restrict__ rec, const uint2 *__restrict__ tab, uint32_t n_batches,
+                     uint32_t hstride, int reverse, int add) {
+  const uint32_t ob = reverse ? n_batches - 1u - blockIdx.x : blockIdx.x;
+  const uint2 t = tab[ob];  // {dof base, word offset of the batch's record}
+  const uint32_t *const r = rec + t.y;
+  const uint32_t e0 = r[1];  // entries, padded to whole waves
+  dst += t.x;  // the record's dof ids are relative to the batch's dof base
+  src += t.x;
+  for (uint32_t e = threadIdx.x; e < e0; e += 256u) {  // (wave-uniform trip count)
+    const uint32_t d = r[kP2Header + e], kk = r[kP2Header + e0 + e];
+    const uint32_t kw = (uint32_t)__builtin_amdgcn_readfirstlane((int)kk);  // the wave's largest k
+    const uint32_t h0 = ob * hstride;
+    switch (kw) {  // wave-uniform
+      case 0: break;
+      case 1: reduce_owned<T, 1>(dst, src, halo, r, e, d, kk, kw, h0, hstride, add); break;
+      case 2: reduce_owned<T, 2>(dst, src, halo, r, e, d, kk, kw, h0, hstride, add); break;
+      case 3: reduce_owned<T, 3>(dst, src, halo, r, e, d, kk, kw, h0, hstride, add); break;
+      case 4: reduce_owned<T, 4>(dst, src, halo, r, e, d, kk, kw, h0, hstride, add); break;
+      case 5: case 6: case 7:
+      case 8: reduce_owned<T, 8>(dst, src, halo, r, e, d, kk, kw, h0, hstride, add); break;
+      default: reduce_owned<T, 0>(dst, src, halo, r, e, d, kk, kw, h0, hstride, add); break;
+    }
+  }
+}
+
 }  // namespace
 
 // Host side: (sdofs, s_off, s_idx) of the plan -> class arrays.  `arr` = for every class [dofs | slots_0 | ... |
@@ -132,6 +200,18 @@ hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint
                      reinterpret_cast<const uint4 *>(tiles), add);
   return hipGetLastError();
 }
+template <typename T>
+hipError_t reduce_owner_batches_launch(T *dst, const T *src, const T *halo, const uint32_t *rec, const uint32_t *tab,
+                                       uint32_t n_batches, uint32_t hstride, int reverse, int add, hipStream_t st) {
+  if (n_batches == 0) return hipSuccess;
+  hipLaunchKernelGGL(reduce_owner_batches<T>, dim3(n_batches), dim3(256), 0, st, dst, src, halo, rec,
+                     reinterpret_cast<const uint2 *>(tab), n_batches, hstride, reverse, add);
+  return hipGetLastError();
+}
+template hipError_t reduce_owner_batches_launch<double>(double *, const double *, const double *, const uint32_t *,
+                                                        const uint32_t *, uint32_t, uint32_t, int, int, hipStream_t);
+template hipError_t reduce_owner_batches_launch<float>(float *, const float *, const float *, const uint32_t *,
+                                                       const uint32_t *, uint32_t, uint32_t, int, int, hipStream_t);
 template hipError_t reduce_classes_launch<double>(double *, const double *, const double *, const uint32_t *,
                                                   const uint32_t *, uint32_t, int, hipStream_t);
 template hipError_t reduce_classes_launch<float>(float *, const float *, const float *, const uint32_t *,

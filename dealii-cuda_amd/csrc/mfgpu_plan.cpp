@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstring>
 #include <numeric>
+#include <unordered_map>
 
 #include "mfgpu_internal.h"
 
@@ -793,7 +794,123 @@ int build_plane_records(Plan &P, const uint32_t *constraint_mask) {
       }
     }
   }
+  share_plane_records(P);
+  share_pass2_records(P);
   return 0;
+}
+
+namespace {
+// FNV-1a over 32-bit words
+uint64_t hash_words(const uint32_t *w, size_t n) {
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ w[i]) * 1099511628211ull;
+  return h;
+}
+
+// Appends rec[0 .. len) to table unless an equal record is there already (hash, then compare); returns its number.
+uint32_t intern_record(std::vector<uint32_t> &table, std::unordered_multimap<uint64_t, uint32_t> &seen,
+                       const uint32_t *rec, size_t len) {
+  const uint64_t h = hash_words(rec, len);
+  const auto range = seen.equal_range(h);
+  for (auto it = range.first; it != range.second; ++it)
+    if (!std::memcmp(table.data() + (size_t)it->second * len, rec, len * sizeof(uint32_t))) return it->second;
+  const uint32_t id = (uint32_t)(table.size() / len);
+  table.insert(table.end(), rec, rec + len);
+  seen.emplace(h, id);
+  return id;
+}
+}  // namespace
+
+void share_plane_records(Plan &P) {
+  const int n = P.n, NT = p_cells_per_wave(n) * n, NIW = (n * n + 1) / 2;
+  const size_t NB = (size_t)p_kgu(n) * 64, NX = (size_t)NIW * NT, nbat = P.n_plane_batches;
+  P.sh_dofs.clear();
+  P.sh_idx.clear();
+  P.sh_batch.assign(nbat * kShBatchWords, 0u);
+  std::unordered_multimap<uint64_t, uint32_t> seen_d, seen_x;
+  std::vector<uint32_t> rel(NB);
+  for (size_t b = 0; b < nbat; ++b) {
+    const uint32_t *g = P.pr_dofs.data() + b * NB;
+    uint32_t base = 0x7fffffffu;
+    for (size_t t = 0; t < NB; ++t) base = std::min(base, g[t] & 0x7fffffffu);
+    for (size_t t = 0; t < NB; ++t) rel[t] = g[t] - base;  // (bit 31 survives: the low 31 bits are >= base)
+    uint32_t *e = P.sh_batch.data() + b * kShBatchWords;
+    e[0] = base;
+    e[1] = intern_record(P.sh_dofs, seen_d, rel.data(), NB);
+    e[2] = intern_record(P.sh_idx, seen_x, P.pr_idx.data() + b * NX, NX);
+  }
+  const size_t shared = P.sh_dofs.size() + P.sh_idx.size() + P.sh_batch.size();
+  const size_t expanded = P.pr_dofs.size() + P.pr_idx.size();
+  P.sh_use = nbat > 0 && P.pr_hn.empty() && (double)shared <= kShareMaxFraction * (double)expanded;
+}
+
+void share_pass2_records(Plan &P) {
+  P.sh_p2rec.clear();
+  P.sh_p2tab.clear();
+  P.sh_p2_use = false;
+  const size_t nb = P.batch_cell_off.size() - 1;
+  const uint32_t hs = (uint32_t)p_hs(P.n) * 64u;
+  if (nb == 0 || P.n_plane_batches != nb || P.halo_off.size() != nb + 1 || hs > (1u << kP2SlotBits)) return;
+  for (size_t b = 0; b <= nb; ++b)
+    if (P.halo_off[b] != (uint64_t)b * hs) return;  // (plane plans: every batch owns hs halo slots)
+  std::vector<std::vector<uint32_t>> owned(nb);
+  size_t expanded = 0;
+  for (size_t i = 0; i < P.sdofs.size(); ++i) {
+    const uint32_t k = P.s_off[i + 1] - P.s_off[i];
+    expanded += 1 + (k ? k : 1);
+    if (k == 0) continue;  // (stays with reduce_classes)
+    if (k > (uint32_t)kP2MaxK) return;
+    const uint32_t owner = P.s_idx[P.s_off[i]] / hs;
+    for (uint32_t t = 0; t < k; ++t) {  // ascending toucher order, batch deltas that fit the packed word
+      const uint32_t tb = P.s_idx[P.s_off[i] + t] / hs;
+      if (tb >= nb || tb < owner || tb - owner >= (1u << (32 - kP2SlotBits))) return;
+    }
+    owned[owner].push_back((uint32_t)i);
+  }
+  P.sh_p2tab.assign(2 * nb, 0u);
+  std::unordered_multimap<uint64_t, std::pair<uint32_t, uint32_t>> seen;  // hash -> (offset, length)
+  std::vector<uint32_t> rec;
+  for (size_t b = 0; b < nb; ++b) {
+    std::vector<uint32_t> &m = owned[b];
+    auto k_of = [&](uint32_t i) { return P.s_off[i + 1] - P.s_off[i]; };
+    std::stable_sort(m.begin(), m.end(), [&](uint32_t x, uint32_t y) { return k_of(x) > k_of(y); });
+    const uint32_t base = P.sh_batch[b * kShBatchWords], ne = (uint32_t)m.size(), kmax = ne ? k_of(m[0]) : 0u;
+    auto pad = [](uint32_t x) { return (x + 63u) & ~63u; };
+    const uint32_t e0 = pad(ne);
+    rec.assign(kP2Header, 0u);
+    rec[0] = ne;
+    rec[1] = e0;
+    rec[2] = kmax;
+    rec.resize(kP2Header + 2 * (size_t)e0, 0u);
+    for (uint32_t e = 0; e < e0; ++e) rec[kP2Header + e] = e < ne ? P.sdofs[m[e]] - base : 0xffffffffu;
+    for (uint32_t e = 0; e < ne; ++e) rec[kP2Header + e0 + e] = k_of(m[e]);
+    for (uint32_t t = 0; t < kmax; ++t) {
+      uint32_t cnt = 0;  // (sorted by k descending: the entries with k > t are a prefix)
+      while (cnt < ne && k_of(m[cnt]) > t) ++cnt;
+      rec[3 + t] = (uint32_t)rec.size();
+      rec.resize(rec.size() + pad(cnt), 0u);
+      for (uint32_t e = 0; e < cnt; ++e) {
+        const uint32_t slot = P.s_idx[P.s_off[m[e]] + t], tb = slot / hs;
+        rec[rec[3 + t] + e] = ((tb - (uint32_t)b) << kP2SlotBits) | (slot - tb * hs);
+      }
+    }
+    const uint64_t h = hash_words(rec.data(), rec.size());
+    uint32_t off = 0xffffffffu;
+    const auto range = seen.equal_range(h);
+    for (auto it = range.first; it != range.second && off == 0xffffffffu; ++it)
+      if (it->second.second == rec.size() &&
+          !std::memcmp(P.sh_p2rec.data() + it->second.first, rec.data(), rec.size() * sizeof(uint32_t)))
+        off = it->second.first;
+    if (off == 0xffffffffu) {
+      off = (uint32_t)P.sh_p2rec.size();
+      P.sh_p2rec.insert(P.sh_p2rec.end(), rec.begin(), rec.end());
+      seen.emplace(h, std::make_pair(off, (uint32_t)rec.size()));
+    }
+    P.sh_p2tab[2 * b] = base;
+    P.sh_p2tab[2 * b + 1] = off;
+  }
+  const size_t shared = P.sh_p2rec.size() + P.sh_p2tab.size();
+  P.sh_p2_use = (double)shared <= kShareMaxFraction * (double)expanded;
 }
 
 int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk, Plan &plan) {
@@ -947,10 +1064,19 @@ int64_t mfgpu_plan_array_u32(const mfgpu_plan *p, int what, const uint32_t **ptr
     case 14: v = &p->plan.pr_idx; break;
     case 15: v = &p->plan.pr_hn; break;
     case 16: v = &p->plan.pr_hn_slot; break;
+    case 17: v = &p->plan.sh_dofs; break;
+    case 18: v = &p->plan.sh_idx; break;
+    case 19: v = &p->plan.sh_batch; break;
+    case 20: v = &p->plan.sh_p2rec; break;
+    case 21: v = &p->plan.sh_p2tab; break;
     default: mfgpu::set_error("bad array id"); return MFGPU_EINVAL;
   }
   *ptr = v->data();
   return (int64_t)v->size();
+}
+
+int mfgpu_plan_shares_records(const mfgpu_plan *p) {
+  return p ? (p->plan.sh_use ? 1 : 0) | (p->plan.sh_p2_use ? 2 : 0) : 0;
 }
 
 int64_t mfgpu_plan_lmap(const mfgpu_plan *p, const uint16_t **ptr) {

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MFGPU_LIB") or os.path.join(os.path.dirname(_HERE), "
 
 F64, F32 = 0, 1
 OK, EINVAL = 0, -1  # MFGPU_OK, MFGPU_EINVAL
-UNIFORM_J0, HANGING_NODES, COLORED_SCATTER = 1, 2, 1 << 8
+UNIFORM_J0, HANGING_NODES, COLORED_SCATTER, NO_SHARED_RECORDS = 1, 2, 1 << 8, 1 << 9
 KERNEL_AUTO, KERNEL_PENCILS, KERNEL_PENCILS_X, KERNEL_PLANES, KERNEL_PLANES_2W = 0, 1, 2, 3, 4  # Desc.kernel
 
 
@@ -46,6 +46,7 @@ SYMBOLS = [
     "mfgpu_vec_sadd", "mfgpu_vec_equ", "mfgpu_vec_scale", "mfgpu_vec_divide", "mfgpu_vec_invert", "mfgpu_vec_mul",
     "mfgpu_vec_dot", "mfgpu_vec_l2_norm", "mfgpu_vec_add_and_dot", "mfgpu_vec_all_zero", "mfgpu_profile_enable", "mfgpu_profile_read", "mfgpu_profile_read_pass2",
     "mfgpu_plan_create", "mfgpu_plan_destroy", "mfgpu_plan_array_u32", "mfgpu_plan_lmap", "mfgpu_plan_bflags",
+    "mfgpu_plan_shares_records", "mfgpu_record_stats",
     "mfgpu_vec_alloc", "mfgpu_vec_free", "mfgpu_vec_fill", "mfgpu_vec_from_host", "mfgpu_vec_to_host",
     "mfgpu_device_synchronize", "mfgpu_device_memory_info", "mfgpu_mesh_create_uniform", "mfgpu_mesh_create_adaptive", "mfgpu_mesh_create_ball", "mfgpu_mesh_create_from_leaves",
     "mfgpu_mesh_cell_levels", "mfgpu_mesh_destroy",
@@ -113,6 +114,8 @@ def lib():
         L.mfgpu_plan_lmap.restype = C.c_int64
         L.mfgpu_plan_bflags.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.mfgpu_plan_bflags.restype = C.c_int64
+        L.mfgpu_plan_shares_records.argtypes = [C.c_void_p]
+        L.mfgpu_record_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.mfgpu_vec_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_int]
         L.mfgpu_vec_free.argtypes = [C.c_void_p]
         L.mfgpu_vec_fill.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p]
@@ -406,6 +409,15 @@ class Plan:
     pr_idx = property(lambda s: s._u32(14))    # index runs
     pr_hn = property(lambda s: s._u32(15))     # hanging-node records of the batches of masked cells
     pr_hn_slot = property(lambda s: s._u32(16))  # per plane batch: index of its record in pr_hn, or 0xffffffff
+    # shared form of pr_dofs / pr_idx: every distinct record once + per plane batch {dof base, dof record, index record, 0}
+    sh_dofs = property(lambda s: s._u32(17))   # entries relative to the batch's smallest dof id, bit 31 kept
+    sh_idx = property(lambda s: s._u32(18))
+    sh_batch = property(lambda s: s._u32(19).reshape(-1, 4))
+    shares_records = property(lambda s: bool(lib().mfgpu_plan_shares_records(s._h) & 1))  # the form a handle would read
+    # shared form of pass 2: records of the owner batches (layout: mfgpu_internal.h) + per batch {dof base, record offset}
+    sh_p2rec = property(lambda s: s._u32(20))
+    sh_p2tab = property(lambda s: s._u32(21).reshape(-1, 2))
+    shares_pass2_records = property(lambda s: bool(lib().mfgpu_plan_shares_records(s._h) & 2))
 
     @property
     def lmap(self):
@@ -537,7 +549,13 @@ class Operator:
         _check(lib().mfgpu_plan_stats(self._h, s))
         keys = ["n_batches", "n_launches", "batch_dofs", "max_batch_dofs", "max_batch_cells", "n_orphans",
                 "first_touch_or_shared_dofs", "rmw_adds_or_halo_slots"]
-        return dict(zip(keys, [int(v) for v in s]))
+        out = dict(zip(keys, [int(v) for v in s]))
+        r = (C.c_uint64 * 4)()
+        _check(lib().mfgpu_record_stats(self._h, r))
+        out.update(index_records="shared" if r[0] & 1 else "expanded",
+                   pass2_records="shared" if r[0] & 2 else "expanded", distinct_dof_records=int(r[1]),
+                   distinct_index_records=int(r[2]), index_record_bytes=int(r[3]))
+        return out
 
     def kernel_name(self):
         return lib().mfgpu_kernel_name(self._h).decode()

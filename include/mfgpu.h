@@ -56,6 +56,10 @@ extern "C" {
                                          Default is the two-pass mode: one sweep over all batches, batch-
                                          surface partial sums reduced per dof by a second kernel.           */
 
+#define MFGPU_NO_SHARED_RECORDS (1u << 9) /* plane kernels: keep the per-batch index records in their expanded form
+                                         even where the plan would share repeated ones (below, "shared form"): for
+                                         tests and for A/B measurements inside one build                            */
+
 typedef struct mfgpu_handle mfgpu_handle; /* replaces MatrixFreeGpu + coefficient + ConstraintHandlerGpu
                                              inside LaplaceOperatorGpu (laplace_operator_gpu.h:85-95) */
 
@@ -143,6 +147,11 @@ const char *mfgpu_last_error(void);
  * [6]=first-touch stores (coloured) / shared dofs (two-pass) [7]=RMW adds (coloured) / halo slots (two-pass) */
 int mfgpu_plan_stats(const mfgpu_handle *h, uint64_t stats[8]);
 
+/* Index records of the plane kernels: stats[0] bit 0 = the cell loop reads the shared form (repeated per-batch records
+ * stored once; 0: the expanded form), bit 1 = pass 2 does [1]=distinct dof-list records [2]=distinct index-run
+ * records (both counted either way; 0 without plane batches) [3]=bytes of the cell loop's records on the device    */
+int mfgpu_record_stats(const mfgpu_handle *h, uint64_t stats[4]);
+
 /* Name of the cell-loop kernel this operator launches ("apply_batches_x", "apply_batches", ...): the
  * kernel the roofline figures of bench.py and the rocprofv3 summaries under profiles/ refer to.      */
 const char *mfgpu_kernel_name(const mfgpu_handle *h);
@@ -166,8 +175,16 @@ void mfgpu_plan_destroy(mfgpu_plan *p);
  *       plane plans (apply_planes3): 13 dof-list records [n_plane_batches * slots * 64] 14 index-run records
  *       15 hanging-node records of the batches of masked cells (layout: mfgpu_internal.h p_hn_rows)
  *       16 per plane batch the index of its record in 15, or 0xffffffff (a batch of cells without a mask)
+ *       shared form of 13 / 14 (every distinct record once): 17 distinct dof-list records, each entry minus the
+ *       batch's smallest dof id (bit 31 kept) 18 distinct index-run records 19 per plane batch 4 words {smallest dof
+ *       id, record number in 17, record number in 18, 0}
+ *       shared form of pass 2 (8-10 regrouped by the batch of a dof's first partial sum, distinct records once):
+ *       20 records 21 per batch {smallest dof id, word offset of its record in 20} (layout: mfgpu_internal.h Plan)
  * returns element count, *ptr = host pointer valid until mfgpu_plan_destroy                  */
 int64_t mfgpu_plan_array_u32(const mfgpu_plan *p, int what, const uint32_t **ptr);
+/* bit 0: a handle of this plan reads the shared form of the cell loop's records (it is clearly smaller than 13 + 14);
+ * bit 1: the same for pass 2 (20 + 21 against the class arrays built from 8-10)                                    */
+int mfgpu_plan_shares_records(const mfgpu_plan *p);
 int64_t mfgpu_plan_lmap(const mfgpu_plan *p, const uint16_t **ptr);   /* [n_cells*n^dim], plan order */
 int64_t mfgpu_plan_bflags(const mfgpu_plan *p, const uint8_t **ptr);  /* bit0 constrained, bit1 add */
 
