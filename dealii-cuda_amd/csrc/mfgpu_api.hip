@@ -75,6 +75,9 @@ struct mfgpu_handle {
   DeviceArray<uint32_t> d_hn_slot;  // ... and per plane batch the index of its record (0xffffffff: none)
   DeviceArray<void> d_coefp;
   DeviceArray<void> d_coef;
+  // mass term (mfgpu_desc.mass_coefficient; empty without): c * JxW in plan cell order, and for the plane batches
+  // again in d_coefp's layout
+  DeviceArray<void> d_mass, d_massp;
   DeviceArray<uint32_t> d_cmask, d_orphans;
   DeviceArray<void> d_hnw;
   DeviceArray<uint32_t> d_constrained;  // constrained dof list (set_constrained_values)
@@ -379,6 +382,12 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     return rc;
   h->d_coef = std::move(metric);
   acct += h->d_coef.bytes();
+  if (d.mass_coefficient) {
+    DeviceArray<T> mass;
+    if ((rc = fold_mass<T>(mass, d.mass_coefficient, d.JxW, P.cell_order.data(), (uint32_t)ncell, (uint32_t)nd))) return rc;
+    h->d_mass = std::move(mass);
+    acct += h->d_mass.bytes();
+  }
   if (h->planes != PlaneKernel::none) {
     // the folded coefficient again, per batch [row y + n z][task]: the layout of stage B of apply_planes3
     // (d_coef in plan cell order stays: the diagonal kernel reads it)
@@ -398,6 +407,12 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     acct += h->d_coefp.bytes();
     HIP_TRY(relayout_coef_launch<T>(h->d_coefp.as<T>(), h->d_coef.as<const T>(), t_cb.get(), t_cp.get(), ncell_p * nd, n,
                                     nullptr));
+    if (d.mass_coefficient) {  // the mass weight in the same layout (d_mass stays: diagonal, pencil batches)
+      if ((rc = h->d_massp.alloc(total * sizeof(T), true))) return rc;
+      acct += h->d_massp.bytes();
+      HIP_TRY(relayout_coef_launch<T>(h->d_massp.as<T>(), h->d_mass.as<const T>(), t_cb.get(), t_cp.get(), ncell_p * nd,
+                                      n, nullptr));
+    }
     HIP_TRY(hipDeviceSynchronize());
   }
   // persistent grids: as many workgroups as fit on the chip (each loops over its batches)
@@ -553,6 +568,8 @@ ApplyArgs<T> make_args(mfgpu_handle *h, void *dst, const void *src, int add) {
   a.hn_slot = h->d_hn_slot.get();
   a.coefp = h->d_coefp.as<const T>();
   a.coef = h->d_coef.as<const T>();
+  a.mass = h->d_mass.as<const T>();
+  a.massp = h->d_massp.as<const T>();
   a.cmask = h->d_cmask.get();
   a.hn_weights = h->d_hnw.as<const T>();
   a.tabS = h->d_tabsd.as<const T>();
@@ -652,6 +669,10 @@ int inverse_diagonal_typed(mfgpu_handle *h, void *diag, hipStream_t st) {
     HIP_TRY(diag_general_launch<T>(P.n, (T *)diag, nb, cell_off, dof_off, bdofs, lmap, coef, cmask, hnw, tab2, st));
   else
     HIP_TRY(diag_launch<T>(P.dim, P.n, (T *)diag, nb, cell_off, dof_off, bdofs, lmap, coef, cmask, hnw, tab2, st));
+  // + the mass term's local diagonal, distributed the same way (tab2's first half: S, squared unless general)
+  if (h->d_mass.get())
+    HIP_TRY(diag_mass_launch<T>(P.dim, P.n, (T *)diag, nb, cell_off, dof_off, bdofs, lmap, h->d_mass.as<const T>(), cmask,
+                                hnw, tab2, !general, st));
   // constraint_handler.set_constrained_values(inv_diag, 1.0)  (:412)
   HIP_TRY(set_values_launch<T>((T *)diag, h->d_constrained.get(), h->n_constrained, T(1), st));
   // inv_diag.invert()  (:414)
@@ -781,7 +802,7 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
     return MFGPU_EUNSUPPORTED;
   }
   if (!d.JxW || !d.inv_jac || !d.shape_values || !d.shape_gradients ||
-      (!d.coefficient && !d.quadrature_points)) {
+      (!d.coefficient && !d.quadrature_points)) {  // (mass_coefficient is optional)
     set_error("JxW, inv_jac, shape tables and coefficient (or quadrature_points) are required");
     return MFGPU_EINVAL;
   }

@@ -240,6 +240,64 @@ hipError_t diag_general2_launch(int n, T *diag, uint32_t n_batches, const uint32
   return hipGetLastError();
 }
 
+// Mass term: M_ii = sum_q m_q prod_d S[i_d][q_d]^2 with the folded weight m = c JxW (plan cell order), added to the
+// diagonal vector like the stiffness part above; the same for all three geometry variants.  `squared`: tab holds S.^2.
+template <int dim, int n, typename T>
+__global__ void __launch_bounds__(256)
+diag_mass_kernel(T *diag, const uint32_t *batch_cell_off, const uint32_t *batch_dof_off, const uint32_t *bdofs,
+                 const uint16_t *lmap, const T *mass, const uint32_t *cmask, const T *hn_weights, const T *tab,
+                 int squared) {
+  constexpr int n2 = n * n, nd = (dim == 3) ? n2 * n : n2;
+  __shared__ T S2[n2], Wl[n2], loc[nd], mq[nd];
+  const int tid = threadIdx.x;
+  for (int t = tid; t < n2; t += 256) {
+    S2[t] = squared ? tab[t] : tab[t] * tab[t];
+    Wl[t] = hn_weights ? hn_weights[t] : T(0);
+  }
+  const uint32_t b = blockIdx.x;
+  const uint32_t c0 = batch_cell_off[b], c1 = batch_cell_off[b + 1], d0 = batch_dof_off[b];
+  for (uint32_t c = c0; c < c1; ++c) {
+    __syncthreads();
+    for (int i = tid; i < nd; i += 256) mq[i] = mass[(size_t)c * nd + i];
+    __syncthreads();
+    for (int i = tid; i < nd; i += 256) {
+      const int ix = i % n, iy = (i / n) % n, iz = i / n2;
+      T sum = T(0);
+      for (int qz = 0; qz < (dim == 3 ? n : 1); ++qz)
+        for (int qy = 0; qy < n; ++qy) {
+          const T syz = dim == 3 ? S2[iy * n + qy] * S2[iz * n + qz] : S2[iy * n + qy];
+          for (int qx = 0; qx < n; ++qx) sum += mq[qx + n * qy + n2 * qz] * (S2[ix * n + qx] * syz);
+        }
+      loc[i] = sum;
+    }
+    __syncthreads();
+    hn_transpose_local<dim, n, T>(loc, Wl, cmask ? cmask[c] : 0u, tid);
+    for (int i = tid; i < nd; i += 256) {
+      const uint32_t g = bdofs[d0 + lmap[(size_t)c * nd + i]];
+      if (!(g >> 31)) atomicAdd(diag + g, loc[i]);
+    }
+  }
+}
+
+template <typename T>
+hipError_t diag_mass_launch(int dim, int n, T *diag, uint32_t n_batches, const uint32_t *batch_cell_off,
+                            const uint32_t *batch_dof_off, const uint32_t *bdofs, const uint16_t *lmap, const T *mass,
+                            const uint32_t *cmask, const T *hn_weights, const T *tab, bool squared, hipStream_t st) {
+  if (n_batches == 0) return hipSuccess;
+#define DM_CASE(D, N)                                                                                        \
+  case D * 10 + N:                                                                                           \
+    hipLaunchKernelGGL((diag_mass_kernel<D, N, T>), dim3(n_batches), dim3(256), 0, st, diag, batch_cell_off, \
+                       batch_dof_off, bdofs, lmap, mass, cmask, hn_weights, tab, squared ? 1 : 0);           \
+    break;
+  switch (dim * 10 + n) {
+    DM_CASE(2, 2) DM_CASE(2, 3) DM_CASE(2, 4) DM_CASE(2, 5) DM_CASE(2, 6) DM_CASE(2, 7)
+    DM_CASE(3, 2) DM_CASE(3, 3) DM_CASE(3, 4) DM_CASE(3, 5) DM_CASE(3, 6) DM_CASE(3, 7)
+    default: return hipErrorInvalidValue;
+  }
+#undef DM_CASE
+  return hipGetLastError();
+}
+
 template <typename T>
 __global__ void set_values_kernel(T *v, const uint32_t *idx, uint32_t n, T value) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -400,6 +458,9 @@ hipError_t vec_reduce_launch(int op, T *v, const T *x, const T *w, T a, size_t n
   template hipError_t diag_general2_launch<T>(int, T *, uint32_t, const uint32_t *, const uint32_t *, const uint32_t *, \
                                               const uint16_t *, const T *, const uint32_t *, const T *, const T *, \
                                               hipStream_t);                                                  \
+  template hipError_t diag_mass_launch<T>(int, int, T *, uint32_t, const uint32_t *, const uint32_t *, const uint32_t *, \
+                                          const uint16_t *, const T *, const uint32_t *, const T *, const T *, bool, \
+                                          hipStream_t);                                                      \
   template hipError_t set_values_launch<T>(T *, const uint32_t *, uint32_t, T, hipStream_t);                  \
   template hipError_t vec_map_launch<T>(int, T *, const T *, T, T, size_t, hipStream_t);                      \
   template hipError_t vec_reduce_launch<T>(int, T *, const T *, const T *, T, size_t, hipStream_t, double *);

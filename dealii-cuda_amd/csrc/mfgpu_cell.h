@@ -179,13 +179,32 @@ struct WaveSync {
 // 4*dim contractions (+ hanging-node passes), add into the batch accumulator `acc`.  A thread owns
 // pencil (pa, pb) of its cell; Wc / Rc / cf / lm point to the cell's scratch, coefficient and index map
 // in LDS.  stage_next() is called once, at the point where cf / lm are no longer needed.
-template <int dim, int n, typename T, bool HN, typename Sync, typename StageNext>
+// MASS: the mass term int c u v.  mq points to the cell's folded mass weights m = c JxW in global memory ([n^dim], x
+// fastest); the thread's pencil of them along the LAST direction is requested at the top and meets the values at the
+// quadrature points where the last interpolation produces them (P2 in 3D, P1 in 2D): r += m .* w.
+// MASS instantiations also add into the batch accumulator ONE WAVE AFTER THE OTHER (a barrier between two waves: 4
+// short rounds per chunk): the adds of one wave execute in program order -- what makes the plane kernels, one wave per
+// batch, repeatable -- so the sum of a dof several cells of a chunk share has a fixed order, and two calls on the same
+// inputs give the same bits.  Without the switch the four waves' ds_add_f64 meet in the order they arrive (last-bit
+// differences between calls on batches of several cells).
+template <int dim, int n, typename T, bool HN, typename Sync, bool MASS = false, typename StageNext>
 __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, const int pb, const unsigned mask,
                                               const bool any_mask, const T *usrc, double *acc, T *Wc, T *Rc,
                                               const T *cf, const uint16_t *lm, const T *Wl,
                                               const Tables<T, n> &tab, StageNext &&stage_next,
-                                              const int dbg = 0, unsigned long long *pst = nullptr) {
+                                              const int dbg = 0, unsigned long long *pst = nullptr,
+                                              const T *mq = nullptr) {
   constexpr int n2 = n * n;
+  // MASS: v -> accumulator, wave by wave (uniform loop: every thread passes every barrier)
+  auto add_in_cell_order = [&](const uint16_t (&idx)[n], const T (&val)[n]) {
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+      if (act && (int)(threadIdx.x >> 6) == w) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) lds_add(&acc[idx[i]], (double)val[i]);
+      }
+      Sync::sync();
+    }
+  };
 #ifdef MFGPU_STAMPS
 #define PDBG(bit) (dbg & (bit))
 #define PSTAMP(k)                                                                        \
@@ -207,6 +226,11 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
   constexpr int sl = (dim == 3) ? n2 : n;                 // stride of the last direction
   const int bl = (dim == 3) ? bz : by;                    // pencil base of the last direction
   T u[n], v[n], w[n], g[n], r[n];
+  T mm[MASS ? n : 1];
+  if (MASS && act) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) mm[i] = __builtin_nontemporal_load(mq + bl + i * sl);
+  }
   uint16_t ix[n], iz[n];
   if (act) {
 #pragma unroll
@@ -266,6 +290,10 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
 #pragma unroll
       for (int s = 0; s < n; ++s) g[s] *= v[s];
       mvt<n, -1>(tab.Dt, g, r);
+      if (MASS) {
+#pragma unroll
+        for (int s = 0; s < n; ++s) r[s] = fma(mm[s], w[s], r[s]);
+      }
       lds_put<n>(Wc + bz, n2, w);
       lds_put<n>(Rc + bz, n2, r);
     }
@@ -335,9 +363,14 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       if (act) {
         lds_load<n>(Rc + bx, 1, v);
         if (mask && hn_flag3<n, 0>(mask, pa, pb, type)) hn_pencil<n, T, true>(Wl, type, v);
+        if (!MASS) {
 #pragma unroll
-        for (int i = 0; i < n; ++i) lds_add(&acc[ix[i]], (double)v[i]);
+          for (int i = 0; i < n; ++i) lds_add(&acc[ix[i]], (double)v[i]);
+        }
       }
+      if (MASS) add_in_cell_order(ix, v);
+    } else if (MASS) {
+      add_in_cell_order(iz, v);
     } else if (act) {
 #pragma unroll
       for (int k = 0; k < n; ++k) if (!PDBG(16)) lds_add(&acc[iz[k]], (double)v[k]); else asm volatile("" ::"v"(v[k]), "v"(iz[k]));
@@ -374,6 +407,10 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
 #pragma unroll
       for (int s = 0; s < n; ++s) g[s] *= v[s];
       mvt<n, -1>(tab.Dt, g, r);
+      if (MASS) {
+#pragma unroll
+        for (int s = 0; s < n; ++s) r[s] = fma(mm[s], w[s], r[s]);
+      }
       lds_put<n>(Wc + by, n, w);
       lds_put<n>(Rc + by, n, r);
     }
@@ -408,9 +445,14 @@ __device__ __forceinline__ void cell_pipeline(const bool act, const int pa, cons
       if (act) {
         lds_load<n>(Rc + bx, 1, v);
         if (mask && hn_flag2<n, 0>(mask, pa, type)) hn_pencil<n, T, true>(Wl, type, v);
+        if (!MASS) {
 #pragma unroll
-        for (int i = 0; i < n; ++i) lds_add(&acc[ix[i]], (double)v[i]);
+          for (int i = 0; i < n; ++i) lds_add(&acc[ix[i]], (double)v[i]);
+        }
       }
+      if (MASS) add_in_cell_order(ix, v);
+    } else if (MASS) {
+      add_in_cell_order(iz, v);
     } else if (act) {
 #pragma unroll
       for (int k = 0; k < n; ++k) if (!PDBG(16)) lds_add(&acc[iz[k]], (double)v[k]); else asm volatile("" ::"v"(v[k]), "v"(iz[k]));

@@ -1,6 +1,7 @@
 // Cell integrals of a Poisson solve (include/mfgpu.h, "integrator"): the load vector with the Dirichlet lift of
 // poisson.cu:182-221 and the L2 error of VectorTools::integrate_difference(..., QGauss(p+2), L2_norm),
-// poisson.cu:277-292.  Double only (the reference's poisson uses `typedef double number`).
+// poisson.cu:277-292.  Double only (the reference's poisson uses `typedef double number`).  With a mass term in the
+// description (mfgpu_desc.mass_coefficient) the lift also subtracts int c phi_i u_b.
 //
 // Structure: one wave64 workgroup per cell; every per-point array is cell-major, so a wave reads its cell contiguously.
 // Inside the cell all tensor work is sum-factorised in LDS (tpass: one 1D contraction along one direction; a thread owns
@@ -51,6 +52,7 @@ struct IntArgs {
   const double *qpts;        // [n_cells * N^dim * dim]
   const double *jxw;         // [n_cells * N^dim]
   const double *metric;      // uniform: [cell][q] a J0^2 JxW; general: [cell][e][q] symmetric a JxW J^-1 J^-T
+  const double *mass;        // [cell][q] c JxW, or nullptr (no mass term)
   int general;
   // rhs
   const double *f_qp, *u_b;
@@ -208,7 +210,8 @@ __device__ __forceinline__ void load_tab(double *tab, const double *g) {
   for (int i = threadIdx.x; i < Tab<N>::size; i += 64) tab[i] = g[i];
 }
 
-// rhs_i = int phi_i f - int grad phi_i . a grad u_b  (poisson.cu:198-214), hanging-node TRANSPOSE, to a.local
+// rhs_i = int phi_i f - int grad phi_i . a grad u_b [- int c phi_i u_b]  (poisson.cu:198-214), hanging-node TRANSPOSE,
+// to a.local
 template <int dim, int N>
 __global__ void __launch_bounds__(64) rhs_cell_kernel(IntArgs a) {
   constexpr int ND = cpow(N, dim);
@@ -262,6 +265,12 @@ __global__ void __launch_bounds__(64) rhs_cell_kernel(IntArgs a) {
 #pragma unroll
     for (int e = 0; e < dim; ++e) {
       tensor<dim, N, N>(G + e * ND, TO, e == 0 ? GI : SI, e == 1 ? GI : SI, e == 2 ? GI : SI, T1, T2);
+      for (int i = threadIdx.x; i < ND; i += 64) LOC[i] -= TO[i];
+    }
+    if (a.mass) {  // mass part of the lift: u_b at the quadrature points, times c JxW, integrated against phi_i
+      tensor<dim, N, N>(A, G, S, S, S, T1, T2);
+      for (int q = threadIdx.x; q < ND; q += 64) G[q] *= a.mass[c0 + q];
+      tensor<dim, N, N>(G, TO, SI, SI, SI, T1, T2);
       for (int i = threadIdx.x; i < ND; i += 64) LOC[i] -= TO[i];
     }
   }
@@ -454,7 +463,7 @@ struct mfgpu_integrator {
   bool general = false;
   uint32_t n_cells = 0, n_dofs = 0;
   DeviceArray<uint32_t> d_l2g, d_cmask, d_off, d_idx;
-  DeviceArray<double> d_tab, d_qpts, d_jxw, d_metric;
+  DeviceArray<double> d_tab, d_qpts, d_jxw, d_metric, d_mass;
   DeviceArray<double> d_local, d_err, d_ones;
 };
 
@@ -520,8 +529,11 @@ static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
   // rather than take the resident d_qpts / d_jxw
   std::vector<uint32_t> order(nc);
   for (size_t c = 0; c < nc; ++c) order[c] = (uint32_t)c;
-  return fold_coefficient<double>(it->d_metric, d.coefficient, d.quadrature_points, d.JxW, d.inv_jac, order.data(), dim,
-                                  (uint32_t)nc, (uint32_t)nd, it->general);
+  if ((rc = fold_coefficient<double>(it->d_metric, d.coefficient, d.quadrature_points, d.JxW, d.inv_jac, order.data(),
+                                     dim, (uint32_t)nc, (uint32_t)nd, it->general)))
+    return rc;
+  return d.mass_coefficient ? fold_mass<double>(it->d_mass, d.mass_coefficient, d.JxW, order.data(), (uint32_t)nc, (uint32_t)nd)
+                            : 0;
 }
 
 int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out) {
@@ -581,6 +593,7 @@ static IntArgs base_args(const mfgpu_integrator *it) {
   a.qpts = it->d_qpts.get();
   a.jxw = it->d_jxw.get();
   a.metric = it->d_metric.get();
+  a.mass = it->d_mass.get();
   a.general = it->general ? 1 : 0;
   a.n_cells = it->n_cells;
   return a;

@@ -165,6 +165,9 @@ void hn_cell_lines(unsigned mask, int n, std::vector<HnLine> (&lines)[3], std::v
 //   x                  apply_batches_x: 3D two-pass otherwise
 //   g / g2             apply_batches_g / apply_batches_g2: no MFGPU_UNIFORM_J0, 3D / 2D
 //   batches            apply_batches: 2D uniform-Jacobian, coloured-scatter mode, MFGPU_KERNEL_PENCILS
+// With a mass term (d.mass_coefficient) every family has an instantiation except apply_planes4w (p = 5, 6): those
+// degrees go to apply_batches_x by default and a forced plane family is refused (MFGPU_EUNSUPPORTED); so is
+// MFGPU_KERNEL_PLANES_2W at p = 4 in double, whose instantiation would spill.
 enum class PlaneKernel : uint8_t { none, planes3, planes4 };
 enum class BatchKernel : uint8_t { none, batches, x, g, g2 };
 int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk, Plan &plan);

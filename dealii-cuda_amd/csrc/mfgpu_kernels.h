@@ -45,6 +45,11 @@ struct ApplyArgs {
   // kShBatchWords words {dof base, dof-list record, index-run record, 0}; bdofsp / idxp then hold every DISTINCT
   // record once, the dof lists relative to the batch's dof base
   const uint32_t *shtab = nullptr;
+  // mass term (mfgpu_desc.mass_coefficient; nullptr: none -- the launchers then run the MASS = false instantiations):
+  // the folded weight m = c * JxW per quadrature point, in plan cell order (pencil families) and in the per-batch
+  // [n*n rows][NT tasks] layout of coefp (plane families)
+  const T *mass = nullptr;
+  const T *massp = nullptr;
 };
 
 // 1D tables, passed by value as kernel arguments (=> scalar registers).
@@ -131,6 +136,11 @@ hipError_t fold_launch(T *c, const T *coef, const T *jxw, const T *j0, const uin
                        uint32_t n_cells, uint32_t nd, hipStream_t st);
 template <typename T>
 hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st);
+// Set-up of the mass weight, synchronised on return: out[pos * nd + q] = c[cell][q] * JxW[cell][q] for the cell at plan
+// position pos (JxW carries the determinant on every geometry path)
+template <typename T>
+int fold_mass(DeviceArray<T> &out, const void *mass_coefficient, const void *JxW, const uint32_t *cell_order,
+              uint32_t n_cells, uint32_t nd);
 // Set-up of the folded metric, synchronised on return: the description's coefficient (or, if NULL, the coefficient
 // evaluated from its quadrature_points), JxW and inv_jac go to the device as temporaries and are folded into `out`,
 // nd points per cell in the order cell_order[0 .. n_cells).  Per point the scalar a J0^2 JxW, or with `general` the
@@ -155,6 +165,12 @@ hipError_t diag_general2_launch(int n, T *diag, uint32_t n_batches, const uint32
                                 const uint32_t *batch_dof_off, const uint32_t *bdofs, const uint16_t *lmap,
                                 const T *metric, const uint32_t *cmask, const T *hn_weights, const T *tab,
                                 hipStream_t st);
+// adds the mass term's local diagonal M_ii = sum_q m_q prod_d S[i_d][q_d]^2 (all geometry variants; tab = the 1D table
+// [n*n] index dof*n + q, squared already or not)
+template <typename T>
+hipError_t diag_mass_launch(int dim, int n, T *diag, uint32_t n_batches, const uint32_t *batch_cell_off,
+                            const uint32_t *batch_dof_off, const uint32_t *bdofs, const uint16_t *lmap, const T *mass,
+                            const uint32_t *cmask, const T *hn_weights, const T *tab, bool squared, hipStream_t st);
 template <typename T>
 hipError_t set_values_launch(T *v, const uint32_t *idx, uint32_t n, T value, hipStream_t st);
 // op: 0 sadd (v = s v + a w), 1 equ (v = a w), 2 scale (v *= w), 3 divide (v /= w), 4 invert, 5 mul (v *= a)

@@ -33,7 +33,8 @@ namespace mfgpu {
 template <int n>
 constexpr int min_waves_per_simd() { return n <= 5 ? 2 : 1; }
 
-template <int dim, int n, typename T, bool HN, bool TWOPASS>
+// MASS: the mass term (A.mass, plan cell order), see cell_pipeline.
+template <int dim, int n, typename T, bool HN, bool TWOPASS, bool MASS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(min_waves_per_simd<n>())))
 apply_batches(const ApplyArgs<T> A, const Tables<T, n> tab) {
   constexpr int kBlock = 256;
@@ -227,13 +228,13 @@ apply_batches(const ApplyArgs<T> A, const Tables<T, n> tab) {
         if (cnt_next > 0) stage(cnt_next);
         return cnt_next > 0;
       };
-      cell_pipeline<dim, n, T, HN, WgSync>(act, pa, pb, mask, any_mask, usrc, acc, Wc, Rc, cf, lm, Wl, tab, stage_next, A.dbg,
+      cell_pipeline<dim, n, T, HN, WgSync, MASS>(act, pa, pb, mask, any_mask, usrc, acc, Wc, Rc, cf, lm, Wl, tab, stage_next, A.dbg,
 #ifdef MFGPU_STAMPS
-                                             (A.stamps && k == 1) ? A.stamps + (size_t)(A.batch_end + b) * 16 : nullptr
+                                             (A.stamps && k == 1) ? A.stamps + (size_t)(A.batch_end + b) * 16 : nullptr,
 #else
-                                             nullptr
+                                             nullptr,
 #endif
-        );
+                                             MASS ? A.mass + ((size_t)c0 + base + (act ? lc : 0)) * nd : nullptr);
       // Wc is next written in P0 of the following chunk and was last read in P4 (P2 in 2D); Rc is next
       // written in P2 (P1) and was last read before the scatter-add: both separated by barriers.
       if (k == 0 && ncell_eff <= CH && has_nb) load_src(Gn, SVn);  // single-chunk batch
@@ -361,7 +362,10 @@ static size_t lds_bytes_t(uint32_t nb_max) {
 
 template <int dim, int n, typename T, bool HN, bool TP>
 static hipError_t launch_k(const ApplyArgs<T> &a, const Tables<T, n> &tab, size_t lds, uint32_t grid, hipStream_t st) {
-  hipLaunchKernelGGL((apply_batches<dim, n, T, HN, TP>), dim3(grid), dim3(256), lds, st, a, tab);
+  if (a.mass)
+    hipLaunchKernelGGL((apply_batches<dim, n, T, HN, TP, true>), dim3(grid), dim3(256), lds, st, a, tab);
+  else
+    hipLaunchKernelGGL((apply_batches<dim, n, T, HN, TP>), dim3(grid), dim3(256), lds, st, a, tab);
   return hipGetLastError();
 }
 
@@ -381,9 +385,12 @@ static hipError_t launch_t(const ApplyArgs<T> &a, const double *S, const double 
 }
 
 template <int dim, int n, typename T, bool HN, bool TP>
-static hipError_t configure_k(size_t lds) {
-  return hipFuncSetAttribute((const void *)apply_batches<dim, n, T, HN, TP>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+static hipError_t configure_k(size_t lds) {  // (the MASS instantiation too: same LDS, same register cap)
+  const hipError_t e = hipFuncSetAttribute((const void *)apply_batches<dim, n, T, HN, TP, true>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  return e != hipSuccess ? e
+                         : hipFuncSetAttribute((const void *)apply_batches<dim, n, T, HN, TP>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 template <int dim, int n, typename T>
 static hipError_t attributes_t(size_t lds) {
@@ -496,6 +503,33 @@ int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *q
   return hip_check(hipDeviceSynchronize(), "coefficient fold");
 }
 
+// m[pos*nd+q] = c * JxW for the cell at plan position pos (mass term)
+template <typename T>
+__global__ void fold_mass_kernel(T *m, const T *c, const T *jxw, const uint32_t *order, uint32_t n_cells, uint32_t nd) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)n_cells * nd) return;
+  const uint32_t pos = (uint32_t)(i / nd), q = (uint32_t)(i - (size_t)pos * nd);
+  const size_t s = (size_t)order[pos] * nd + q;
+  m[i] = c[s] * jxw[s];
+}
+
+template <typename T>
+int fold_mass(DeviceArray<T> &out, const void *mass_coefficient, const void *JxW, const uint32_t *cell_order,
+              uint32_t n_cells, uint32_t nd) {
+  const size_t np = (size_t)n_cells * nd;
+  DeviceArray<T> c, jxw;
+  DeviceArray<uint32_t> order;
+  int rc;
+  if ((rc = c.upload(mass_coefficient, np)) || (rc = jxw.upload(JxW, np)) || (rc = order.upload(cell_order, n_cells)) ||
+      (rc = out.alloc(np)))
+    return rc;
+  if (np == 0) return 0;
+  hipLaunchKernelGGL(fold_mass_kernel<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, nullptr, out.get(), c.get(),
+                     jxw.get(), order.get(), n_cells, nd);
+  if ((rc = hip_check(hipGetLastError(), "mass fold"))) return rc;
+  return hip_check(hipDeviceSynchronize(), "mass fold");
+}
+
 template <typename T>
 hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
   if (n == 0) return hipSuccess;
@@ -515,6 +549,7 @@ hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
                                      uint32_t, hipStream_t);                                            \
   template int fold_coefficient<T>(DeviceArray<T> &, const void *, const void *, const void *, const void *,       \
                                    const uint32_t *, int, uint32_t, uint32_t, bool);                    \
+  template int fold_mass<T>(DeviceArray<T> &, const void *, const void *, const uint32_t *, uint32_t, uint32_t); \
   template hipError_t fill_launch<T>(T *, size_t, T, hipStream_t);
 INST(double)
 INST(float)

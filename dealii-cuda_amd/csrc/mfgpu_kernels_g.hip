@@ -30,7 +30,12 @@ __device__ __forceinline__ int gix_at(const uint32_t (&w)[(n + 1) / 2], int i) {
   return (int)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
 }
 
-template <int n, typename T, bool HN>
+// MASS: the mass term int c u v.  The pointwise stage P5 is where everything per quadrature point meets in linear order:
+// the values at the quadrature points w are still in their array (last read as w in P4), so P5 also replaces w by
+// m .* w (m = c JxW, A.mass, loaded with the metric), and P6 starts the result from it: r = m .* w + D_z^T tz.
+// MASS instantiations add into the batch accumulator one wave after the other (fixed summation order: two calls on the
+// same inputs give the same bits; see cell_pipeline in mfgpu_cell.h).
+template <int n, typename T, bool HN, bool MASS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
   constexpr int kBlock = 256;
@@ -123,6 +128,7 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
   // folded metric M = a JxW J J^T of this thread's points of a chunk, stored [cell][e][q] with
   // e = {00, 01, 02, 11, 12, 22}: for one entry the lanes of a wave read consecutive doubles
   T M[PF][6];
+  T MM[MASS ? PF : 1];
   auto load_metric = [&](uint32_t cell0, int cnt) {
     const T *mg = A.coef + (size_t)cell0 * nd * 6;
     const int l = lane();
@@ -134,6 +140,7 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
       const T *p = mg + (size_t)cl * (6 * nd) + q;
 #pragma unroll
       for (int e = 0; e < 6; ++e) M[j][e] = g_stream_load(p + e * nd);
+      if (MASS) MM[j] = g_stream_load(A.mass + (size_t)cell0 * nd + i);
     }
   };
   auto chunk_count = [&](int ncell_, int base_) { return (ncell_ - base_ < CH ? ncell_ - base_ : CH) * nd; };
@@ -281,6 +288,7 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
             Gxb[i] = fma(M[j][0], gx, fma(M[j][1], gy, M[j][2] * gz));
             Gyb[i] = fma(M[j][1], gx, fma(M[j][3], gy, M[j][4] * gz));
             Gzb[i] = fma(M[j][2], gx, fma(M[j][4], gy, M[j][5] * gz));
+            if (MASS) Wb[i] = MM[j] * Wb[i];
           }
         }
       }
@@ -289,6 +297,11 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
       if (act) {
         lds_load<n>(Gzc + bz, n2, g);
         mvt<n, -1>(tab.Dt, g, v);
+        if (MASS) {
+          lds_load<n>(Wc + bz, n2, u);
+#pragma unroll
+          for (int s = 0; s < n; ++s) v[s] += u[s];
+        }
         lds_put<n>(Wc + bz, n2, v);
       }
       __syncthreads();
@@ -348,7 +361,15 @@ apply_batches_g(const ApplyArgs<T> A, const Tables<T, n> tab) {
           if (mask && hn_flag3<n, 0>(mask, pa, pb, type)) hn_pencil<n, T, true, true>(Wl, type, v);
         }
       }
-      if (act) {
+      if (MASS) {
+        for (int w = 0; w < 4; ++w) {  // (256 threads; uniform: every thread passes every barrier)
+          if (act && (tid >> 6) == w) {
+#pragma unroll
+            for (int i = 0; i < n; ++i) lds_add(&ua[gix_at<n>(IX[k], i)], (double)v[i]);
+          }
+          __syncthreads();
+        }
+      } else if (act) {
 #pragma unroll
         for (int i = 0; i < n; ++i) lds_add(&ua[gix_at<n>(IX[k], i)], (double)v[i]);
       }
@@ -425,14 +446,18 @@ static size_t g_lds_bytes(uint32_t nb_max) {
 template <int n, typename T, bool HN>
 static hipError_t g_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
   *lds = g_lds_bytes<n, T>(nb_max);
-  return configure_kernel((const void *)apply_batches_g<n, T, HN>, *lds, 256, blocks);
+  const hipError_t e = configure_kernel((const void *)apply_batches_g<n, T, HN, true>, *lds, 256, blocks);  // (MASS too)
+  return e == hipSuccess ? configure_kernel((const void *)apply_batches_g<n, T, HN>, *lds, 256, blocks) : e;
 }
 
 template <int n, typename T, bool HN>
 static hipError_t g_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
   const Tables<T, n> tab = make_tables<T, n>(S, Dt);
   const size_t lds = g_lds_bytes<n, T>(a.nb_max);
-  hipLaunchKernelGGL((apply_batches_g<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
+  if (a.mass)
+    hipLaunchKernelGGL((apply_batches_g<n, T, HN, true>), dim3(grid), dim3(256), lds, st, a, tab);
+  else
+    hipLaunchKernelGGL((apply_batches_g<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
   return hipGetLastError();
 }
 

@@ -20,7 +20,10 @@ namespace {
 // hanging_nodes.cuh:38-50 (2D subset)
 constexpr unsigned kTypeX = 1u << 0, kTypeY = 1u << 1, kFaceX = 1u << 3, kFaceY = 1u << 4;
 
-template <int n, typename T, bool HN>
+// MASS: the mass term int c u v -- m .* v (m = c JxW, A.mass) joins the result at the quadrature points, next to
+// D_x^T f_x + D_y^T f_y, before the transposed interpolation.  MASS instantiations add into the batch accumulator one
+// wave after the other (fixed summation order: two calls on the same inputs give the same bits; see cell_pipeline).
+template <int n, typename T, bool HN, bool MASS = false>
 __global__ void __launch_bounds__(256)
 apply_batches_g2(const ApplyArgs<T> A) {
   constexpr int nd = n * n, CH = 256 / nd, p = n - 1;
@@ -106,8 +109,10 @@ apply_batches_g2(const ApplyArgs<T> A) {
       }
       __syncthreads();
       // reference-cell gradient, metric, per point
+      T mv = T(0);  // MASS: m .* v of this thread's point
       if (act) {
         T gx = T(0), gy = T(0);
+        if (MASS) mv = A.mass[cell * nd + q] * x[q];
         for (int t = 0; t < n; ++t) {
           gx += Dt[i * n + t] * x[t + n * j];
           gy += Dt[j * n + t] * x[i + n * t];
@@ -122,7 +127,7 @@ apply_batches_g2(const ApplyArgs<T> A) {
       if (act) {
         T s = T(0);
         for (int t = 0; t < n; ++t) s += Dt[t * n + i] * fx[t + n * j] + Dt[t * n + j] * fy[i + n * t];
-        y[q] = s;
+        y[q] = MASS ? s + mv : s;
       }
       __syncthreads();
       if (act) {
@@ -143,8 +148,15 @@ apply_batches_g2(const ApplyArgs<T> A) {
         __syncthreads();
         if (act) out = hn_pass(x, 0, true);
       }
-      if (act) atomicAdd(&acc[lm], (double)out);
-      __syncthreads();
+      if (MASS) {
+        for (int w = 0; w < 4; ++w) {  // (256 threads; uniform: every thread passes every barrier)
+          if (act && (tid >> 6) == w) atomicAdd(&acc[lm], (double)out);
+          __syncthreads();
+        }
+      } else {
+        if (act) atomicAdd(&acc[lm], (double)out);
+        __syncthreads();
+      }
     }
     // ---- scatter (fee_gpu.cuh:346-363): interior dofs are this batch's alone and final; partial sums of the others
     // go to the batch's halo slots (pass 2)
@@ -185,13 +197,17 @@ size_t g2_lds_bytes(uint32_t nb_max) {
 template <int n, typename T, bool HN>
 hipError_t g2_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
   *lds = g2_lds_bytes<n, T>(nb_max);
-  return configure_kernel((const void *)apply_batches_g2<n, T, HN>, *lds, 256, blocks);
+  const hipError_t e = configure_kernel((const void *)apply_batches_g2<n, T, HN, true>, *lds, 256, blocks);  // (MASS too)
+  return e == hipSuccess ? configure_kernel((const void *)apply_batches_g2<n, T, HN>, *lds, 256, blocks) : e;
 }
 
 template <int n, typename T, bool HN>
 hipError_t g2_launch_t(const ApplyArgs<T> &a, uint32_t grid, hipStream_t st) {
   const size_t lds = g2_lds_bytes<n, T>(a.nb_max);
-  hipLaunchKernelGGL((apply_batches_g2<n, T, HN>), dim3(grid), dim3(256), lds, st, a);
+  if (a.mass)
+    hipLaunchKernelGGL((apply_batches_g2<n, T, HN, true>), dim3(grid), dim3(256), lds, st, a);
+  else
+    hipLaunchKernelGGL((apply_batches_g2<n, T, HN>), dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 

@@ -52,7 +52,13 @@ namespace mfgpu {
 // addressing are what they are in the expanded form, and so are the arithmetic and its order.  A batch's table entry
 // is fetched THREE batches ahead (one before the dof list it addresses) with one coalesced vector load that joins the
 // iteration's other loads under the same vmcnt wait; its words become scalars at the iteration boundary.
-template <int n, typename T, bool ADD, bool HN, bool SH = false>
+//
+// MASS: the mass term int c u v (mfgpu_desc.mass_coefficient).  The values at the quadrature points v = S u are
+// stage B's v[] (collocation form), in the layout in which the folded coefficient meets the gradients, so the term is
+// one more streamed array in coefp's layout (A.massp, m = c JxW) and one FMA per point, r += m .* v, where the
+// y-derivative part completes r -- before the transposed interpolation; no new contraction, transpose or barrier.
+// Its rows travel with the coefficient rows (the next batch's, in stage C).  MASS = false is the code without it.
+template <int n, typename T, bool ADD, bool HN, bool SH = false, bool MASS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   constexpr int n2 = n * n;
@@ -198,6 +204,7 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     }
   };
   T Cc[n2];
+  T Mm[MASS ? n2 : 1];  // MASS: the batch's mass rows, as Cc
   T SVn[KGU], R[KGU], old[KGU];
   // SH: the table entries of the previous batch (deferred scatter), this one, the next two; Mv: the third ahead, in
   // flight.  Expanded form: all zero and unused.
@@ -221,6 +228,11 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     const T *p = A.coefp + (size_t)b * (n2 * NT) + tk;
 #pragma unroll
     for (int r = 0; r < n2; ++r) Cc[r] = nt_load(p + r * NT);
+  }
+  if (MASS) {
+    const T *p = A.massp + (size_t)b * (n2 * NT) + tk;
+#pragma unroll
+    for (int r = 0; r < n2; ++r) Mm[r] = nt_load(p + r * NT);
   }
 #pragma unroll
   for (int j = 0; j < KGU; ++j) {
@@ -331,11 +343,17 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
       MFGPU_PIN_VMEM();
     };
     const T *const cnext = A.coefp + (size_t)b1 * (n2 * NT) + tk;
+    const T *const mnext = MASS ? A.massp + (size_t)b1 * (n2 * NT) + tk : nullptr;
     auto hookC = [&](int s) {  // 2 n steps: the next batch's coefficient rows (stage B is done with this batch's)
       MFGPU_PIN_VMEM();
 #pragma unroll
       for (int r = (n2 * s) / (2 * n); r < (n2 * (s + 1)) / (2 * n); ++r)
         Cc[r] = nt_load(cnext + r * NT);
+      if (MASS) {  // ... and its mass rows
+#pragma unroll
+        for (int r = (n2 * s) / (2 * n); r < (n2 * (s + 1)) / (2 * n); ++r)
+          Mm[r] = nt_load(mnext + r * NT);
+      }
       MFGPU_PIN_VMEM();
     };
 
@@ -434,8 +452,9 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
 #pragma unroll
         for (int y = 0; y < n; ++y) g[y] *= Cc[y + n * z];
         eo_apply<n, 3>(tab, g, o);
+        // (MASS: + m .* v, the line of v is still in `in`)
 #pragma unroll
-        for (int y = 0; y < n; ++y) r[y + n * z] += o[y];
+        for (int y = 0; y < n; ++y) r[y + n * z] += MASS ? fma(Mm[y + n * z], in[y], o[y]) : o[y];
         hookB(3 * n + z);
       }
       // r' = S_z^T r
@@ -568,44 +587,58 @@ static size_t p_lds_bytes(bool hn) {
          (size_t)2 * (p_cells_per_wave(n) + 1) * p_cell_stride(n) * sizeof(T);
 }
 
-template <int n, typename T>
-static hipError_t p_configure_t(bool hn, size_t *lds, int *blocks) {
+template <int n, typename T, bool MASS>
+static hipError_t p_configure_m(bool hn, size_t *lds, int *blocks) {
   *lds = p_lds_bytes<n, T>(hn);
-  const void *f0 = hn ? (const void *)apply_planes3<n, T, false, true> : (const void *)apply_planes3<n, T, false, false>;
-  const void *f1 = hn ? (const void *)apply_planes3<n, T, true, true> : (const void *)apply_planes3<n, T, true, false>;
+  const void *f0 = hn ? (const void *)apply_planes3<n, T, false, true, false, MASS>
+                      : (const void *)apply_planes3<n, T, false, false, false, MASS>;
+  const void *f1 = hn ? (const void *)apply_planes3<n, T, true, true, false, MASS>
+                      : (const void *)apply_planes3<n, T, true, false, false, MASS>;
   hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
   if (e == hipSuccess && !hn) {  // the shared-record instantiations (same LDS; same occupancy, checked at build time)
-    e = hipFuncSetAttribute((const void *)apply_planes3<n, T, true, false, true>,
+    e = hipFuncSetAttribute((const void *)apply_planes3<n, T, true, false, true, MASS>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
     if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)apply_planes3<n, T, false, false, true>,
+      e = hipFuncSetAttribute((const void *)apply_planes3<n, T, false, false, true, MASS>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
   }
   return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
 }
-
+// both the plain and the MASS instantiations get the attribute (a handle launches one set, chosen by a.massp); they
+// have the same LDS and the same occupancy (one wave per SIMD)
 template <int n, typename T>
-static hipError_t p_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
+static hipError_t p_configure_t(bool hn, size_t *lds, int *blocks) {
+  const hipError_t e = p_configure_m<n, T, true>(hn, lds, blocks);
+  return e == hipSuccess ? p_configure_m<n, T, false>(hn, lds, blocks) : e;
+}
+
+template <int n, typename T, bool MASS>
+static hipError_t p_launch_m(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
                              hipStream_t st) {
   const size_t lds = p_lds_bytes<n, T>(hn);
   const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
   if (hn) {
     if (a.add)
-      hipLaunchKernelGGL((apply_planes3<n, T, true, true>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes3<n, T, true, true, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
     else
-      hipLaunchKernelGGL((apply_planes3<n, T, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes3<n, T, false, true, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
   } else if (a.shtab) {  // shared form of the index records (chosen per plan: Plan::sh_use)
     if (a.add)
-      hipLaunchKernelGGL((apply_planes3<n, T, true, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes3<n, T, true, false, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
     else
-      hipLaunchKernelGGL((apply_planes3<n, T, false, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes3<n, T, false, false, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
   } else {
     if (a.add)
-      hipLaunchKernelGGL((apply_planes3<n, T, true, false>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes3<n, T, true, false, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
     else
-      hipLaunchKernelGGL((apply_planes3<n, T, false, false>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes3<n, T, false, false, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
   }
   return hipGetLastError();
+}
+template <int n, typename T>
+static hipError_t p_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
+                             hipStream_t st) {
+  return a.massp ? p_launch_m<n, T, true>(a, S, Dt, hn, grid, st) : p_launch_m<n, T, false>(a, S, Dt, hn, grid, st);
 }
 
 #define P_SWITCH(FN, ...)                 \

@@ -45,7 +45,12 @@ namespace mfgpu {
 // Only LDS instructions may cross: pins a global memory operation between two compute steps
 #define MFGPU_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x380)
 
-template <int n, typename T, bool ADD, bool HN>
+// MASS: the mass term int c u v (see apply_planes3): r += m .* v in S4, where the y-derivative part rewrites v in
+// place.  The batch's mass rows (A.massp, coefp's layout) are requested during S3, n rows per step between its
+// contractions under the same pins as the other spread loads, and consumed at the end of S4, three contraction passes
+// later.  apply_planes4 at n <= 4 and at n = 5 in float only: <5, double> spills with the extra plane and
+// apply_planes4w has four planes live in S4 -- the planner refuses or reroutes those (choose_kernel_and_plan).
+template <int n, typename T, bool ADD, bool HN, bool MASS = false>
 __device__ __forceinline__ void planes4_body(const ApplyArgs<T> &A, const TablesEO<T, n> &tab) {
   constexpr int n2 = n * n;
   constexpr int CW = p_cells_per_wave(n);  // cells per wave
@@ -308,6 +313,8 @@ __device__ __forceinline__ void planes4_body(const ApplyArgs<T> &A, const Tables
     // the next batch's dof list: the gather addresses must be here when the gather is issued (before S5)
     uint32_t Gn[KGU];
     load_dofs(b1, Gn);
+    T Mm[MASS ? n2 : 1];  // MASS: this batch's mass rows, consumed at the end of S4
+    const T *const mthis = MASS ? A.massp + (size_t)b * (n2 * NT) + tk : nullptr;
 
     // ---- S3 (xy): w = D_x^T t' into registers; a -> T (same entries, this lane's own)
     T w[n2];
@@ -320,6 +327,12 @@ __device__ __forceinline__ void planes4_body(const ApplyArgs<T> &A, const Tables
       set_line<n, 0>(w, y, wl);
 #pragma unroll
       for (int x = 0; x < n; ++x) Tw[pxy + x + n * y] = u[x + n * y];
+      if (MASS) {  // n of the n * n mass rows per step
+        MFGPU_PIN_VMEM();
+#pragma unroll
+        for (int r = n * y; r < n * (y + 1); ++r) Mm[r] = nt_load(mthis + r * NT);
+        MFGPU_PIN_VMEM();
+      }
     }
     WaveSync::sync();
 
@@ -356,6 +369,10 @@ __device__ __forceinline__ void planes4_body(const ApplyArgs<T> &A, const Tables
 #pragma unroll
         for (int y = 0; y < n; ++y) g[y] *= Cc[y + n * z];
         eo_apply<n, 3>(tab, g, o);
+        if (MASS) {  // + m .* v
+#pragma unroll
+          for (int y = 0; y < n; ++y) o[y] = fma(Mm[y + n * z], in[y], o[y]);
+        }
         set_line<n, 0>(v, z, o);
       }
       // ... and its S_z^T image added
@@ -475,10 +492,10 @@ __device__ __forceinline__ void planes4_body(const ApplyArgs<T> &A, const Tables
 // p <= 4: two waves per SIMD (<= 256 registers).  p = 5, 6 (n = 6, 7): a plane is 72 / 98 registers and four of them
 // are live in S4 -- one wave per SIMD with the whole register file; the single aliased transpose array is what lets
 // four such workgroups share a CU's LDS at all (34 / 36 KB each).
-template <int n, typename T, bool ADD, bool HN>
+template <int n, typename T, bool ADD, bool HN, bool MASS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 apply_planes4(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
-  planes4_body<n, T, ADD, HN>(A, tab);
+  planes4_body<n, T, ADD, HN, MASS>(A, tab);
 }
 template <int n, typename T, bool ADD>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
@@ -496,6 +513,7 @@ static hipError_t q_configure_w(size_t *lds, int *blocks) {
 
 template <int n, typename T>
 static hipError_t q_launch_w(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
+  if (a.massp) return hipErrorInvalidValue;  // no MASS instantiation (the planner sends such descriptions elsewhere)
   const size_t lds = q_lds_bytes<T>(n, false);
   const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
   if (a.add)
@@ -505,32 +523,51 @@ static hipError_t q_launch_w(const ApplyArgs<T> &a, const double *S, const doubl
   return hipGetLastError();
 }
 
-template <int n, typename T>
-static hipError_t q_configure_t(bool hn, size_t *lds, int *blocks) {
+// <5, double, MASS> would spill (148 B per lane, <HN> 292): not instantiated, the planner refuses the request
+template <int n, typename T, bool MASS>
+constexpr bool q_has() { return !(MASS && n == 5 && sizeof(T) == 8); }
+
+template <int n, typename T, bool MASS>
+static hipError_t q_configure_m(bool hn, size_t *lds, int *blocks) {
   *lds = q_lds_bytes<T>(n, hn);
-  const void *f0 = hn ? (const void *)apply_planes4<n, T, false, true> : (const void *)apply_planes4<n, T, false, false>;
-  const void *f1 = hn ? (const void *)apply_planes4<n, T, true, true> : (const void *)apply_planes4<n, T, true, false>;
+  if constexpr (!q_has<n, T, MASS>()) return hipSuccess; else {
+  const void *f0 = hn ? (const void *)apply_planes4<n, T, false, true, MASS> : (const void *)apply_planes4<n, T, false, false, MASS>;
+  const void *f1 = hn ? (const void *)apply_planes4<n, T, true, true, MASS> : (const void *)apply_planes4<n, T, true, false, MASS>;
   const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
   return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
+  }
+}
+// (both sets get the attribute; same LDS, same two waves per SIMD)
+template <int n, typename T>
+static hipError_t q_configure_t(bool hn, size_t *lds, int *blocks) {
+  const hipError_t e = q_configure_m<n, T, true>(hn, lds, blocks);
+  return e == hipSuccess ? q_configure_m<n, T, false>(hn, lds, blocks) : e;
 }
 
-template <int n, typename T>
-static hipError_t q_launch_t(bool hn, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+template <int n, typename T, bool MASS>
+static hipError_t q_launch_m(bool hn, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
                              hipStream_t st) {
+  if constexpr (!q_has<n, T, MASS>()) return hipErrorInvalidValue; else {
   const size_t lds = q_lds_bytes<T>(n, hn);
   const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
   if (hn) {
     if (a.add)
-      hipLaunchKernelGGL((apply_planes4<n, T, true, true>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes4<n, T, true, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
     else
-      hipLaunchKernelGGL((apply_planes4<n, T, false, true>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes4<n, T, false, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
   } else {
     if (a.add)
-      hipLaunchKernelGGL((apply_planes4<n, T, true, false>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes4<n, T, true, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
     else
-      hipLaunchKernelGGL((apply_planes4<n, T, false, false>), dim3(grid), dim3(64), lds, st, a, tab);
+      hipLaunchKernelGGL((apply_planes4<n, T, false, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
   }
   return hipGetLastError();
+  }
+}
+template <int n, typename T>
+static hipError_t q_launch_t(bool hn, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
+                             hipStream_t st) {
+  return a.massp ? q_launch_m<n, T, true>(hn, a, S, Dt, grid, st) : q_launch_m<n, T, false>(hn, a, S, Dt, grid, st);
 }
 
 // p = 5, 6: the one-wave-per-SIMD kernel, no <HN> instantiation

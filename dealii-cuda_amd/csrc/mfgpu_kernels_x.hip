@@ -39,16 +39,28 @@ __device__ __forceinline__ int ix_at(const uint32_t (&w)[(n + 1) / 2], int i) {
 // One chunk of cells: a thread owns pencil (pa, pb) of its cell.  u: the cell's source values along the
 // thread's x-pencil; ixw: batch-local dof ids of that pencil (packed 16-bit).  stage_next() is called
 // where the coefficient buffer is dead.
-template <int n, typename T, bool HN, typename StageNext>
+// MASS: the mass term int c u v.  mz points to the folded mass weight m = c JxW at the first point of the thread's
+// z-pencil (global memory, plan cell order; stride n*n): requested at the top, used in P2, where the values at the
+// quadrature points are in registers along that pencil: r += m .* w.  (Straight from global memory, no LDS staging:
+// the lanes of the z-layout cover whole cells, so every line fetched is used; n registers per thread.)
+// MASS instantiations add into the batch accumulator one wave after the other (see cell_pipeline): a fixed summation
+// order, two calls on the same inputs give the same bits.
+template <int n, typename T, bool HN, bool MASS = false, typename StageNext>
 __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty, const bool actz, const int pa, const int pb,
                                                 const unsigned mask, const bool any_mask, T (&u)[n],
                                                 const uint32_t (&ixw)[(n + 1) / 2], double *acc, T *Wc, T *Rc, const T *cf,
                                                 T *Wy, T *Ry, const T *Cy, T *Wz, T *Rz, const T *Cz, const T *Wl,
-                                                const Tables<T, n> &tab, StageNext &&stage_next) {
+                                                const Tables<T, n> &tab, StageNext &&stage_next,
+                                                const T *mz = nullptr) {
 
   constexpr int n2 = n * n;
   const int bx = n * pa + n2 * pb;  // x-pencil (y = pa, z = pb), stride 1
   T v[n], w[n], g[n], r[n];
+  T mm[MASS ? n : 1];
+  if (MASS && actz) {
+#pragma unroll
+    for (int s = 0; s < n; ++s) mm[s] = stream_load(mz + s * n2);
+  }
   if (HN && any_mask) {
     // resolve_hanging_nodes_shmem<NOTRANSPOSE>: x, then y, then z (hanging_nodes.cuh:767-777)
     bool type;
@@ -94,6 +106,10 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
 #pragma unroll
     for (int s = 0; s < n; ++s) g[s] *= v[s];
     mvt<n, -1>(tab.Dt, g, r);
+    if (MASS) {
+#pragma unroll
+      for (int s = 0; s < n; ++s) r[s] = fma(mm[s], w[s], r[s]);
+    }
     lds_put<n>(Wz, n2, w);
     lds_put<n>(Rz, n2, r);
   }
@@ -163,7 +179,15 @@ __device__ __forceinline__ void cell_pipeline_x(const bool act, const bool acty,
       if (mask && hn_flag3<n, 0>(mask, pa, pb, type)) hn_pencil<n, T, true, true>(Wl, type, v);
     }
   }
-  if (act) {
+  if (MASS) {
+    for (int w = 0; w < 4; ++w) {  // (256 threads; uniform: every thread passes every barrier)
+      if (act && (int)(threadIdx.x >> 6) == w) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) lds_add(&acc[ix_at<n>(ixw, i)], (double)v[i]);
+      }
+      __syncthreads();
+    }
+  } else if (act) {
 #pragma unroll
     for (int i = 0; i < n; ++i) lds_add(&acc[ix_at<n>(ixw, i)], (double)v[i]);
   }
@@ -176,7 +200,7 @@ constexpr int x_waves_per_simd() { return n <= 5 ? 3 : 2; }
 template <int n>
 constexpr int x_chunks() { return n == 4 ? 4 : kMaxChunks; }
 
-template <int n, typename T, bool HN>
+template <int n, typename T, bool HN, bool MASS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(x_waves_per_simd<n>())))
 apply_batches_x(const ApplyArgs<T> A, const Tables<T, n> tab) {
   constexpr int kBlock = 256;
@@ -420,10 +444,14 @@ apply_batches_x(const ApplyArgs<T> A, const Tables<T, n> tab) {
         any_mask = __syncthreads_or(mask != 0) != 0;
       }
       const bool acty = oy >= 0 && base + cy < ncell, actz = oz >= 0 && base + cz < ncell;
-      cell_pipeline_x<n, T, HN>(act, acty, actz, pa, pb, mask, any_mask, U[k], IX[k], ua, Wc, Rc, cf, Wb + oy, Rb + oy,
-                                Cb + oy, Wb + oz, Rb + oz, Cb + oz, Wl, tab, [&]() {
-                                  if (cnt_next > 0) stage(cnt_next);
-                                });
+      // (oz indexes the chunk's CH * nd values, and the chunk's cells are contiguous in plan order)
+      cell_pipeline_x<n, T, HN, MASS>(
+          act, acty, actz, pa, pb, mask, any_mask, U[k], IX[k], ua, Wc, Rc, cf, Wb + oy, Rb + oy, Cb + oy, Wb + oz,
+          Rb + oz, Cb + oz, Wl, tab,
+          [&]() {
+            if (cnt_next > 0) stage(cnt_next);
+          },
+          MASS && actz ? A.mass + ((size_t)c0 + base) * nd + oz : nullptr);
     }
     if (has_nb && ncell <= (KC - 1) * CH) {  // short batch (ragged meshes): no overlap
       load_src(Gn, SVn);
@@ -484,14 +512,19 @@ static size_t x_lds_bytes(uint32_t nb_max) {
 template <int n, typename T, bool HN>
 static hipError_t x_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
   *lds = x_lds_bytes<n, T>(nb_max);
-  return configure_kernel((const void *)apply_batches_x<n, T, HN>, *lds, 256, blocks);
+  // (the MASS instantiation too: same LDS, same register cap, hence the same occupancy)
+  const hipError_t e = configure_kernel((const void *)apply_batches_x<n, T, HN, true>, *lds, 256, blocks);
+  return e == hipSuccess ? configure_kernel((const void *)apply_batches_x<n, T, HN>, *lds, 256, blocks) : e;
 }
 
 template <int n, typename T, bool HN>
 static hipError_t x_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
   const Tables<T, n> tab = make_tables<T, n>(S, Dt);
   const size_t lds = x_lds_bytes<n, T>(a.nb_max);
-  hipLaunchKernelGGL((apply_batches_x<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
+  if (a.mass)
+    hipLaunchKernelGGL((apply_batches_x<n, T, HN, true>), dim3(grid), dim3(256), lds, st, a, tab);
+  else
+    hipLaunchKernelGGL((apply_batches_x<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
   return hipGetLastError();
 }
 

@@ -930,13 +930,24 @@ int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk
     set_error("mfgpu_desc.kernel: this kernel family does not cover the description (see include/mfgpu.h)");
     return MFGPU_EUNSUPPORTED;
   }
+  // mass term: apply_planes4w (p = 5, 6) has no MASS instantiation -- a fifth plane of registers spills there -- so
+  // those degrees run in the pencil kernel, whose plan is the one of MFGPU_KERNEL_PENCILS_X
+  const bool mass_no_planes = d.mass_coefficient != nullptr && d.degree >= 5;
+  // ... and apply_planes4<5, double> would spill with it (p = 4 in double runs in apply_planes3)
+  const bool mass_no_planes4 = d.mass_coefficient != nullptr && d.degree == 4 && d.number_type == MFGPU_F64 &&
+                               d.kernel == MFGPU_KERNEL_PLANES_2W;
+  if ((mass_no_planes && want_planes) || mass_no_planes4) {
+    set_error("mfgpu_desc.kernel: this plane kernel has no mass-term instantiation at this degree (apply_planes4w at "
+              "p = 5, 6; apply_planes4 at p = 4 in double); use MFGPU_KERNEL_AUTO or MFGPU_KERNEL_PENCILS_X");
+    return MFGPU_EUNSUPPORTED;
+  }
   // by default the plane kernel serves p = 4 only: at p = 2, 3 the pencil kernel measures faster
   // (on meshes with hanging nodes also p = 3: 0.174 instead of 0.256 ms on the bmop ADAPTIVE_GRID mesh, n_ref = 6)
   // p = 5, 6: apply_planes4 with one wave per SIMD (apply_planes3's two transpose arrays do not fit the LDS there)
   // p = 3: apply_planes4 with two waves per SIMD (16 cells per wave) measures 9 % faster than the pencil kernel per
   // vmult (0.222 vs 0.243 ms at 10^7 dofs; profiles/r03_notes.md); p = 2: the pencil kernel stays ahead
   // (in float the pencil kernel is ahead at p = 3 on conforming meshes: 0.152 vs 0.179 ms)
-  bool planes = pk_ok && (want_planes || (d.kernel == MFGPU_KERNEL_AUTO &&
+  bool planes = pk_ok && !mass_no_planes && (want_planes || (d.kernel == MFGPU_KERNEL_AUTO &&
                                      (d.degree >= 4 || (d.degree == 3 && (hn || d.number_type == MFGPU_F64)))));
   bool pencils_x = xk_ok && !planes && d.kernel != MFGPU_KERNEL_PENCILS;
   PlanLimits lim;
@@ -991,7 +1002,9 @@ int mfgpu_plan_create(const mfgpu_desc *desc, mfgpu_plan **out) {
   mfgpu_plan *p = new mfgpu_plan();
   mfgpu::PlaneKernel pk;
   mfgpu::BatchKernel bk;
-  int rc = mfgpu::choose_kernel_and_plan(*desc, pk, bk, p->plan);
+  mfgpu_desc d = *desc;
+  d.mass_coefficient = nullptr;  // the plan is the Laplace operator's, with or without a mass term
+  int rc = mfgpu::choose_kernel_and_plan(d, pk, bk, p->plan);
   if (!rc && pk != mfgpu::PlaneKernel::none) rc = mfgpu::build_plane_records(p->plan, desc->constraint_mask);
   if (rc) {
     delete p;
@@ -1003,6 +1016,8 @@ int mfgpu_plan_create(const mfgpu_desc *desc, mfgpu_plan **out) {
 
 void mfgpu_plan_destroy(mfgpu_plan *p) { delete p; }
 
+size_t mfgpu_desc_size(void) { return sizeof(mfgpu_desc); }
+
 int mfgpu_suggest_renumbering(const mfgpu_desc *desc, uint32_t *new_index) {
   if (!desc || !new_index) {
     mfgpu::set_error("null argument");
@@ -1011,7 +1026,9 @@ int mfgpu_suggest_renumbering(const mfgpu_desc *desc, uint32_t *new_index) {
   mfgpu::Plan P;
   mfgpu::PlaneKernel pk;
   mfgpu::BatchKernel bk;
-  int rc = mfgpu::choose_kernel_and_plan(*desc, pk, bk, P);
+  mfgpu_desc d = *desc;
+  d.mass_coefficient = nullptr;  // (as mfgpu_plan_create)
+  int rc = mfgpu::choose_kernel_and_plan(d, pk, bk, P);
   if (rc) return rc;
   // batch-major: the dofs a batch owns alone, batch after batch (one contiguous run per batch: coalesced gathers and
   // stores of the cell loop), then the dofs several batches share in the order pass 2 walks them (grouped by the set

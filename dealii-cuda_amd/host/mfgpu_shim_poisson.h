@@ -62,6 +62,13 @@ public:
   explicit PoissonIntegrator(const DoFHandler<dim> &dof_handler) {
     check(mfgpu_integrator_create(&dof_handler.desc, &it), "mfgpu_integrator_create");
   }
+  // ... with a mass term: mass_coefficient = c at the quadrature points [n_cells * (p+1)^dim] (mfgpu_desc.mass_coefficient);
+  // the lift of create_right_hand_side then also subtracts int c phi_i u_b
+  PoissonIntegrator(const DoFHandler<dim> &dof_handler, const double *mass_coefficient) {
+    mfgpu_desc d = dof_handler.desc;
+    d.mass_coefficient = mass_coefficient;
+    check(mfgpu_integrator_create(&d, &it), "mfgpu_integrator_create");
+  }
   ~PoissonIntegrator() { mfgpu_integrator_destroy(it); }
   PoissonIntegrator(const PoissonIntegrator &) = delete;
   PoissonIntegrator &operator=(const PoissonIntegrator &) = delete;

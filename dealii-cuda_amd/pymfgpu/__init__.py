@@ -36,6 +36,7 @@ class Desc(C.Structure):
         ("constraint_weights", C.c_void_p), ("constrained_dofs", C.c_void_p),
         ("n_constrained", C.c_uint32), ("max_cells_per_batch", C.c_uint32), ("max_dofs_per_batch", C.c_uint32),
         ("kernel", C.c_uint32), ("cell_loop_segments", C.c_uint32), ("max_workgroups", C.c_uint32),
+        ("mass_coefficient", C.c_void_p),
     ]
 
 
@@ -63,6 +64,7 @@ SYMBOLS = [
     "mfgpu_integrator_create", "mfgpu_integrator_rhs", "mfgpu_integrator_l2_error", "mfgpu_integrator_error_points",
     "mfgpu_integrator_destroy",
     "mfgpu_vec_convert", "mfgpu_vec_copy_pairs_convert", "mfgpu_vec_chebyshev_start", "mfgpu_vec_chebyshev_update",
+    "mfgpu_desc_size",
 ]
 
 _lib = None
@@ -77,6 +79,8 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.mfgpu_last_error.restype = C.c_char_p
         L.mfgpu_create.argtypes = [C.POINTER(Desc), C.POINTER(C.c_void_p)]
+        L.mfgpu_desc_size.argtypes = []
+        L.mfgpu_desc_size.restype = C.c_size_t
         L.mfgpu_vmult.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mfgpu_vmult_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mfgpu_n_dofs.argtypes = [C.c_void_p]
@@ -288,6 +292,16 @@ class Mesh:
         )
         return out
 
+    def set_mass_coefficient(self, c):
+        """desc.mass_coefficient = c [n_cells * (p+1)^dim] in the mesh's number type (None: no mass term); the array is
+        kept alive by the mesh.  Objects created from self.desc afterwards carry the term."""
+        if c is None:
+            self._mass, self.desc.mass_coefficient = None, None
+            return
+        self._mass = np.ascontiguousarray(c, dtype=np_dtype(self.desc.number_type)).reshape(-1)
+        assert self._mass.size == self.n_cells * self.nd
+        self.desc.mass_coefficient = self._mass.ctypes.data
+
     def dof_coords(self):
         p = C.c_void_p()
         cnt = lib().mfgpu_mesh_dof_coords(self._h, C.byref(p))
@@ -326,8 +340,9 @@ class Mesh:
 def make_desc(dim, degree, n_dofs, loc2glob, JxW, inv_jac, coefficient, constrained,
               shape_values, shape_gradients, number_type=F64, constraint_mask=None,
               constraint_weights=None, quadrature_points=None, max_cells_per_batch=0, max_dofs_per_batch=0,
-              colored=False, kernel=0, cell_loop_segments=0, max_workgroups=0):
-    """Build a Desc from numpy arrays; returns (desc, keepalive list)."""
+              colored=False, kernel=0, cell_loop_segments=0, max_workgroups=0, mass_coefficient=None):
+    """Build a Desc from numpy arrays; returns (desc, keepalive list).  mass_coefficient: values of c at the quadrature
+    points [n_cells * (p+1)^dim] for the mass term int c u v, or None (the Laplace operator)."""
     dt = np_dtype(number_type)
     keep = []
 
@@ -365,6 +380,7 @@ def make_desc(dim, degree, n_dofs, loc2glob, JxW, inv_jac, coefficient, constrai
     d.kernel = kernel
     d.cell_loop_segments = cell_loop_segments
     d.max_workgroups = max_workgroups
+    d.mass_coefficient = ptr(mass_coefficient, dt)
     return d, keep
 
 
@@ -605,7 +621,8 @@ class Integrator:
         return (self.degree + 2) ** self.dim
 
     def rhs(self, dst, f=None, u_b=None, stream=None):
-        """dst = int phi_i f - int grad phi_i . a grad u_b; f: values at the quadrature points [n_cells * (p+1)^dim]"""
+        """dst = int phi_i f - int grad phi_i . a grad u_b (- int c phi_i u_b with a mass term in the description);
+        f: values at the quadrature points [n_cells * (p+1)^dim]"""
         _check(lib().mfgpu_integrator_rhs(self._h, _ptr(dst), None if f is None else _ptr(f),
                                           None if u_b is None else _ptr(u_b), stream))
 

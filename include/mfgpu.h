@@ -104,9 +104,29 @@ typedef struct mfgpu_desc {
   uint32_t max_workgroups;     /* cap on the resident workgroups of the persistent cell-loop launches (0 = as many
                                   as fit on the device): leaves room for other work on the GPU; also lets small
                                   meshes exercise the multi-batch loop of a workgroup                          */
+  const void *mass_coefficient; /* [n_cells * n^dim] values of c at the quadrature points (number_type), or NULL:
+                                   adds the mass term int c u v to the operator, A = sum_cells P^T C^T (K_cell + M_cell)
+                                   C P with M_cell[i][j] = sum_q phi_i(x_q) phi_j(x_q) c_q JxW_q on free rows, the
+                                   identity on constrained rows as before.  NULL = no mass term (the Laplace operator).
+                                   c is not checked for sign (a Helmholtz operator with c < 0 is the caller's business).
+                                   A pure mass matrix: coefficient = zeros plus mass_coefficient.  No reference
+                                   counterpart (LaplaceOperatorGpu has the stiffness term only; this is the value half
+                                   of FEEvaluationGpu, fee_gpu.cuh: evaluate / get_value / submit_value / integrate).
+                                   Carried by everything created from a description: mfgpu_create, mfgpu_level_create
+                                   (level operator and interface matrices), mfgpu_integrator_create (Dirichlet lift).
+                                   Ignored by mfgpu_plan_create and mfgpu_suggest_renumbering: the plan of a degree does
+                                   not depend on it, except that mfgpu_create serves p = 5, 6 in 3D with apply_batches_x
+                                   when the field is set.  Appended last: a caller that zeroes
+                                   the struct before filling it keeps today's operator.                                */
 } mfgpu_desc;
 
-/* mfgpu_desc.kernel (all variants compute the same operator; non-default ones exist for tests and measurements) */
+/* sizeof(mfgpu_desc) of the library: lets a binding check its mirror of the struct against this header */
+size_t mfgpu_desc_size(void);
+
+/* mfgpu_desc.kernel (all variants compute the same operator; non-default ones exist for tests and measurements).
+ * With a mass term every family has an instantiation except the plane kernels at p = 5, 6 (apply_planes4w, whose
+ * registers the extra plane does not fit) and MFGPU_KERNEL_PLANES_2W at p = 4 in double (it would spill): forcing
+ * one of them returns MFGPU_EUNSUPPORTED.                                                                            */
 #define MFGPU_KERNEL_AUTO 0
 #define MFGPU_KERNEL_PENCILS 1   /* apply_batches: a thread owns a 1D pencil, 2 workgroups per CU (2D; coloured mode)   */
 #define MFGPU_KERNEL_PENCILS_X 2 /* apply_batches_x: the same for 3 workgroups per CU (3D two-pass; hanging nodes)      */
@@ -119,8 +139,8 @@ typedef struct mfgpu_desc {
 
 /* laplace_operator_gpu.h:120-151 (reinit): copies the description to the device, builds the
  * batch plan, folds coefficient * J0^2 * JxW (general geometry: the symmetric coefficient * JxW * J^-1 J^-T per
- * quadrature point).  Uses the current HIP device.  Fails (MFGPU_EHIP) if no HIP device / kernel image is
- * available: there is no CPU fallback.                                                        */
+ * quadrature point) and, with mass_coefficient, the mass weight c * JxW.  Uses the current HIP device.  Fails
+ * (MFGPU_EHIP) if no HIP device / kernel image is available: there is no CPU fallback.        */
 int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out);
 
 /* laplace_operator_gpu.h:216-223: dst = A src.  dst, src: device vectors of n_dofs Numbers.
@@ -199,7 +219,8 @@ int mfgpu_suggest_renumbering(const mfgpu_desc *desc, uint32_t *new_index /* [n_
  * LaplaceOperatorGpu::compute_diagonal + get_diagonal_inverse (laplace_operator_gpu.h:401-429): writes
  * 1 / diag(A) into inv_diag[n_dofs] (device, operator's number type); the local diagonal of every cell
  * (DiagonalLocalOperator, :355-399) is distributed like a cell result, including the transposed hanging-node
- * resolution, constrained rows are set to 1 before the inversion (:412-414).                              */
+ * resolution, constrained rows are set to 1 before the inversion (:412-414).  With a mass term the local diagonal is
+ * K_ii + M_ii, M_ii = sum_q c_q JxW_q prod_d S[i_d][q_d]^2.                                                */
 int mfgpu_compute_inverse_diagonal(mfgpu_handle *h, void *inv_diag, void *stream);
 /* ConstraintHandlerGpu::set_constrained_values (constraint_handler_gpu.cu:126-137): vec[c] = value for every
  * constrained dof c of the description.                                                                   */
@@ -340,7 +361,8 @@ int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out);
  * f_qp: [n_cells * (p+1)^dim] values at the quadrature points, or NULL = RightHandSide<dim> (poisson_common.h:277-296,
  * which assumes the built-in coefficient).  u_b: read on every dof a cell references, constrained dofs included (unlike
  * vmult), hanging-node interpolated as in the cell loop; NULL = no lift.  a = the description's coefficient or the
- * built-in one, as mfgpu_create.  Asynchronous.                                                                   */
+ * built-in one, as mfgpu_create.  With mass_coefficient the lift is - int a grad phi_i . grad u_b - int c phi_i u_b;
+ * f_qp = NULL still means the built-in Poisson load, so a caller with a mass term normally passes f_qp.  Asynchronous. */
 int mfgpu_integrator_rhs(mfgpu_integrator *it, void *rhs, const void *f_qp, const void *u_b, void *stream);
 /* VectorTools::integrate_difference(..., QGauss(p+2), L2_norm), poisson.cu:277-292.  u in the operator's numbering;
  * entries of hanging dofs are not read (values come through loc2glob + hanging-node interpolation).  exact:
