@@ -112,9 +112,18 @@ struct mfgpu_handle {
   // `batches` the rest
   PlaneKernel planes = PlaneKernel::none;
   BatchKernel batches = BatchKernel::none;
-  uint32_t max_grid = 0;     // resident workgroups of the batch family
-  uint32_t max_grid_p = 0;   // ... of the plane family
-  uint32_t max_grid_ph = 0;  // ... of its <HN> instantiation (the plane batches of cells with a hanging-node mask)
+  // ... and their kernels, bound once by create_arrays (those of the handle's number type; a family the handle does
+  // not use stays unbound): the plane family's plain instantiation, its <HN> one (the plane batches of cells with a
+  // hanging-node mask), the batch family
+  enum { kPlain, kMasked, kBatch };
+  CellKernel<double> kernels_f64[3];
+  CellKernel<float> kernels_f32[3];
+  template <typename T>
+  CellKernel<T> &kernel(int which) {
+    if constexpr (std::is_same<T, double>::value) return kernels_f64[which];
+    else return kernels_f32[which];
+  }
+  uint32_t n_cus = 0, max_workgroups = 0;  // persistent grids: the chip's CUs, mfgpu_desc.max_workgroups (0: no cap)
   // profiling
   bool prof = false;
   EventTimer t_cells;  // around the cell loop
@@ -124,50 +133,31 @@ struct mfgpu_handle {
 
 namespace {
 
-// The only mapping from a kernel family to its launcher pair (mfgpu_kernels.h); hn selects the <HN> instantiation.
+// The only mapping from a kernel family to its F_bind (mfgpu_kernels.h): binds the instantiation (hn, sh) of the plane
+// family pk or, with PlaneKernel::none, of the batch family bk
 template <typename T>
-hipError_t family_configure(const mfgpu_handle *h, PlaneKernel k, bool hn, size_t *lds, int *blocks) {
+hipError_t bind_kernel(const mfgpu_handle *h, PlaneKernel pk, BatchKernel bk, bool hn, bool sh, CellKernel<T> *k) {
   const Plan &P = h->plan;
-  switch (k) {
-    case PlaneKernel::planes3: return p_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
-    case PlaneKernel::planes4: return q_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
-    default: return hipErrorInvalidValue;
-  }
+  const auto bind = pk == PlaneKernel::planes3 ? p_bind<T> : pk == PlaneKernel::planes4 ? q_bind<T>
+                    : bk == BatchKernel::batches ? apply_bind<T> : bk == BatchKernel::x ? x_bind<T>
+                    : bk == BatchKernel::g ? g_bind<T> : bk == BatchKernel::g2 ? g2_bind<T> : nullptr;
+  if (!bind) return hipErrorInvalidValue;
+  return bind(P.dim, P.n, hn, h->twopass, sh, h->d_mass.get() != nullptr, P.max_batch_dofs, k);
 }
+
+// batches [a.batch0, a.batch_end) less the hole, nbat of them, in a bound kernel: a persistent grid of as many
+// workgroups as fit on the chip (each loops over its batches)
 template <typename T>
-hipError_t family_configure(const mfgpu_handle *h, BatchKernel k, bool hn, size_t *lds, int *blocks) {
-  const Plan &P = h->plan;
-  switch (k) {
-    case BatchKernel::batches: return apply_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
-    case BatchKernel::x: return x_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
-    case BatchKernel::g: return g_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
-    case BatchKernel::g2: return g2_configure<T>(P.dim, P.n, hn, h->twopass, P.max_batch_dofs, lds, blocks);
-    default: return hipErrorInvalidValue;
+int launch_bound(mfgpu_handle *h, int which, const ApplyArgs<T> &a, uint32_t nbat, hipStream_t st) {
+  const CellKernel<T> &k = h->kernel<T>(which);
+  if (!k.launch[0]) {
+    set_error("cell-loop kernel not bound");
+    return MFGPU_EINVAL;
   }
-}
-template <typename T>
-hipError_t family_launch(const mfgpu_handle *h, PlaneKernel k, const ApplyArgs<T> &a, bool hn, uint32_t grid,
-                         hipStream_t st) {
-  const Plan &P = h->plan;
-  const double *S = h->S.data(), *Dt = h->Dt.data();
-  switch (k) {
-    case PlaneKernel::planes3: return p_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
-    case PlaneKernel::planes4: return q_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
-    default: return hipErrorInvalidValue;
-  }
-}
-template <typename T>
-hipError_t family_launch(const mfgpu_handle *h, BatchKernel k, const ApplyArgs<T> &a, bool hn, uint32_t grid,
-                         hipStream_t st) {
-  const Plan &P = h->plan;
-  const double *S = h->S.data(), *Dt = h->Dt.data();
-  switch (k) {
-    case BatchKernel::batches: return apply_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
-    case BatchKernel::x: return x_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
-    case BatchKernel::g: return g_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
-    case BatchKernel::g2: return g2_launch<T>(P.dim, P.n, hn, h->twopass, a, S, Dt, grid, st);
-    default: return hipErrorInvalidValue;
-  }
+  uint32_t grid = (uint32_t)(k.per_cu < 1 ? 1 : k.per_cu) * h->n_cus;
+  if (h->max_workgroups && h->max_workgroups < grid) grid = h->max_workgroups;
+  HIP_TRY(k.launch[a.add != 0](a, h->S.data(), h->Dt.data(), k.lds, nbat < grid ? nbat : grid, st));
+  return 0;
 }
 
 // symmetry of the 1D tables (see mfgpu_kernels.hip tab_at); also makes mirrored entries bit-equal
@@ -345,9 +335,10 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
       if ((rc = up(h->d_hnrec, P.pr_hn.data(), P.pr_hn.size()))) return rc;
       if ((rc = up(h->d_hn_slot, P.pr_hn_slot.data(), P.pr_hn_slot.size()))) return rc;
     }
-    // The shared form where the plan chose it (by bytes) and the kernel family has the instantiation: apply_planes3.
+    // The shared form where the plan chose it (by bytes) and the kernel family has the instantiation (kernel_exists).
     // The expanded arrays are then not uploaded at all.
-    h->shared_records = P.sh_use && h->planes == PlaneKernel::planes3 && !(d.flags & MFGPU_NO_SHARED_RECORDS);
+    h->shared_records = P.sh_use && !(d.flags & MFGPU_NO_SHARED_RECORDS) &&
+                        kernel_exists(h->planes, P.n, d.number_type, false, true, d.mass_coefficient != nullptr);
     const std::vector<uint32_t> &rd = h->shared_records ? P.sh_dofs : P.pr_dofs;
     const std::vector<uint32_t> &rx = h->shared_records ? P.sh_idx : P.pr_idx;
     if ((rc = up(h->d_bdofsp, rd.data(), rd.size()))) return rc;
@@ -415,33 +406,31 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     }
     HIP_TRY(hipDeviceSynchronize());
   }
-  // persistent grids: as many workgroups as fit on the chip (each loops over its batches)
-  int dev = 0, per_cu = 0;
+  // the kernels this handle launches, bound once
+  int dev = 0;
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipGetDeviceProperties(&prop, dev));
-  auto resident_grid = [&](int blocks_per_cu) {
-    const uint32_t g = (uint32_t)(blocks_per_cu < 1 ? 1 : blocks_per_cu) * (uint32_t)prop.multiProcessorCount;
-    return d.max_workgroups && d.max_workgroups < g ? d.max_workgroups : g;
-  };
+  h->n_cus = (uint32_t)prop.multiProcessorCount;
+  h->max_workgroups = d.max_workgroups;
   if (h->planes != PlaneKernel::none) {
-    HIP_TRY(family_configure<T>(h, h->planes, false, &h->lds, &per_cu));
-    h->max_grid_p = resident_grid(per_cu);
+    CellKernel<T> &plain = h->kernel<T>(mfgpu_handle::kPlain), &masked = h->kernel<T>(mfgpu_handle::kMasked);
+    HIP_TRY(bind_kernel<T>(h, h->planes, BatchKernel::none, false, h->shared_records, &plain));
+    h->lds = plain.lds;
     if (P.n_plain_plane_batches < P.n_plane_batches) {  // batches of masked cells: the <HN> instantiation
-      size_t lds_h = 0;
-      HIP_TRY(family_configure<T>(h, h->planes, true, &lds_h, &per_cu));
-      h->max_grid_ph = resident_grid(per_cu);
-      h->lds = std::max(h->lds, lds_h);
+      HIP_TRY(bind_kernel<T>(h, h->planes, BatchKernel::none, true, false, &masked));
+      h->lds = std::max(h->lds, masked.lds);
     }
   }
   if (h->batches == BatchKernel::none) return 0;
-  const hipError_t configure_batch_family = family_configure<T>(h, h->batches, h->hn, &h->lds, &per_cu);
-  if (h->lds > 160 * 1024) {  // (takes precedence over an error of the configure call)
+  CellKernel<T> &batch = h->kernel<T>(mfgpu_handle::kBatch);
+  const hipError_t bind_batch_family = bind_kernel<T>(h, PlaneKernel::none, h->batches, h->hn, false, &batch);
+  h->lds = batch.lds;
+  if (h->lds > 160 * 1024) {  // (takes precedence over an error of the bind call)
     set_error("batch needs more than 160 KiB of LDS; lower max_dofs_per_batch");
     return MFGPU_EINVAL;
   }
-  HIP_TRY(configure_batch_family);
-  h->max_grid = resident_grid(per_cu);
+  HIP_TRY(bind_batch_family);
   return 0;
 }
 
@@ -531,23 +520,19 @@ int launch_cells(mfgpu_handle *h, ApplyArgs<T> a, uint32_t b0, uint32_t b1, hipS
   if (b0 < nplain) {  // the batches of cells without a hanging-node mask (all batches on conforming meshes)
     a.batch0 = b0;
     a.batch_end = b1 < nplain ? b1 : nplain;
-    const uint32_t nbat = a.batch_end - a.batch0;
-    HIP_TRY(family_launch<T>(h, h->planes, a, false, nbat < h->max_grid_p ? nbat : h->max_grid_p, st));
+    if (const int rc = launch_bound<T>(h, mfgpu_handle::kPlain, a, a.batch_end - a.batch0, st)) return rc;
     b0 = a.batch_end;
   }
   if (b0 < npl && b0 < b1) {  // plane batches of cells WITH a mask
     a.batch0 = b0;
     a.batch_end = b1 < npl ? b1 : npl;
-    const uint32_t nbat = a.batch_end - a.batch0;
-    HIP_TRY(family_launch<T>(h, h->planes, a, true, nbat < h->max_grid_ph ? nbat : h->max_grid_ph, st));
+    if (const int rc = launch_bound<T>(h, mfgpu_handle::kMasked, a, a.batch_end - a.batch0, st)) return rc;
     b0 = a.batch_end;
   }
   if (b0 >= b1) return 0;
   a.batch0 = b0;
   a.batch_end = b1;
-  const uint32_t nrest = b1 - b0, grid = nrest < h->max_grid ? nrest : h->max_grid;
-  HIP_TRY(family_launch<T>(h, h->batches, a, h->hn, grid, st));
-  return 0;
+  return launch_bound<T>(h, mfgpu_handle::kBatch, a, b1 - b0, st);
 }
 
 template <typename T>
@@ -762,11 +747,8 @@ int handle_cells_two_ranges(mfgpu_handle *h, uint32_t b0, uint32_t b1, uint32_t 
     a.batch_end = c1;
     a.hole0 = b1;
     a.hole_len = c0 - b1;
-    const uint32_t nbat = (b1 - b0) + (c1 - c0);
     using T = typename std::remove_const<typename std::remove_pointer<decltype(a.src)>::type>::type;
-    const uint32_t cap = plain ? h->max_grid_p : h->max_grid_ph;
-    HIP_TRY(family_launch<T>(h, h->planes, a, !plain, nbat < cap ? nbat : cap, st));
-    return 0;
+    return launch_bound<T>(h, plain ? mfgpu_handle::kPlain : mfgpu_handle::kMasked, a, (b1 - b0) + (c1 - c0), st);
   };
   return h->number_type == MFGPU_F64 ? run(make_args<double>(h, dst, src, add)) : run(make_args<float>(h, dst, src, add));
 }

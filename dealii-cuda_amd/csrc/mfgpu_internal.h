@@ -165,12 +165,36 @@ void hn_cell_lines(unsigned mask, int n, std::vector<HnLine> (&lines)[3], std::v
 //   x                  apply_batches_x: 3D two-pass otherwise
 //   g / g2             apply_batches_g / apply_batches_g2: no MFGPU_UNIFORM_J0, 3D / 2D
 //   batches            apply_batches: 2D uniform-Jacobian, coloured-scatter mode, MFGPU_KERNEL_PENCILS
-// With a mass term (d.mass_coefficient) every family has an instantiation except apply_planes4w (p = 5, 6): those
-// degrees go to apply_batches_x by default and a forced plane family is refused (MFGPU_EUNSUPPORTED); so is
-// MFGPU_KERNEL_PLANES_2W at p = 4 in double, whose instantiation would spill.
+// Which instantiations a family has is kernel_exists' to say, and the planner asks it: where the plane kernel it
+// would pick lacks the one with a mass term (d.mass_coefficient), the degree goes to apply_batches_x by default and a
+// forced plane family is refused (MFGPU_EUNSUPPORTED); where it lacks the <HN> one, masked cells stay with
+// apply_batches_x.
 enum class PlaneKernel : uint8_t { none, planes3, planes4 };
 enum class BatchKernel : uint8_t { none, batches, x, g, g2 };
 int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk, Plan &plan);
+
+// THE statement of which cell-loop kernel instantiations exist, for n = degree + 1 dofs per direction, a number type
+// (MFGPU_F64 / MFGPU_F32) and the compile-time switches HN (hanging-node records / masks), SH (shared form of the
+// plane records) and MASS (mass term).  The planner (fallbacks and refusals), create_arrays (shared records) and the
+// kernel files (F_bind instantiates exactly these) all ask here.
+//   planes3  apply_planes3, n = 3..5: SH only without HN (hanging-node batches keep the expanded records)
+//   planes4  n = 3..5 apply_planes4: with or without HN, never SH, and no MASS at n = 5 in double (it would spill: 148 B
+//            per lane, <HN> 292); n = 6, 7 (planes4_wide) apply_planes4w: one wave per SIMD with four register planes
+//            live, so none of HN, SH, MASS -- a fifth plane spills
+//   batches, x, g, g2  the pencil families, n = 2..7: HN and MASS in every combination, never SH
+constexpr bool planes4_wide(int n) { return n >= 6; }
+constexpr bool kernel_exists(PlaneKernel k, int n, int number_type, bool hn, bool sh, bool mass) {
+  switch (k) {
+    case PlaneKernel::planes3: return n >= 3 && n <= 5 && !(sh && hn);
+    case PlaneKernel::planes4:
+      return planes4_wide(n) ? n <= 7 && !hn && !sh && !mass
+                             : n >= 3 && !sh && !(mass && n == 5 && number_type == MFGPU_F64);
+    default: return false;
+  }
+}
+constexpr bool kernel_exists(BatchKernel k, int n, int /*number_type*/, bool /*hn*/, bool sh, bool /*mass*/) {
+  return k != BatchKernel::none && n >= 2 && n <= 7 && !sh;
+}
 int build_plane_records(Plan &plan, const uint32_t *constraint_mask);
 // The shared form of the plane records (Plan::sh_*), derived from pr_dofs / pr_idx at the end of build_plane_records.
 // It is used when its bytes (distinct records + per-batch table) are at most kShareMaxFraction of the expanded

@@ -1,8 +1,10 @@
-// Kernel argument structs + launcher declarations (implemented in mfgpu_kernels.hip).
+// Kernel argument structs + launcher declarations (implemented in the mfgpu_kernels*.hip files).
 #ifndef MFGPU_KERNELS_H
 #define MFGPU_KERNELS_H
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "mfgpu_device.h"
 #include "mfgpu_internal.h"
@@ -70,40 +72,78 @@ inline Tables<T, n> make_tables(const double *S, const double *Dt) {
   return tab;
 }
 
-// sets a kernel's dynamic LDS size and returns its resident workgroups per CU
-inline hipError_t configure_kernel(const void *kernel, size_t lds, int block, int *blocks) {
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  return e == hipSuccess ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kernel, block, lds) : e;
+// One cell-loop kernel instantiation, bound for a handle (mfgpu_api.hip create_arrays; at most three per handle: the
+// plane family, its <HN> instantiation, the batch family).  The six families -- apply: apply_batches, x:
+// apply_batches_x, g / g2: apply_batches_g / _g2 (g2 reads a.tabS, a.tabDt instead of S, Dt), p: apply_planes3,
+// q: apply_planes4 / apply_planes4w -- each have ONE function F_bind, the only place that names the family's
+// instantiations: it maps (dim, n, hn, twopass, sh, mass) to the instantiation that kernel_exists (mfgpu_internal.h)
+// admits (else hipErrorInvalidValue) and hands it to bind_cell_kernel, which sets the dynamic-LDS attribute of
+// precisely the kernels whose launch entries it stores.  So what can be launched has been configured.
+// launch[add](a, S, Dt, lds, grid, st) runs batches [a.batch0, a.batch_end) with the 1D tables made from S, Dt.
+template <typename T>
+struct CellKernel {
+  size_t lds = 0;  // dynamic LDS bytes per workgroup (set first, also when binding fails)
+  int per_cu = 0;  // resident workgroups per CU (of launch[0])
+  hipError_t (*launch[2])(const ApplyArgs<T> &a, const double *S, const double *Dt, size_t lds, uint32_t grid,
+                          hipStream_t st) = {nullptr, nullptr};
+};
+
+// MakeTab: the kernel's by-value table argument from the host tables (make_tables, make_tables_eo), or nullptr
+template <typename T, int Block, auto K, auto MakeTab>
+hipError_t launch_cell_kernel(const ApplyArgs<T> &a, const double *S, const double *Dt, size_t lds, uint32_t grid,
+                              hipStream_t st) {
+  if constexpr (std::is_null_pointer_v<decltype(MakeTab)>)
+    hipLaunchKernelGGL(K, dim3(grid), dim3(Block), lds, st, a);
+  else
+    hipLaunchKernelGGL(K, dim3(grid), dim3(Block), lds, st, a, MakeTab(S, Dt));
+  return hipGetLastError();
 }
 
-// The six cell-loop kernel families, one launcher pair each (mfgpu_api.hip family_configure / family_launch):
-// F_configure sets the LDS attribute for (n, hn[, dim, twopass]) and returns the LDS bytes (written first) and the
-// workgroups per CU; F_launch runs batches [a.batch0, a.batch_end).  apply: apply_batches, x: apply_batches_x, g / g2:
-// apply_batches_g / _g2 (g2 reads a.tabS, a.tabDt instead of S, Dt), p / q: apply_planes3 / apply_planes4.
-#define MFGPU_CELL_LOOP_LAUNCHERS(F)                                                                               \
-  template <typename T>                                                                                            \
-  hipError_t F##_configure(int dim, int n, bool hn, bool twopass, uint32_t nb_max, size_t *lds, int *blocks);     \
-  template <typename T>                                                                                            \
-  hipError_t F##_launch(int dim, int n, bool hn, bool twopass, const ApplyArgs<T> &a, const double *S,            \
-                        const double *Dt, uint32_t grid, hipStream_t st);
-MFGPU_CELL_LOOP_LAUNCHERS(apply)
-MFGPU_CELL_LOOP_LAUNCHERS(x)
-MFGPU_CELL_LOOP_LAUNCHERS(g)
-MFGPU_CELL_LOOP_LAUNCHERS(g2)
-MFGPU_CELL_LOOP_LAUNCHERS(p)
-MFGPU_CELL_LOOP_LAUNCHERS(q)
-#undef MFGPU_CELL_LOOP_LAUNCHERS
-// (x, g, g2) dispatch of the run-time degree n = 2 .. 7 and hanging-node switch hn onto FN<n, T, HN>(...)
-#define MFGPU_SWITCH_N_HN(FN, ...)                                                                \
-  switch (n) {                                                                                    \
-    case 2: return hn ? FN<2, T, true>(__VA_ARGS__) : FN<2, T, false>(__VA_ARGS__);               \
-    case 3: return hn ? FN<3, T, true>(__VA_ARGS__) : FN<3, T, false>(__VA_ARGS__);               \
-    case 4: return hn ? FN<4, T, true>(__VA_ARGS__) : FN<4, T, false>(__VA_ARGS__);               \
-    case 5: return hn ? FN<5, T, true>(__VA_ARGS__) : FN<5, T, false>(__VA_ARGS__);               \
-    case 6: return hn ? FN<6, T, true>(__VA_ARGS__) : FN<6, T, false>(__VA_ARGS__);               \
-    case 7: return hn ? FN<7, T, true>(__VA_ARGS__) : FN<7, T, false>(__VA_ARGS__);               \
-    default: return hipErrorInvalidValue;                                                         \
+// K0 / K1: the add = 0 / add = 1 instantiations (the same kernel where ADD is the run-time field a.add)
+template <typename T, int Block, auto K0, auto K1, auto MakeTab>
+hipError_t bind_cell_kernel(size_t lds, CellKernel<T> *k) {
+  k->lds = lds;
+  for (const void *f : {(const void *)K1, (const void *)K0})
+    if (const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  k->launch[0] = launch_cell_kernel<T, Block, K0, MakeTab>;
+  k->launch[1] = launch_cell_kernel<T, Block, K1, MakeTab>;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&k->per_cu, (const void *)K0, Block, lds);
+}
+
+// run-time n = 2 .. 7 and switches -> f(std::integral_constant<int, n>, std::bool_constant<flag>...)
+template <typename F>
+hipError_t dispatch_flags(F &&f) { return f(); }
+template <typename F, typename... B>
+hipError_t dispatch_flags(F &&f, bool flag, B... rest) {
+  return dispatch_flags(
+      [&](auto... c) { return flag ? f(std::true_type{}, c...) : f(std::false_type{}, c...); }, rest...);
+}
+template <typename F, typename... B>
+hipError_t dispatch_instantiation(int n, F &&f, B... flags) {
+  auto at = [&](auto N) { return dispatch_flags([&](auto... c) { return f(N, c...); }, flags...); };
+  switch (n) {
+    case 2: return at(std::integral_constant<int, 2>{});
+    case 3: return at(std::integral_constant<int, 3>{});
+    case 4: return at(std::integral_constant<int, 4>{});
+    case 5: return at(std::integral_constant<int, 5>{});
+    case 6: return at(std::integral_constant<int, 6>{});
+    case 7: return at(std::integral_constant<int, 7>{});
+    default: return hipErrorInvalidValue;
   }
+}
+template <typename T>
+constexpr int number_type_of = sizeof(T) == 8 ? MFGPU_F64 : MFGPU_F32;
+
+#define MFGPU_CELL_LOOP_FAMILY(F)                                                                              \
+  template <typename T>                                                                                        \
+  hipError_t F##_bind(int dim, int n, bool hn, bool twopass, bool sh, bool mass, uint32_t nb_max, CellKernel<T> *k);
+MFGPU_CELL_LOOP_FAMILY(apply)
+MFGPU_CELL_LOOP_FAMILY(x)
+MFGPU_CELL_LOOP_FAMILY(g)
+MFGPU_CELL_LOOP_FAMILY(g2)
+MFGPU_CELL_LOOP_FAMILY(p)
+MFGPU_CELL_LOOP_FAMILY(q)
+#undef MFGPU_CELL_LOOP_FAMILY
 
 // pass 2, class-sorted structure-of-arrays form (mfgpu_pass2.hip)
 void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<uint32_t> &s_off,

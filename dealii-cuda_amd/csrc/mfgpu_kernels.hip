@@ -360,92 +360,17 @@ static size_t lds_bytes_t(uint32_t nb_max) {
          (size_t)CH * nd * sizeof(uint16_t);
 }
 
-template <int dim, int n, typename T, bool HN, bool TP>
-static hipError_t launch_k(const ApplyArgs<T> &a, const Tables<T, n> &tab, size_t lds, uint32_t grid, hipStream_t st) {
-  if (a.mass)
-    hipLaunchKernelGGL((apply_batches<dim, n, T, HN, TP, true>), dim3(grid), dim3(256), lds, st, a, tab);
-  else
-    hipLaunchKernelGGL((apply_batches<dim, n, T, HN, TP>), dim3(grid), dim3(256), lds, st, a, tab);
-  return hipGetLastError();
-}
-
-// dispatch over the run-time switches (hanging nodes, scatter mode)
-#define MFGPU_SWITCH(FN, ...)                                             \
-  (hn ? (twopass ? FN<dim, n, T, true, true>(__VA_ARGS__)                  \
-                 : FN<dim, n, T, true, false>(__VA_ARGS__))                \
-      : (twopass ? FN<dim, n, T, false, true>(__VA_ARGS__)                 \
-                 : FN<dim, n, T, false, false>(__VA_ARGS__)))
-
-template <int dim, int n, typename T>
-static hipError_t launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn,
-                           bool twopass, uint32_t grid, hipStream_t st) {
-  const Tables<T, n> tab = make_tables<T, n>(S, Dt);
-  const size_t lds = lds_bytes_t<dim, n, T>(a.nb_max);
-  return MFGPU_SWITCH(launch_k, a, tab, lds, grid, st);
-}
-
-template <int dim, int n, typename T, bool HN, bool TP>
-static hipError_t configure_k(size_t lds) {  // (the MASS instantiation too: same LDS, same register cap)
-  const hipError_t e = hipFuncSetAttribute((const void *)apply_batches<dim, n, T, HN, TP, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  return e != hipSuccess ? e
-                         : hipFuncSetAttribute((const void *)apply_batches<dim, n, T, HN, TP>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-template <int dim, int n, typename T>
-static hipError_t attributes_t(size_t lds) {
-  hipError_t e = hipSuccess;
-  for (int hn_ = 0; hn_ < 2 && e == hipSuccess; ++hn_)
-    for (int tp_ = 0; tp_ < 2 && e == hipSuccess; ++tp_) {
-      const bool hn = hn_, twopass = tp_;
-      e = MFGPU_SWITCH(configure_k, lds);
-    }
-  return e;
-}
-
-template <int dim, int n, typename T, bool HN, bool TP>
-static hipError_t occupancy_k(size_t lds, int *blocks) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, apply_batches<dim, n, T, HN, TP>, 256, lds);
-}
-// the attribute goes to all four instantiations, the occupancy is that of (hn, twopass)
-template <int dim, int n, typename T>
-static hipError_t configure_t(bool hn, bool twopass, uint32_t nb_max, size_t *lds_out, int *blocks) {
-  const size_t lds = lds_bytes_t<dim, n, T>(nb_max);
-  *lds_out = lds;
-  const hipError_t e = attributes_t<dim, n, T>(lds);
-  return e == hipSuccess ? MFGPU_SWITCH(occupancy_k, lds, blocks) : e;
-}
-
-#define MFGPU_DISPATCH(CALL)                                \
-  switch (dim * 10 + n) {                                   \
-    case 22: return CALL(2, 2);                             \
-    case 23: return CALL(2, 3);                             \
-    case 24: return CALL(2, 4);                             \
-    case 25: return CALL(2, 5);                             \
-    case 26: return CALL(2, 6);                             \
-    case 27: return CALL(2, 7);                             \
-    case 32: return CALL(3, 2);                             \
-    case 33: return CALL(3, 3);                             \
-    case 34: return CALL(3, 4);                             \
-    case 35: return CALL(3, 5);                             \
-    case 36: return CALL(3, 6);                             \
-    case 37: return CALL(3, 7);                             \
-    default: return hipErrorInvalidValue;                   \
-  }
-
 template <typename T>
-hipError_t apply_configure(int dim, int n, bool hn, bool twopass, uint32_t nb_max, size_t *lds, int *blocks) {
-#define CALL(D, N) configure_t<D, N, T>(hn, twopass, nb_max, lds, blocks)
-  MFGPU_DISPATCH(CALL)
-#undef CALL
-}
-
-template <typename T>
-hipError_t apply_launch(int dim, int n, bool hn, bool twopass, const ApplyArgs<T> &a, const double *S,
-                        const double *Dt, uint32_t grid, hipStream_t st) {
-#define CALL(D, N) launch_t<D, N, T>(a, S, Dt, hn, twopass, grid, st)
-  MFGPU_DISPATCH(CALL)
-#undef CALL
+hipError_t apply_bind(int dim, int n, bool hn, bool twopass, bool sh, bool mass, uint32_t nb_max, CellKernel<T> *k) {
+  if (dim != 2 && dim != 3) return hipErrorInvalidValue;
+  return dispatch_instantiation(n, [&](auto N, auto D3, auto HN, auto TP, auto SH, auto MASS) {
+    constexpr int n_ = N, dim_ = D3 ? 3 : 2;
+    if constexpr (kernel_exists(BatchKernel::batches, n_, number_type_of<T>, HN, SH, MASS)) {
+      constexpr auto K = apply_batches<dim_, n_, T, HN, TP, MASS>;
+      return bind_cell_kernel<T, 256, K, K, make_tables<T, n_>>(lds_bytes_t<dim_, n_, T>(nb_max), k);
+    } else
+      return hipErrorInvalidValue;
+  }, dim == 3, hn, twopass, sh, mass);
 }
 
 template <typename T>
@@ -540,9 +465,7 @@ hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
 }
 
 #define INST(T)                                                                                         \
-  template hipError_t apply_configure<T>(int, int, bool, bool, uint32_t, size_t *, int *);             \
-  template hipError_t apply_launch<T>(int, int, bool, bool, const ApplyArgs<T> &, const double *,       \
-                                      const double *, uint32_t, hipStream_t);                           \
+  template hipError_t apply_bind<T>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<T> *);      \
   template hipError_t orphan_launch<T>(T *, const T *, const uint32_t *, uint32_t, int, hipStream_t);   \
   template hipError_t coefficient_launch<T>(T *, const T *, size_t, int, hipStream_t);                  \
   template hipError_t fold_launch<T>(T *, const T *, const T *, const T *, const uint32_t *, uint32_t,  \

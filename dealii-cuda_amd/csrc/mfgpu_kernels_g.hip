@@ -443,33 +443,16 @@ static size_t g_lds_bytes(uint32_t nb_max) {
   return (size_t)nb_max * sizeof(double) + (size_t)(4 * CH * nd + n * n) * sizeof(T);
 }
 
-template <int n, typename T, bool HN>
-static hipError_t g_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
-  *lds = g_lds_bytes<n, T>(nb_max);
-  const hipError_t e = configure_kernel((const void *)apply_batches_g<n, T, HN, true>, *lds, 256, blocks);  // (MASS too)
-  return e == hipSuccess ? configure_kernel((const void *)apply_batches_g<n, T, HN>, *lds, 256, blocks) : e;
-}
-
-template <int n, typename T, bool HN>
-static hipError_t g_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
-  const Tables<T, n> tab = make_tables<T, n>(S, Dt);
-  const size_t lds = g_lds_bytes<n, T>(a.nb_max);
-  if (a.mass)
-    hipLaunchKernelGGL((apply_batches_g<n, T, HN, true>), dim3(grid), dim3(256), lds, st, a, tab);
-  else
-    hipLaunchKernelGGL((apply_batches_g<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
-  return hipGetLastError();
-}
-
 template <typename T>
-hipError_t g_configure(int, int n, bool hn, bool, uint32_t nb_max, size_t *lds, int *blocks) {
-  MFGPU_SWITCH_N_HN(g_configure_t, nb_max, lds, blocks)
-}
-
-template <typename T>
-hipError_t g_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
-                    hipStream_t st) {
-  MFGPU_SWITCH_N_HN(g_launch_t, a, S, Dt, grid, st)
+hipError_t g_bind(int, int n, bool hn, bool, bool sh, bool mass, uint32_t nb_max, CellKernel<T> *k) {
+  return dispatch_instantiation(n, [&](auto N, auto HN, auto SH, auto MASS) {
+    constexpr int n_ = N;
+    if constexpr (kernel_exists(BatchKernel::g, n_, number_type_of<T>, HN, SH, MASS)) {
+      constexpr auto K = apply_batches_g<n_, T, HN, MASS>;
+      return bind_cell_kernel<T, 256, K, K, make_tables<T, n_>>(g_lds_bytes<n_, T>(nb_max), k);
+    } else
+      return hipErrorInvalidValue;
+  }, hn, sh, mass);
 }
 
 template <typename T>
@@ -482,9 +465,7 @@ hipError_t fold_general_launch(T *M, const T *coef, const T *jxw, const T *jinv,
 }
 
 #define INST(T)                                                                                              \
-  template hipError_t g_configure<T>(int, int, bool, bool, uint32_t, size_t *, int *);                          \
-  template hipError_t g_launch<T>(int, int, bool, bool, const ApplyArgs<T> &, const double *, const double *,    \
-                                  uint32_t, hipStream_t);                                                      \
+  template hipError_t g_bind<T>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<T> *);                  \
   template hipError_t fold_general_launch<T>(T *, const T *, const T *, const T *, const uint32_t *, uint32_t, \
                                              uint32_t, hipStream_t);
 INST(double)

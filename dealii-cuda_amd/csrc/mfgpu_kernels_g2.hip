@@ -194,42 +194,22 @@ size_t g2_lds_bytes(uint32_t nb_max) {
   return (size_t)nb_max * sizeof(double) + ((size_t)nb_max + 4 * CH * nd + 3 * nd) * sizeof(T);
 }
 
-template <int n, typename T, bool HN>
-hipError_t g2_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
-  *lds = g2_lds_bytes<n, T>(nb_max);
-  const hipError_t e = configure_kernel((const void *)apply_batches_g2<n, T, HN, true>, *lds, 256, blocks);  // (MASS too)
-  return e == hipSuccess ? configure_kernel((const void *)apply_batches_g2<n, T, HN>, *lds, 256, blocks) : e;
-}
-
-template <int n, typename T, bool HN>
-hipError_t g2_launch_t(const ApplyArgs<T> &a, uint32_t grid, hipStream_t st) {
-  const size_t lds = g2_lds_bytes<n, T>(a.nb_max);
-  if (a.mass)
-    hipLaunchKernelGGL((apply_batches_g2<n, T, HN, true>), dim3(grid), dim3(256), lds, st, a);
-  else
-    hipLaunchKernelGGL((apply_batches_g2<n, T, HN>), dim3(grid), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
 }  // namespace
-
-template <typename T>
-hipError_t g2_configure(int, int n, bool hn, bool, uint32_t nb_max, size_t *lds, int *blocks) {
-  MFGPU_SWITCH_N_HN(g2_configure_t, nb_max, lds, blocks)
-}
 
 // (the 1D tables come from a.tabS / a.tabDt on the device, not from S, Dt)
 template <typename T>
-hipError_t g2_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *, const double *, uint32_t grid,
-                     hipStream_t st) {
-  MFGPU_SWITCH_N_HN(g2_launch_t, a, grid, st)
+hipError_t g2_bind(int, int n, bool hn, bool, bool sh, bool mass, uint32_t nb_max, CellKernel<T> *k) {
+  return dispatch_instantiation(n, [&](auto N, auto HN, auto SH, auto MASS) {
+    constexpr int n_ = N;
+    if constexpr (kernel_exists(BatchKernel::g2, n_, number_type_of<T>, HN, SH, MASS)) {
+      constexpr auto K = apply_batches_g2<n_, T, HN, MASS>;
+      return bind_cell_kernel<T, 256, K, K, nullptr>(g2_lds_bytes<n_, T>(nb_max), k);
+    } else
+      return hipErrorInvalidValue;
+  }, hn, sh, mass);
 }
-template hipError_t g2_configure<double>(int, int, bool, bool, uint32_t, size_t *, int *);
-template hipError_t g2_configure<float>(int, int, bool, bool, uint32_t, size_t *, int *);
-template hipError_t g2_launch<double>(int, int, bool, bool, const ApplyArgs<double> &, const double *, const double *,
-                                      uint32_t, hipStream_t);
-template hipError_t g2_launch<float>(int, int, bool, bool, const ApplyArgs<float> &, const double *, const double *,
-                                     uint32_t, hipStream_t);
+template hipError_t g2_bind<double>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<double> *);
+template hipError_t g2_bind<float>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<float> *);
 
 template <typename T>
 hipError_t fold_general2_launch(T *M, const T *coef, const T *jxw, const T *jinv, const uint32_t *order,

@@ -116,7 +116,7 @@ apply_planes3(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
     return l < bend ? (l >= hole0 ? l + hole_len : l) : x;
   };
   if (b >= hole0) b += hole_len;
-  static_assert(!(SH && HN), "hanging-node batches keep the expanded records");
+  static_assert(kernel_exists(PlaneKernel::planes3, n, number_type_of<T>, HN, SH, MASS), "no such instantiation");
   // SH: {dof base, dof-list record, index-run record} of a batch
   struct Meta {
     uint32_t base, drec, irec;
@@ -587,84 +587,19 @@ static size_t p_lds_bytes(bool hn) {
          (size_t)2 * (p_cells_per_wave(n) + 1) * p_cell_stride(n) * sizeof(T);
 }
 
-template <int n, typename T, bool MASS>
-static hipError_t p_configure_m(bool hn, size_t *lds, int *blocks) {
-  *lds = p_lds_bytes<n, T>(hn);
-  const void *f0 = hn ? (const void *)apply_planes3<n, T, false, true, false, MASS>
-                      : (const void *)apply_planes3<n, T, false, false, false, MASS>;
-  const void *f1 = hn ? (const void *)apply_planes3<n, T, true, true, false, MASS>
-                      : (const void *)apply_planes3<n, T, true, false, false, MASS>;
-  hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
-  if (e == hipSuccess && !hn) {  // the shared-record instantiations (same LDS; same occupancy, checked at build time)
-    e = hipFuncSetAttribute((const void *)apply_planes3<n, T, true, false, true, MASS>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void *)apply_planes3<n, T, false, false, true, MASS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
-  }
-  return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
-}
-// both the plain and the MASS instantiations get the attribute (a handle launches one set, chosen by a.massp); they
-// have the same LDS and the same occupancy (one wave per SIMD)
-template <int n, typename T>
-static hipError_t p_configure_t(bool hn, size_t *lds, int *blocks) {
-  const hipError_t e = p_configure_m<n, T, true>(hn, lds, blocks);
-  return e == hipSuccess ? p_configure_m<n, T, false>(hn, lds, blocks) : e;
-}
-
-template <int n, typename T, bool MASS>
-static hipError_t p_launch_m(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                             hipStream_t st) {
-  const size_t lds = p_lds_bytes<n, T>(hn);
-  const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
-  if (hn) {
-    if (a.add)
-      hipLaunchKernelGGL((apply_planes3<n, T, true, true, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-    else
-      hipLaunchKernelGGL((apply_planes3<n, T, false, true, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-  } else if (a.shtab) {  // shared form of the index records (chosen per plan: Plan::sh_use)
-    if (a.add)
-      hipLaunchKernelGGL((apply_planes3<n, T, true, false, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-    else
-      hipLaunchKernelGGL((apply_planes3<n, T, false, false, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-  } else {
-    if (a.add)
-      hipLaunchKernelGGL((apply_planes3<n, T, true, false, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-    else
-      hipLaunchKernelGGL((apply_planes3<n, T, false, false, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-  }
-  return hipGetLastError();
-}
-template <int n, typename T>
-static hipError_t p_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, bool hn, uint32_t grid,
-                             hipStream_t st) {
-  return a.massp ? p_launch_m<n, T, true>(a, S, Dt, hn, grid, st) : p_launch_m<n, T, false>(a, S, Dt, hn, grid, st);
-}
-
-#define P_SWITCH(FN, ...)                 \
-  switch (n) {                            \
-    case 3: return FN<3, T>(__VA_ARGS__); \
-    case 4: return FN<4, T>(__VA_ARGS__); \
-    case 5: return FN<5, T>(__VA_ARGS__); \
-    default: return hipErrorInvalidValue; \
-  }
 template <typename T>
-hipError_t p_configure(int, int n, bool hn, bool, uint32_t, size_t *lds, int *blocks) {
-  P_SWITCH(p_configure_t, hn, lds, blocks)
+hipError_t p_bind(int, int n, bool hn, bool, bool sh, bool mass, uint32_t, CellKernel<T> *k) {
+  return dispatch_instantiation(n, [&](auto N, auto HN, auto SH, auto MASS) {
+    constexpr int n_ = N;
+    if constexpr (kernel_exists(PlaneKernel::planes3, n_, number_type_of<T>, HN, SH, MASS))
+      return bind_cell_kernel<T, 64, apply_planes3<n_, T, false, HN, SH, MASS>, apply_planes3<n_, T, true, HN, SH, MASS>,
+                              make_tables_eo<T, n_>>(p_lds_bytes<n_, T>(HN), k);
+    else
+      return hipErrorInvalidValue;
+  }, hn, sh, mass);
 }
-template <typename T>
-hipError_t p_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
-                    hipStream_t st) {
-  P_SWITCH(p_launch_t, a, S, Dt, hn, grid, st)
-}
-#undef P_SWITCH
-
-template hipError_t p_configure<double>(int, int, bool, bool, uint32_t, size_t *, int *);
-template hipError_t p_configure<float>(int, int, bool, bool, uint32_t, size_t *, int *);
-template hipError_t p_launch<double>(int, int, bool, bool, const ApplyArgs<double> &, const double *, const double *,
-                                     uint32_t, hipStream_t);
-template hipError_t p_launch<float>(int, int, bool, bool, const ApplyArgs<float> &, const double *, const double *,
-                                    uint32_t, hipStream_t);
+template hipError_t p_bind<double>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<double> *);
+template hipError_t p_bind<float>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<float> *);
 
 // coefficient in plan cell order [cell][q] -> per batch [row r = y + n z][NT tasks = cell_in_batch * n + x]
 // (fixed record size n*n*NT per batch; the tasks of a ragged batch's missing cells stay zero)

@@ -48,7 +48,7 @@ namespace mfgpu {
 // MASS: the mass term int c u v (see apply_planes3): r += m .* v in S4, where the y-derivative part rewrites v in
 // place.  The batch's mass rows (A.massp, coefp's layout) are requested during S3, n rows per step between its
 // contractions under the same pins as the other spread loads, and consumed at the end of S4, three contraction passes
-// later.  apply_planes4 at n <= 4 and at n = 5 in float only: <5, double> spills with the extra plane and
+// later.  Not every instantiation has it (kernel_exists, mfgpu_internal.h): <5, double> spills with the extra plane and
 // apply_planes4w has four planes live in S4 -- the planner refuses or reroutes those (choose_kernel_and_plan).
 template <int n, typename T, bool ADD, bool HN, bool MASS = false>
 __device__ __forceinline__ void planes4_body(const ApplyArgs<T> &A, const TablesEO<T, n> &tab) {
@@ -503,99 +503,21 @@ apply_planes4w(const ApplyArgs<T> A, const TablesEO<T, n> tab) {
   planes4_body<n, T, ADD, false>(A, tab);
 }
 
-template <int n, typename T>
-static hipError_t q_configure_w(size_t *lds, int *blocks) {
-  *lds = q_lds_bytes<T>(n, false);
-  const void *f0 = (const void *)apply_planes4w<n, T, false>, *f1 = (const void *)apply_planes4w<n, T, true>;
-  const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
-  return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;
-}
-
-template <int n, typename T>
-static hipError_t q_launch_w(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
-  if (a.massp) return hipErrorInvalidValue;  // no MASS instantiation (the planner sends such descriptions elsewhere)
-  const size_t lds = q_lds_bytes<T>(n, false);
-  const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
-  if (a.add)
-    hipLaunchKernelGGL((apply_planes4w<n, T, true>), dim3(grid), dim3(64), lds, st, a, tab);
-  else
-    hipLaunchKernelGGL((apply_planes4w<n, T, false>), dim3(grid), dim3(64), lds, st, a, tab);
-  return hipGetLastError();
-}
-
-// <5, double, MASS> would spill (148 B per lane, <HN> 292): not instantiated, the planner refuses the request
-template <int n, typename T, bool MASS>
-constexpr bool q_has() { return !(MASS && n == 5 && sizeof(T) == 8); }
-
-template <int n, typename T, bool MASS>
-static hipError_t q_configure_m(bool hn, size_t *lds, int *blocks) {
-  *lds = q_lds_bytes<T>(n, hn);
-  if constexpr (!q_has<n, T, MASS>()) return hipSuccess; else {
-  const void *f0 = hn ? (const void *)apply_planes4<n, T, false, true, MASS> : (const void *)apply_planes4<n, T, false, false, MASS>;
-  const void *f1 = hn ? (const void *)apply_planes4<n, T, true, true, MASS> : (const void *)apply_planes4<n, T, true, false, MASS>;
-  const hipError_t e = hipFuncSetAttribute(f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds);
-  return e == hipSuccess ? configure_kernel(f0, *lds, 64, blocks) : e;  // occupancy: the ADD = false instantiation
-  }
-}
-// (both sets get the attribute; same LDS, same two waves per SIMD)
-template <int n, typename T>
-static hipError_t q_configure_t(bool hn, size_t *lds, int *blocks) {
-  const hipError_t e = q_configure_m<n, T, true>(hn, lds, blocks);
-  return e == hipSuccess ? q_configure_m<n, T, false>(hn, lds, blocks) : e;
-}
-
-template <int n, typename T, bool MASS>
-static hipError_t q_launch_m(bool hn, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
-                             hipStream_t st) {
-  if constexpr (!q_has<n, T, MASS>()) return hipErrorInvalidValue; else {
-  const size_t lds = q_lds_bytes<T>(n, hn);
-  const TablesEO<T, n> tab = make_tables_eo<T, n>(S, Dt);
-  if (hn) {
-    if (a.add)
-      hipLaunchKernelGGL((apply_planes4<n, T, true, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-    else
-      hipLaunchKernelGGL((apply_planes4<n, T, false, true, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-  } else {
-    if (a.add)
-      hipLaunchKernelGGL((apply_planes4<n, T, true, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-    else
-      hipLaunchKernelGGL((apply_planes4<n, T, false, false, MASS>), dim3(grid), dim3(64), lds, st, a, tab);
-  }
-  return hipGetLastError();
-  }
-}
-template <int n, typename T>
-static hipError_t q_launch_t(bool hn, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
-                             hipStream_t st) {
-  return a.massp ? q_launch_m<n, T, true>(hn, a, S, Dt, grid, st) : q_launch_m<n, T, false>(hn, a, S, Dt, grid, st);
-}
-
-// p = 5, 6: the one-wave-per-SIMD kernel, no <HN> instantiation
-#define Q_SWITCH(FN, ...)                                                     \
-  switch (n) {                                                                \
-    case 3: return FN##_t<3, T>(hn, __VA_ARGS__);                             \
-    case 4: return FN##_t<4, T>(hn, __VA_ARGS__);                             \
-    case 5: return FN##_t<5, T>(hn, __VA_ARGS__);                             \
-    case 6: return hn ? hipErrorInvalidValue : FN##_w<6, T>(__VA_ARGS__);     \
-    case 7: return hn ? hipErrorInvalidValue : FN##_w<7, T>(__VA_ARGS__);     \
-    default: return hipErrorInvalidValue;                                     \
-  }
 template <typename T>
-hipError_t q_configure(int, int n, bool hn, bool, uint32_t, size_t *lds, int *blocks) {
-  Q_SWITCH(q_configure, lds, blocks)
+hipError_t q_bind(int, int n, bool hn, bool, bool sh, bool mass, uint32_t, CellKernel<T> *k) {
+  return dispatch_instantiation(n, [&](auto N, auto HN, auto SH, auto MASS) {
+    constexpr int n_ = N;
+    if constexpr (!kernel_exists(PlaneKernel::planes4, n_, number_type_of<T>, HN, SH, MASS))
+      return hipErrorInvalidValue;
+    else if constexpr (planes4_wide(n_))
+      return bind_cell_kernel<T, 64, apply_planes4w<n_, T, false>, apply_planes4w<n_, T, true>, make_tables_eo<T, n_>>(
+          q_lds_bytes<T>(n_, false), k);
+    else
+      return bind_cell_kernel<T, 64, apply_planes4<n_, T, false, HN, MASS>, apply_planes4<n_, T, true, HN, MASS>,
+                              make_tables_eo<T, n_>>(q_lds_bytes<T>(n_, HN), k);
+  }, hn, sh, mass);
 }
-template <typename T>
-hipError_t q_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
-                    hipStream_t st) {
-  Q_SWITCH(q_launch, a, S, Dt, grid, st)
-}
-#undef Q_SWITCH
-
-template hipError_t q_configure<double>(int, int, bool, bool, uint32_t, size_t *, int *);
-template hipError_t q_configure<float>(int, int, bool, bool, uint32_t, size_t *, int *);
-template hipError_t q_launch<double>(int, int, bool, bool, const ApplyArgs<double> &, const double *, const double *,
-                                     uint32_t, hipStream_t);
-template hipError_t q_launch<float>(int, int, bool, bool, const ApplyArgs<float> &, const double *, const double *,
-                                    uint32_t, hipStream_t);
+template hipError_t q_bind<double>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<double> *);
+template hipError_t q_bind<float>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<float> *);
 
 }  // namespace mfgpu

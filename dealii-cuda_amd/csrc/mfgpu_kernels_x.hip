@@ -509,40 +509,19 @@ static size_t x_lds_bytes(uint32_t nb_max) {
   return (size_t)nb_max * sizeof(double) + (size_t)(3 * CH * nd + n * n) * sizeof(T) + 4 * 256 * sizeof(uint32_t);
 }
 
-template <int n, typename T, bool HN>
-static hipError_t x_configure_t(uint32_t nb_max, size_t *lds, int *blocks) {
-  *lds = x_lds_bytes<n, T>(nb_max);
-  // (the MASS instantiation too: same LDS, same register cap, hence the same occupancy)
-  const hipError_t e = configure_kernel((const void *)apply_batches_x<n, T, HN, true>, *lds, 256, blocks);
-  return e == hipSuccess ? configure_kernel((const void *)apply_batches_x<n, T, HN>, *lds, 256, blocks) : e;
-}
-
-template <int n, typename T, bool HN>
-static hipError_t x_launch_t(const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid, hipStream_t st) {
-  const Tables<T, n> tab = make_tables<T, n>(S, Dt);
-  const size_t lds = x_lds_bytes<n, T>(a.nb_max);
-  if (a.mass)
-    hipLaunchKernelGGL((apply_batches_x<n, T, HN, true>), dim3(grid), dim3(256), lds, st, a, tab);
-  else
-    hipLaunchKernelGGL((apply_batches_x<n, T, HN>), dim3(grid), dim3(256), lds, st, a, tab);
-  return hipGetLastError();
-}
-
 template <typename T>
-hipError_t x_configure(int, int n, bool hn, bool, uint32_t nb_max, size_t *lds, int *blocks) {
-  MFGPU_SWITCH_N_HN(x_configure_t, nb_max, lds, blocks)
+hipError_t x_bind(int, int n, bool hn, bool, bool sh, bool mass, uint32_t nb_max, CellKernel<T> *k) {
+  return dispatch_instantiation(n, [&](auto N, auto HN, auto SH, auto MASS) {
+    constexpr int n_ = N;
+    if constexpr (kernel_exists(BatchKernel::x, n_, number_type_of<T>, HN, SH, MASS)) {
+      constexpr auto K = apply_batches_x<n_, T, HN, MASS>;
+      return bind_cell_kernel<T, 256, K, K, make_tables<T, n_>>(x_lds_bytes<n_, T>(nb_max), k);
+    } else
+      return hipErrorInvalidValue;
+  }, hn, sh, mass);
 }
 
-template <typename T>
-hipError_t x_launch(int, int n, bool hn, bool, const ApplyArgs<T> &a, const double *S, const double *Dt, uint32_t grid,
-                    hipStream_t st) {
-  MFGPU_SWITCH_N_HN(x_launch_t, a, S, Dt, grid, st)
-}
-
-#define INST(T)                                                                                                    \
-  template hipError_t x_configure<T>(int, int, bool, bool, uint32_t, size_t *, int *);                              \
-  template hipError_t x_launch<T>(int, int, bool, bool, const ApplyArgs<T> &, const double *, const double *,        \
-                                  uint32_t, hipStream_t);
+#define INST(T) template hipError_t x_bind<T>(int, int, bool, bool, bool, bool, uint32_t, CellKernel<T> *);
 INST(double)
 INST(float)
 

@@ -930,13 +930,19 @@ int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk
     set_error("mfgpu_desc.kernel: this kernel family does not cover the description (see include/mfgpu.h)");
     return MFGPU_EUNSUPPORTED;
   }
-  // mass term: apply_planes4w (p = 5, 6) has no MASS instantiation -- a fifth plane of registers spills there -- so
-  // those degrees run in the pencil kernel, whose plan is the one of MFGPU_KERNEL_PENCILS_X
-  const bool mass_no_planes = d.mass_coefficient != nullptr && d.degree >= 5;
-  // ... and apply_planes4<5, double> would spill with it (p = 4 in double runs in apply_planes3)
-  const bool mass_no_planes4 = d.mass_coefficient != nullptr && d.degree == 4 && d.number_type == MFGPU_F64 &&
-                               d.kernel == MFGPU_KERNEL_PLANES_2W;
-  if ((mass_no_planes && want_planes) || mass_no_planes4) {
+  // which plane kernel: apply_planes4 on request, at p = 5, 6 (the only one that fits), and by default at p = 3 in
+  // double; apply_planes3 otherwise (p = 4: equal in double, faster in float)
+  const bool planes4 = d.kernel == MFGPU_KERNEL_PLANES_2W || d.degree >= 5 ||
+                       (d.kernel == MFGPU_KERNEL_AUTO && d.degree == 3 && d.number_type == MFGPU_F64);
+  const PlaneKernel plane_kind = planes4 ? PlaneKernel::planes4 : PlaneKernel::planes3;
+  const bool mass = d.mass_coefficient != nullptr;
+  auto plane_kernel_exists = [&](bool with_hn) {
+    return kernel_exists(plane_kind, d.degree + 1, d.number_type, with_hn, false, mass);
+  };
+  // mass term: where that plane kernel has no MASS instantiation (kernel_exists), the degree runs in the pencil kernel,
+  // whose plan is the one of MFGPU_KERNEL_PENCILS_X, and a request for the plane family is refused
+  const bool mass_without_planes = mass && pk_ok && !plane_kernel_exists(false);
+  if (mass_without_planes && want_planes) {
     set_error("mfgpu_desc.kernel: this plane kernel has no mass-term instantiation at this degree (apply_planes4w at "
               "p = 5, 6; apply_planes4 at p = 4 in double); use MFGPU_KERNEL_AUTO or MFGPU_KERNEL_PENCILS_X");
     return MFGPU_EUNSUPPORTED;
@@ -947,7 +953,7 @@ int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk
   // p = 3: apply_planes4 with two waves per SIMD (16 cells per wave) measures 9 % faster than the pencil kernel per
   // vmult (0.222 vs 0.243 ms at 10^7 dofs; profiles/r03_notes.md); p = 2: the pencil kernel stays ahead
   // (in float the pencil kernel is ahead at p = 3 on conforming meshes: 0.152 vs 0.179 ms)
-  bool planes = pk_ok && !mass_no_planes && (want_planes || (d.kernel == MFGPU_KERNEL_AUTO &&
+  bool planes = pk_ok && !mass_without_planes && (want_planes || (d.kernel == MFGPU_KERNEL_AUTO &&
                                      (d.degree >= 4 || (d.degree == 3 && (hn || d.number_type == MFGPU_F64)))));
   bool pencils_x = xk_ok && !planes && d.kernel != MFGPU_KERNEL_PENCILS;
   PlanLimits lim;
@@ -959,7 +965,7 @@ int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk
     lim.shared_max = lim.halo_stride - 1u;  // the list's last slot stays padding (idle tasks)
     lim.segregate_masked = hn;
     // cells with a hanging-node mask run in the plane kernel too (apply_planes3<HN>), in batches of their own
-    lim.masked_planes = hn && d.degree <= 4;  // (p = 5, 6: masked cells stay in the pencil kernel)
+    lim.masked_planes = hn && plane_kernel_exists(true);  // (else masked cells stay in the pencil kernel: p = 5, 6)
     lim.private_max = (uint32_t)p_priv_max(d.degree + 1);
   }
   // apply_batches_x unrolls 4 chunks at p=3 (64-cell batches = 13^3 dofs like p=4); everything else 3
@@ -977,11 +983,7 @@ int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk
     pencils_x = plan.n_plane_batches < nbat;  // the masked cells' batches
     if (plan.n_plane_batches == 0) planes = false;
   }
-  // which plane kernel: apply_planes4 on request, at p = 5, 6 (the only one that fits), and by default at p = 3 in
-  // double; apply_planes3 otherwise (p = 4: equal in double, faster in float)
-  const bool planes4 = d.kernel == MFGPU_KERNEL_PLANES_2W || d.degree >= 5 ||
-                       (d.kernel == MFGPU_KERNEL_AUTO && d.degree == 3 && d.number_type == MFGPU_F64);
-  pk = !planes ? PlaneKernel::none : planes4 ? PlaneKernel::planes4 : PlaneKernel::planes3;
+  pk = planes ? plane_kind : PlaneKernel::none;
   bk = pencils_x ? BatchKernel::x : general ? (d.dim == 2 ? BatchKernel::g2 : BatchKernel::g)
                                    : planes ? BatchKernel::none : BatchKernel::batches;
   assert(rc || (pk != PlaneKernel::none) == (plan.n_plane_batches > 0));
