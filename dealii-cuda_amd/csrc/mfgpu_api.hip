@@ -78,6 +78,12 @@ struct mfgpu_handle {
   // mass term (mfgpu_desc.mass_coefficient; empty without): c * JxW in plan cell order, and for the plane batches
   // again in d_coefp's layout
   DeviceArray<void> d_mass, d_massp;
+  // MFGPU_UPDATABLE_COEFFICIENTS: what a re-fold reads stays on the device (empty without the flag) -- JxW, inv_jac and
+  // the cell order, and for plane plans the cell -> (batch, position in the batch) tables of the relayout
+  bool updatable = false;
+  FoldGeometry geo;
+  DeviceArray<uint32_t> d_cell_batch, d_cell_pos;
+  size_t n_plane_cells = 0;  // the plane batches' cells (they come first in plan order)
   DeviceArray<uint32_t> d_cmask, d_orphans;
   DeviceArray<void> d_hnw;
   DeviceArray<uint32_t> d_constrained;  // constrained dof list (set_constrained_values)
@@ -267,6 +273,28 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
   return 0;
 }
 
+// d_coef -> d_coefp and / or d_mass -> d_massp for the plane batches (set-up and mfgpu_update_coefficients)
+template <typename T>
+int relayout_planes(mfgpu_handle *h, const uint32_t *cell_batch, const uint32_t *cell_pos, bool coef, bool mass,
+                    hipStream_t st) {
+  const size_t total = h->n_plane_cells * (size_t)h->nd;
+  if (coef)
+    HIP_TRY(relayout_coef_launch<T>(h->d_coefp.as<T>(), h->d_coef.as<const T>(), cell_batch, cell_pos, total, h->n, st));
+  if (mass)
+    HIP_TRY(relayout_coef_launch<T>(h->d_massp.as<T>(), h->d_mass.as<const T>(), cell_batch, cell_pos, total, h->n, st));
+  return 0;
+}
+
+// mfgpu_update_coefficients: the set-up's folds again, from device arrays, into the handle's existing arrays
+template <typename T>
+int update_typed(mfgpu_handle *h, const void *coef, const void *mass, hipStream_t st) {
+  const FoldInputs<T> in = h->geo.inputs<T>();
+  if (coef) HIP_TRY(fold_coefficient_launch<T>(h->d_coef.as<T>(), (const T *)coef, in, st));
+  if (mass) HIP_TRY(fold_mass_launch<T>(h->d_mass.as<T>(), (const T *)mass, in, st));
+  if (h->planes == PlaneKernel::none) return 0;
+  return relayout_planes<T>(h, h->d_cell_batch.get(), h->d_cell_pos.get(), coef != nullptr, mass != nullptr, st);
+}
+
 template <typename T>
 int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
   const Plan &P = h->plan;
@@ -366,18 +394,25 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     for (size_t i = 0; i < w.size(); ++i) w[i] = (T)d.constraint_weights[i];
     if ((rc = up(h->d_hnw, w.data(), w.size() * sizeof(T)))) return rc;
   }
-  // coefficient (given, or evaluated on the device from the quadrature points), then folded
-  DeviceArray<T> metric;
-  if ((rc = fold_coefficient<T>(metric, d.coefficient, d.quadrature_points, d.JxW, d.inv_jac, P.cell_order.data(), P.dim,
-                                (uint32_t)ncell, (uint32_t)nd, general)))
+  // coefficient (given, or evaluated on the device from the quadrature points), then folded; the folds' other inputs
+  // are temporaries unless the handle is updatable
+  FoldGeometry geo;
+  if ((rc = geo.upload(d.JxW, d.inv_jac, P.cell_order.data(), P.dim, (uint32_t)ncell, (uint32_t)nd, general,
+                       d.number_type)))
     return rc;
+  DeviceArray<T> metric;
+  if ((rc = fold_coefficient<T>(metric, d.coefficient, d.quadrature_points, geo.inputs<T>()))) return rc;
   h->d_coef = std::move(metric);
   acct += h->d_coef.bytes();
   if (d.mass_coefficient) {
     DeviceArray<T> mass;
-    if ((rc = fold_mass<T>(mass, d.mass_coefficient, d.JxW, P.cell_order.data(), (uint32_t)ncell, (uint32_t)nd))) return rc;
+    if ((rc = fold_mass<T>(mass, d.mass_coefficient, geo.inputs<T>()))) return rc;
     h->d_mass = std::move(mass);
     acct += h->d_mass.bytes();
+  }
+  if (h->updatable) {
+    acct += geo.bytes();
+    h->geo = std::move(geo);
   }
   if (h->planes != PlaneKernel::none) {
     // the folded coefficient again, per batch [row y + n z][task]: the layout of stage B of apply_planes3
@@ -396,15 +431,18 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     if ((rc = t_cp.upload(cp.data(), ncell_p))) return rc;
     if ((rc = h->d_coefp.alloc(total * sizeof(T), true))) return rc;
     acct += h->d_coefp.bytes();
-    HIP_TRY(relayout_coef_launch<T>(h->d_coefp.as<T>(), h->d_coef.as<const T>(), t_cb.get(), t_cp.get(), ncell_p * nd, n,
-                                    nullptr));
+    h->n_plane_cells = ncell_p;
     if (d.mass_coefficient) {  // the mass weight in the same layout (d_mass stays: diagonal, pencil batches)
       if ((rc = h->d_massp.alloc(total * sizeof(T), true))) return rc;
       acct += h->d_massp.bytes();
-      HIP_TRY(relayout_coef_launch<T>(h->d_massp.as<T>(), h->d_mass.as<const T>(), t_cb.get(), t_cp.get(), ncell_p * nd,
-                                      n, nullptr));
     }
+    if ((rc = relayout_planes<T>(h, t_cb.get(), t_cp.get(), true, d.mass_coefficient != nullptr, nullptr))) return rc;
     HIP_TRY(hipDeviceSynchronize());
+    if (h->updatable) {
+      acct += t_cb.bytes() + t_cp.bytes();
+      h->d_cell_batch = std::move(t_cb);
+      h->d_cell_pos = std::move(t_cp);
+    }
   }
   // the kernels this handle launches, bound once
   int dev = 0;
@@ -803,6 +841,7 @@ int mfgpu_create(const mfgpu_desc *desc, mfgpu_handle **out) {
   h->hn = hn;
   h->twopass = !(d.flags & MFGPU_COLORED_SCATTER);
   h->no_shared_records = (d.flags & MFGPU_NO_SHARED_RECORDS) != 0;
+  h->updatable = (d.flags & MFGPU_UPDATABLE_COEFFICIENTS) != 0;
   const int nn = h->n * h->n;
   std::vector<double> sv(nn), sg(nn);
   for (int i = 0; i < nn; ++i) {
@@ -854,6 +893,29 @@ int mfgpu_vmult_add(mfgpu_handle *h, void *dst, const void *src, void *stream) {
   }
   return h->number_type == MFGPU_F64 ? vmult_typed<double>(h, dst, src, (hipStream_t)stream, 1)
                                      : vmult_typed<float>(h, dst, src, (hipStream_t)stream, 1);
+}
+
+int mfgpu_update_coefficients(mfgpu_handle *h, const void *coefficient_dev, const void *mass_coefficient_dev,
+                              void *stream) {
+  if (!h) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  if (!h->updatable) {
+    set_error("mfgpu_update_coefficients: the handle was created without MFGPU_UPDATABLE_COEFFICIENTS");
+    return MFGPU_EINVAL;
+  }
+  if (!coefficient_dev && !mass_coefficient_dev) {
+    set_error("mfgpu_update_coefficients: coefficient_dev and mass_coefficient_dev are both NULL");
+    return MFGPU_EINVAL;
+  }
+  if (mass_coefficient_dev && !h->d_mass.get()) {
+    set_error("mfgpu_update_coefficients: the handle was created without a mass term (its kernels have no mass "
+              "instantiation bound); create it with mass_coefficient");
+    return MFGPU_EINVAL;
+  }
+  return h->number_type == MFGPU_F64 ? update_typed<double>(h, coefficient_dev, mass_coefficient_dev, (hipStream_t)stream)
+                                     : update_typed<float>(h, coefficient_dev, mass_coefficient_dev, (hipStream_t)stream);
 }
 
 uint32_t mfgpu_n_dofs(const mfgpu_handle *h) { return h ? h->plan.n_dofs : 0; }

@@ -10,6 +10,7 @@
 //   rhs:   cell kernel -> per-cell local vectors (scratch) -> per-dof gather over a host-built CSR (dof -> cell-major
 //          local index, ascending), constrained and unreferenced dofs 0.  No atomics: bitwise repeatable.
 //   error: cell kernel -> squared cell errors -> the two-stage fixed-order reduction of mfgpu_vec_dot.
+//   evaluate: cell kernel -> values and real-space gradients of a field at the quadrature points, cell-major.
 // Geometry at the (p+2)^dim error points is interpolated from the description's QGauss(p+1) points with the 1D Lagrange
 // basis on those points (values and derivatives): exact for mappings of degree <= p per direction (affine cells,
 // MappingQ1, i.e. all mesh stand-ins).
@@ -61,6 +62,9 @@ struct IntArgs {
   const double *u, *exact;
   double *per_cell;
   double *points;  // error_points
+  // evaluate
+  const double *jinv;     // uniform: [n_cells] J0^-1; general: [n_cells * N^dim * dim * dim] row-major J^-1 per point
+  double *values, *grads;  // [n_cells * N^dim], [n_cells * N^dim * dim]; either may be nullptr
   uint32_t n_cells;
 };
 
@@ -390,7 +394,53 @@ __global__ void __launch_bounds__(64) error_points_kernel(IntArgs a) {
   }
 }
 
-enum Which { RHS, L2, POINTS };
+// u and grad u at the quadrature points (the read_dof_values + evaluate + get_value / get_gradient half of
+// FEEvaluationGpu, fee_gpu.cuh:155-281): nodal values through loc2glob, hanging-node interpolation, sum-factorised
+// values and reference gradients, then grad_x = J^-T grad_xi per point (uniform: J0^-1 grad_xi).  Every output entry
+// is written by exactly one thread.
+template <int dim, int N>
+__global__ void __launch_bounds__(64) evaluate_cell_kernel(IntArgs a) {
+  constexpr int ND = cpow(N, dim);
+  using TB = Tab<N>;
+  __shared__ double tab[TB::size], A[ND], G[dim * ND], T1[ND], T2[ND];
+  const uint32_t c = blockIdx.x;
+  const size_t c0 = (size_t)c * ND;
+  load_tab<N>(tab, a.tab);
+  for (int i = threadIdx.x; i < ND; i += 64) A[i] = a.u[a.loc2glob[c0 + i]];
+  const unsigned mask = a.cmask ? a.cmask[c] : 0u;
+  if (mask) hn_resolve<dim, N, false>(A, mask, tab + TB::W);
+  const double *S = tab + TB::SE, *D = tab + TB::GE;
+  if (a.values) {
+    tensor<dim, N, N>(A, G, S, S, S, T1, T2);
+    for (int q = threadIdx.x; q < ND; q += 64) a.values[c0 + q] = G[q];
+  }
+  if (!a.grads) return;
+#pragma unroll
+  for (int e = 0; e < dim; ++e) tensor<dim, N, N>(A, G + e * ND, e == 0 ? D : S, e == 1 ? D : S, e == 2 ? D : S, T1, T2);
+  const double j0 = a.general ? 0.0 : a.jinv[c];
+  for (int q = threadIdx.x; q < ND; q += 64) {
+    double g[dim], r[dim];
+#pragma unroll
+    for (int e = 0; e < dim; ++e) g[e] = G[e * ND + q];
+    if (!a.general) {
+#pragma unroll
+      for (int k = 0; k < dim; ++k) r[k] = j0 * g[k];
+    } else {
+      const double *J = a.jinv + (c0 + q) * (dim * dim);  // J^-1[e][k] = d xi_e / d x_k
+#pragma unroll
+      for (int k = 0; k < dim; ++k) {
+        double s = 0;
+#pragma unroll
+        for (int e = 0; e < dim; ++e) s = fma(J[e * dim + k], g[e], s);
+        r[k] = s;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < dim; ++k) a.grads[(c0 + q) * dim + k] = r[k];
+  }
+}
+
+enum Which { RHS, L2, POINTS, EVAL };
 
 template <int dim, int N>
 hipError_t launch_dn(Which w, const IntArgs &a, hipStream_t st) {
@@ -398,6 +448,7 @@ hipError_t launch_dn(Which w, const IntArgs &a, hipStream_t st) {
   if (w == RHS) hipLaunchKernelGGL((rhs_cell_kernel<dim, N>), grid, block, 0, st, a);
   if (w == L2) hipLaunchKernelGGL((l2_error_kernel<dim, N>), grid, block, 0, st, a);
   if (w == POINTS) hipLaunchKernelGGL((error_points_kernel<dim, N>), grid, block, 0, st, a);
+  if (w == EVAL) hipLaunchKernelGGL((evaluate_cell_kernel<dim, N>), grid, block, 0, st, a);
   return hipGetLastError();
 }
 
@@ -465,6 +516,10 @@ struct mfgpu_integrator {
   DeviceArray<uint32_t> d_l2g, d_cmask, d_off, d_idx;
   DeviceArray<double> d_tab, d_qpts, d_jxw, d_metric, d_mass;
   DeviceArray<double> d_local, d_err, d_ones;
+  // MFGPU_UPDATABLE_COEFFICIENTS: inv_jac and the (identity) cell order of the folds stay on the device -- what
+  // mfgpu_integrator_update_coefficients and the gradients of mfgpu_integrator_evaluate read (JxW: d_jxw)
+  bool updatable = false;
+  FoldGeometry geo;
 };
 
 void mfgpu_integrator_destroy(mfgpu_integrator *it) { delete it; }
@@ -525,15 +580,19 @@ static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
   std::vector<double> ones(nc, 1.0);
   if ((rc = it->d_ones.upload(ones.data(), nc))) return rc;
   // coefficient (given, or evaluated from the quadrature points) folded with JxW and the inverse Jacobian by the
-  // operator's own set-up (cell order = identity); it uploads the quadrature points and JxW again as its temporaries
-  // rather than take the resident d_qpts / d_jxw
+  // operator's own set-up (cell order = identity, JxW = the resident d_jxw); it uploads the quadrature points again as
+  // its temporary rather than take the resident d_qpts
   std::vector<uint32_t> order(nc);
   for (size_t c = 0; c < nc; ++c) order[c] = (uint32_t)c;
-  if ((rc = fold_coefficient<double>(it->d_metric, d.coefficient, d.quadrature_points, d.JxW, d.inv_jac, order.data(),
-                                     dim, (uint32_t)nc, (uint32_t)nd, it->general)))
+  it->updatable = (d.flags & MFGPU_UPDATABLE_COEFFICIENTS) != 0;
+  FoldGeometry geo;
+  if ((rc = geo.upload(nullptr, d.inv_jac, order.data(), dim, (uint32_t)nc, (uint32_t)nd, it->general, MFGPU_F64)))
     return rc;
-  return d.mass_coefficient ? fold_mass<double>(it->d_mass, d.mass_coefficient, d.JxW, order.data(), (uint32_t)nc, (uint32_t)nd)
-                            : 0;
+  const FoldInputs<double> in = geo.inputs<double>(it->d_jxw.get());
+  if ((rc = fold_coefficient<double>(it->d_metric, d.coefficient, d.quadrature_points, in))) return rc;
+  if (d.mass_coefficient && (rc = fold_mass<double>(it->d_mass, d.mass_coefficient, in))) return rc;
+  if (it->updatable) it->geo = std::move(geo);
+  return 0;
 }
 
 int mfgpu_integrator_create(const mfgpu_desc *desc, mfgpu_integrator **out) {
@@ -642,5 +701,53 @@ int mfgpu_integrator_error_points(mfgpu_integrator *it, void *points, void *stre
   IntArgs a = base_args(it);
   a.points = (double *)points;
   HIP_TRY(launch(it->dim, it->n, POINTS, a, (hipStream_t)stream));
+  return 0;
+}
+
+int mfgpu_integrator_update_coefficients(mfgpu_integrator *it, const void *coefficient_dev,
+                                         const void *mass_coefficient_dev, void *stream) {
+  if (!it) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  if (!it->updatable) {
+    set_error("mfgpu_integrator_update_coefficients: the integrator was created without MFGPU_UPDATABLE_COEFFICIENTS");
+    return MFGPU_EINVAL;
+  }
+  if (!coefficient_dev && !mass_coefficient_dev) {
+    set_error("mfgpu_integrator_update_coefficients: coefficient_dev and mass_coefficient_dev are both NULL");
+    return MFGPU_EINVAL;
+  }
+  if (mass_coefficient_dev && !it->d_mass.get()) {
+    set_error("mfgpu_integrator_update_coefficients: the integrator was created without a mass term");
+    return MFGPU_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const FoldInputs<double> in = it->geo.inputs<double>(it->d_jxw.get());
+  if (coefficient_dev) HIP_TRY(fold_coefficient_launch<double>(it->d_metric.get(), (const double *)coefficient_dev, in, st));
+  if (mass_coefficient_dev) HIP_TRY(fold_mass_launch<double>(it->d_mass.get(), (const double *)mass_coefficient_dev, in, st));
+  return 0;
+}
+
+int mfgpu_integrator_evaluate(mfgpu_integrator *it, const void *u, void *values_qp, void *gradients_qp, void *stream) {
+  if (!it || !u) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  if (!values_qp && !gradients_qp) {
+    set_error("mfgpu_integrator_evaluate: values_qp and gradients_qp are both NULL");
+    return MFGPU_EINVAL;
+  }
+  if (gradients_qp && !it->updatable) {
+    set_error("mfgpu_integrator_evaluate: gradients need inv_jac on the device; create the integrator with "
+              "MFGPU_UPDATABLE_COEFFICIENTS");
+    return MFGPU_EINVAL;
+  }
+  IntArgs a = base_args(it);
+  a.u = (const double *)u;
+  a.jinv = it->geo.jinv.as<const double>();
+  a.values = (double *)values_qp;
+  a.grads = (double *)gradients_qp;
+  HIP_TRY(launch(it->dim, it->n, EVAL, a, (hipStream_t)stream));
   return 0;
 }

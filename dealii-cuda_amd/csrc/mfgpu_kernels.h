@@ -176,19 +176,57 @@ hipError_t fold_launch(T *c, const T *coef, const T *jxw, const T *j0, const uin
                        uint32_t n_cells, uint32_t nd, hipStream_t st);
 template <typename T>
 hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st);
-// Set-up of the mass weight, synchronised on return: out[pos * nd + q] = c[cell][q] * JxW[cell][q] for the cell at plan
-// position pos (JxW carries the determinant on every geometry path)
+// What a fold of the coefficient or of the mass weight reads besides the coefficient itself, on the device: JxW
+// [n_cells * nd], inv_jac (one scalar per cell, or with `general` the full J^-1 per point), and the plan's cell order
+// (plan position -> caller cell).  Temporaries of the set-up, or resident in a handle created with
+// MFGPU_UPDATABLE_COEFFICIENTS (FoldGeometry).
 template <typename T>
-int fold_mass(DeviceArray<T> &out, const void *mass_coefficient, const void *JxW, const uint32_t *cell_order,
-              uint32_t n_cells, uint32_t nd);
+struct FoldInputs {
+  const T *jxw = nullptr, *jinv = nullptr;
+  const uint32_t *order = nullptr;
+  int dim = 0;
+  uint32_t n_cells = 0, nd = 0;
+  bool general = false;
+  size_t metric_entries() const { return (size_t)n_cells * nd * (general ? (dim == 3 ? 6 : 3) : 1); }
+};
+// The folds themselves, asynchronous on st, no allocation: the one code path of the set-up and of
+// mfgpu_*_update_coefficients.  coef, c: device arrays [n_cells * nd] in the caller's cell order.
+//   metric: per point the scalar a J0^2 JxW, or with `general` the symmetric a JxW J^-1 J^-T (6 entries in 3D, 3 in 2D)
+//   mass:   out[pos * nd + q] = c[cell][q] * JxW[cell][q] for the cell at plan position pos
+template <typename T>
+hipError_t fold_coefficient_launch(T *out, const T *coef, const FoldInputs<T> &in, hipStream_t st);
+template <typename T>
+hipError_t fold_mass_launch(T *out, const T *c, const FoldInputs<T> &in, hipStream_t st);
+// Owner of the device copies behind a FoldInputs (the operator's number type; JxW may stay empty where the owner has
+// it resident already)
+struct FoldGeometry {
+  DeviceArray<void> jxw, jinv;
+  DeviceArray<uint32_t> order;
+  int dim = 0;
+  uint32_t n_cells = 0, nd = 0;
+  bool general = false;
+  int upload(const void *JxW, const void *inv_jac, const uint32_t *cell_order, int dim_, uint32_t n_cells_, uint32_t nd_,
+             bool general_, int number_type);
+  size_t bytes() const { return jxw.bytes() + jinv.bytes() + order.bytes(); }
+  template <typename T>
+  FoldInputs<T> inputs(const T *jxw_resident = nullptr) const {
+    FoldInputs<T> in;
+    in.jxw = jxw_resident ? jxw_resident : jxw.as<const T>();
+    in.jinv = jinv.as<const T>();
+    in.order = order.get();
+    in.dim = dim, in.n_cells = n_cells, in.nd = nd, in.general = general;
+    return in;
+  }
+};
+// Set-up of the mass weight, synchronised on return: the description's mass_coefficient goes to the device as a
+// temporary and is folded into `out` (allocated here)
+template <typename T>
+int fold_mass(DeviceArray<T> &out, const void *mass_coefficient, const FoldInputs<T> &in);
 // Set-up of the folded metric, synchronised on return: the description's coefficient (or, if NULL, the coefficient
-// evaluated from its quadrature_points), JxW and inv_jac go to the device as temporaries and are folded into `out`,
-// nd points per cell in the order cell_order[0 .. n_cells).  Per point the scalar a J0^2 JxW, or with `general` the
-// symmetric a JxW J^-1 J^-T (6 entries in 3D, 3 in 2D) from the full J^-1 per point.
+// evaluated from its quadrature_points) goes to the device as a temporary and is folded into `out` (allocated here)
 template <typename T>
-int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *quadrature_points, const void *JxW,
-                     const void *inv_jac, const uint32_t *cell_order, int dim, uint32_t n_cells, uint32_t nd,
-                     bool general);
+int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *quadrature_points,
+                     const FoldInputs<T> &in);
 
 // ---- SURVEY.md 8(f) N1 / N2 (mfgpu_aux.hip)
 template <typename T>

@@ -400,31 +400,40 @@ hipError_t fold_launch(T *c, const T *coef, const T *jxw, const T *j0, const uin
   return hipGetLastError();
 }
 
+int FoldGeometry::upload(const void *JxW, const void *inv_jac, const uint32_t *cell_order, int dim_, uint32_t n_cells_,
+                         uint32_t nd_, bool general_, int number_type) {
+  dim = dim_, n_cells = n_cells_, nd = nd_, general = general_;
+  const size_t np = (size_t)n_cells * nd, es = esize(number_type);
+  int rc;
+  if (JxW && (rc = jxw.upload(JxW, np * es))) return rc;
+  // full J^-1 per point, or one scalar per cell
+  if ((rc = jinv.upload(inv_jac, (general ? np * (size_t)(dim * dim) : n_cells) * es))) return rc;
+  return order.upload(cell_order, n_cells);
+}
+
 template <typename T>
-int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *quadrature_points, const void *JxW,
-                     const void *inv_jac, const uint32_t *cell_order, int dim, uint32_t n_cells, uint32_t nd,
-                     bool general) {
-  const size_t np = (size_t)n_cells * nd;
-  DeviceArray<T> coef, qpts, jxw, jinv;
-  DeviceArray<uint32_t> order;
+hipError_t fold_coefficient_launch(T *out, const T *coef, const FoldInputs<T> &in, hipStream_t st) {
+  if ((size_t)in.n_cells * in.nd == 0) return hipSuccess;
+  const auto fold = !in.general ? fold_launch<T> : in.dim == 3 ? fold_general_launch<T> : fold_general2_launch<T>;
+  return fold(out, coef, in.jxw, in.jinv, in.order, in.n_cells, in.nd, st);
+}
+
+template <typename T>
+int fold_coefficient(DeviceArray<T> &out, const void *coefficient, const void *quadrature_points,
+                     const FoldInputs<T> &in) {
+  const size_t np = (size_t)in.n_cells * in.nd;
+  DeviceArray<T> coef, qpts;
   int rc;
   if (coefficient) {
     if ((rc = coef.upload(coefficient, np))) return rc;
   } else {
-    if ((rc = qpts.upload(quadrature_points, np * dim))) return rc;
+    if ((rc = qpts.upload(quadrature_points, np * in.dim))) return rc;
     if ((rc = coef.alloc(np))) return rc;
-    if ((rc = hip_check(coefficient_launch<T>(coef.get(), qpts.get(), np, dim, nullptr), "coefficient evaluation")))
+    if ((rc = hip_check(coefficient_launch<T>(coef.get(), qpts.get(), np, in.dim, nullptr), "coefficient evaluation")))
       return rc;
   }
-  if ((rc = jxw.upload(JxW, np))) return rc;
-  // full J^-1 per point, or one scalar per cell
-  if ((rc = jinv.upload(inv_jac, general ? np * (size_t)(dim * dim) : n_cells))) return rc;
-  if ((rc = order.upload(cell_order, n_cells))) return rc;
-  if ((rc = out.alloc(np * (general ? (dim == 3 ? 6 : 3) : 1)))) return rc;
-  const auto fold = !general ? fold_launch<T> : dim == 3 ? fold_general_launch<T> : fold_general2_launch<T>;
-  if ((rc = hip_check(fold(out.get(), coef.get(), jxw.get(), jinv.get(), order.get(), n_cells, nd, nullptr),
-                      "coefficient fold")))
-    return rc;
+  if ((rc = out.alloc(in.metric_entries()))) return rc;
+  if ((rc = hip_check(fold_coefficient_launch<T>(out.get(), coef.get(), in, nullptr), "coefficient fold"))) return rc;
   return hip_check(hipDeviceSynchronize(), "coefficient fold");
 }
 
@@ -439,19 +448,21 @@ __global__ void fold_mass_kernel(T *m, const T *c, const T *jxw, const uint32_t 
 }
 
 template <typename T>
-int fold_mass(DeviceArray<T> &out, const void *mass_coefficient, const void *JxW, const uint32_t *cell_order,
-              uint32_t n_cells, uint32_t nd) {
-  const size_t np = (size_t)n_cells * nd;
-  DeviceArray<T> c, jxw;
-  DeviceArray<uint32_t> order;
+hipError_t fold_mass_launch(T *out, const T *c, const FoldInputs<T> &in, hipStream_t st) {
+  const size_t np = (size_t)in.n_cells * in.nd;
+  if (np == 0) return hipSuccess;
+  hipLaunchKernelGGL(fold_mass_kernel<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, out, c, in.jxw,
+                     in.order, in.n_cells, in.nd);
+  return hipGetLastError();
+}
+
+template <typename T>
+int fold_mass(DeviceArray<T> &out, const void *mass_coefficient, const FoldInputs<T> &in) {
+  const size_t np = (size_t)in.n_cells * in.nd;
+  DeviceArray<T> c;
   int rc;
-  if ((rc = c.upload(mass_coefficient, np)) || (rc = jxw.upload(JxW, np)) || (rc = order.upload(cell_order, n_cells)) ||
-      (rc = out.alloc(np)))
-    return rc;
-  if (np == 0) return 0;
-  hipLaunchKernelGGL(fold_mass_kernel<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, nullptr, out.get(), c.get(),
-                     jxw.get(), order.get(), n_cells, nd);
-  if ((rc = hip_check(hipGetLastError(), "mass fold"))) return rc;
+  if ((rc = c.upload(mass_coefficient, np)) || (rc = out.alloc(np))) return rc;
+  if ((rc = hip_check(fold_mass_launch<T>(out.get(), c.get(), in, nullptr), "mass fold"))) return rc;
   return hip_check(hipDeviceSynchronize(), "mass fold");
 }
 
@@ -470,9 +481,10 @@ hipError_t fill_launch(T *v, size_t n, T a, hipStream_t st) {
   template hipError_t coefficient_launch<T>(T *, const T *, size_t, int, hipStream_t);                  \
   template hipError_t fold_launch<T>(T *, const T *, const T *, const T *, const uint32_t *, uint32_t,  \
                                      uint32_t, hipStream_t);                                            \
-  template int fold_coefficient<T>(DeviceArray<T> &, const void *, const void *, const void *, const void *,       \
-                                   const uint32_t *, int, uint32_t, uint32_t, bool);                    \
-  template int fold_mass<T>(DeviceArray<T> &, const void *, const void *, const uint32_t *, uint32_t, uint32_t); \
+  template hipError_t fold_coefficient_launch<T>(T *, const T *, const FoldInputs<T> &, hipStream_t);   \
+  template hipError_t fold_mass_launch<T>(T *, const T *, const FoldInputs<T> &, hipStream_t);          \
+  template int fold_coefficient<T>(DeviceArray<T> &, const void *, const void *, const FoldInputs<T> &); \
+  template int fold_mass<T>(DeviceArray<T> &, const void *, const FoldInputs<T> &);                    \
   template hipError_t fill_launch<T>(T *, size_t, T, hipStream_t);
 INST(double)
 INST(float)

@@ -143,6 +143,17 @@ int mfgpu_level_create(const mfgpu_desc *desc, const uint32_t *edge_dofs, uint32
 
 mfgpu_handle *mfgpu_level_operator(mfgpu_level *L) { return L ? L->A : nullptr; }
 
+int mfgpu_level_update_coefficients(mfgpu_level *L, const void *coefficient_dev, const void *mass_coefficient_dev,
+                                    void *stream) {
+  if (!L) {
+    set_error("mfgpu_level_update_coefficients: null argument");
+    return MFGPU_EINVAL;
+  }
+  // A first: it refuses what Ab (made from a copy of the same description) would refuse, before anything is written
+  if (const int rc = mfgpu_update_coefficients(L->A, coefficient_dev, mass_coefficient_dev, stream)) return rc;
+  return L->Ab ? mfgpu_update_coefficients(L->Ab, coefficient_dev, mass_coefficient_dev, stream) : 0;
+}
+
 int mfgpu_level_vmult_interface_down(mfgpu_level *L, void *dst, const void *src, void *stream) {
   if (!L || !dst || !src || dst == src) {
     set_error("mfgpu_level_vmult_interface_down: null or aliasing argument");

@@ -69,6 +69,8 @@ public:
     d.mass_coefficient = mass_coefficient;
     check(mfgpu_integrator_create(&d, &it), "mfgpu_integrator_create");
   }
+  // ... from a description the caller has adjusted (flags, coefficient, mass_coefficient)
+  explicit PoissonIntegrator(const mfgpu_desc &d) { check(mfgpu_integrator_create(&d, &it), "mfgpu_integrator_create"); }
   ~PoissonIntegrator() { mfgpu_integrator_destroy(it); }
   PoissonIntegrator(const PoissonIntegrator &) = delete;
   PoissonIntegrator &operator=(const PoissonIntegrator &) = delete;

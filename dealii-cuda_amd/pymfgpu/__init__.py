@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MFGPU_LIB") or os.path.join(os.path.dirname(_HERE), "
 F64, F32 = 0, 1
 OK, EINVAL = 0, -1  # MFGPU_OK, MFGPU_EINVAL
 UNIFORM_J0, HANGING_NODES, COLORED_SCATTER, NO_SHARED_RECORDS = 1, 2, 1 << 8, 1 << 9
+UPDATABLE_COEFFICIENTS = 1 << 10  # keep what update_coefficients (and Integrator.evaluate's gradients) read on the device
 KERNEL_AUTO, KERNEL_PENCILS, KERNEL_PENCILS_X, KERNEL_PLANES, KERNEL_PLANES_2W = 0, 1, 2, 3, 4  # Desc.kernel
 
 
@@ -65,6 +66,8 @@ SYMBOLS = [
     "mfgpu_integrator_destroy",
     "mfgpu_vec_convert", "mfgpu_vec_copy_pairs_convert", "mfgpu_vec_chebyshev_start", "mfgpu_vec_chebyshev_update",
     "mfgpu_desc_size",
+    "mfgpu_update_coefficients", "mfgpu_level_update_coefficients", "mfgpu_integrator_update_coefficients",
+    "mfgpu_integrator_evaluate",
 ]
 
 _lib = None
@@ -184,6 +187,10 @@ def lib():
         L.mfgpu_integrator_destroy.argtypes = [C.c_void_p]
         L.mfgpu_integrator_destroy.restype = None
         L.mfgpu_vec_convert.argtypes = [vp, i, vp, i, z, vp]
+        L.mfgpu_update_coefficients.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_level_update_coefficients.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_integrator_update_coefficients.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_integrator_evaluate.argtypes = [vp, vp, vp, vp, vp]
         L.mfgpu_vec_copy_pairs_convert.argtypes = [vp, vp, i, vp, i, vp]
         L.mfgpu_vec_chebyshev_start.argtypes = [vp, vp, vp, vp, vp, vp, d, i, z, i, vp]
         L.mfgpu_vec_chebyshev_update.argtypes = [vp, vp, vp, vp, vp, d, d, z, i, vp]
@@ -584,6 +591,11 @@ class Operator:
         """ConstraintHandlerGpu::set_constrained_values (constraint_handler_gpu.cu:126-137)"""
         _check(lib().mfgpu_set_constrained_values(self._h, _ptr(vec), float(value), stream))
 
+    def update_coefficients(self, coef=None, mass=None, stream=None):
+        """mfgpu_update_coefficients: new a and / or c from DEVICE arrays [n_cells * (p+1)^dim] (None: unchanged); the
+        operator must have been created with UPDATABLE_COEFFICIENTS"""
+        _check(lib().mfgpu_update_coefficients(self._h, _optr(coef), _optr(mass), stream))
+
     def profile_enable(self, on=True):
         _check(lib().mfgpu_profile_enable(self._h, int(on)))
 
@@ -632,6 +644,15 @@ class Integrator:
         _check(lib().mfgpu_integrator_l2_error(self._h, _ptr(u), None if exact is None else _ptr(exact),
                                                None if per_cell is None else _ptr(per_cell), stream, C.byref(r)))
         return r.value
+
+    def update_coefficients(self, coef=None, mass=None, stream=None):
+        """mfgpu_integrator_update_coefficients: a and c of the lift from device arrays (UPDATABLE_COEFFICIENTS)"""
+        _check(lib().mfgpu_integrator_update_coefficients(self._h, _optr(coef), _optr(mass), stream))
+
+    def evaluate(self, u, values=None, gradients=None, stream=None):
+        """u at the quadrature points into `values` [n_cells * (p+1)^dim] and / or its real-space gradient into
+        `gradients` [n_cells * (p+1)^dim * dim] (device arrays; gradients need UPDATABLE_COEFFICIENTS)"""
+        _check(lib().mfgpu_integrator_evaluate(self._h, _ptr(u), _optr(values), _optr(gradients), stream))
 
     def error_points(self):
         """the error points of every cell on the host, [n_cells, (p+2)^dim, dim]"""
@@ -696,6 +717,10 @@ class Level:
     def compute_inverse_diagonal(self, inv_diag, stream=None):
         _check(lib().mfgpu_compute_inverse_diagonal(lib().mfgpu_level_operator(self._h), _ptr(inv_diag), stream))
 
+    def update_coefficients(self, coef=None, mass=None, stream=None):
+        """mfgpu_level_update_coefficients: the level operator and the interface matrices (UPDATABLE_COEFFICIENTS)"""
+        _check(lib().mfgpu_level_update_coefficients(self._h, _optr(coef), _optr(mass), stream))
+
     def vmult_interface_down(self, dst, src, stream=None):
         _check(lib().mfgpu_level_vmult_interface_down(self._h, _ptr(dst), _ptr(src), stream))
 
@@ -756,6 +781,10 @@ def _ptr(v):
     if hasattr(v, "data_ptr"):  # torch tensor on the GPU
         return v.data_ptr()
     return int(v)
+
+
+def _optr(v):
+    return None if v is None else _ptr(v)
 
 
 class IndexPairs:

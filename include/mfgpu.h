@@ -60,6 +60,19 @@ extern "C" {
                                          even where the plan would share repeated ones (below, "shared form"): for
                                          tests and for A/B measurements inside one build                            */
 
+#define MFGPU_UPDATABLE_COEFFICIENTS (1u << 10) /* the operator, level or integrator created from the description
+                                         keeps on the device what a re-fold of its coefficients reads, so that
+                                         mfgpu_update_coefficients / mfgpu_level_update_coefficients /
+                                         mfgpu_integrator_update_coefficients (below) can replace a and c from device
+                                         arrays without a new plan: JxW [n_cells * n^dim], inv_jac (one scalar per cell,
+                                         or the full J^-1 per point), the plan's cell order [n_cells] (uint32) and, where
+                                         the cell loop runs a plane kernel, two uint32 tables over the plane batches'
+                                         cells.  Opt-in because of the memory: mfgpu_memory_consumption grows by exactly
+                                         these bytes -- with the full J^-1 in 3D (8 + 72 =) 80 B per quadrature point in
+                                         double; with MFGPU_UNIFORM_J0 8 B per point plus 12 B per cell (20 on plane plans).  Plan, kernel
+                                         choice and every result are the same with and without the flag;
+                                         mfgpu_plan_create and mfgpu_suggest_renumbering ignore it.                  */
+
 typedef struct mfgpu_handle mfgpu_handle; /* replaces MatrixFreeGpu + coefficient + ConstraintHandlerGpu
                                              inside LaplaceOperatorGpu (laplace_operator_gpu.h:85-95) */
 
@@ -149,6 +162,19 @@ int mfgpu_vmult(mfgpu_handle *h, void *dst_dev, const void *src_dev, void *strea
 
 /* laplace_operator_gpu.h:286-303: dst += A src on free rows, dst_c += src_c on constrained rows. */
 int mfgpu_vmult_add(mfgpu_handle *h, void *dst_dev, const void *src_dev, void *stream);
+
+/* New coefficients for an operator created with MFGPU_UPDATABLE_COEFFICIENTS (no reference counterpart: the reference
+ * evaluates its coefficient once, in reinit).  coefficient_dev / mass_coefficient_dev: DEVICE arrays [n_cells * n^dim] of
+ * the handle's number type, values at the quadrature points in the description's cell order; NULL leaves that term as it
+ * is.  Folds with the kernels and the arithmetic of mfgpu_create into the handle's existing arrays: afterwards vmult,
+ * vmult_add, vmult_dist* and compute_inverse_diagonal are those of a handle created with the new values.  Asynchronous on
+ * `stream` and ordered like every other call on the handle; allocates nothing, does not synchronise with the host, reads
+ * the arrays when the stream gets there.  MFGPU_EINVAL (nothing is written): no MFGPU_UPDATABLE_COEFFICIENTS at
+ * creation; both pointers NULL; mass_coefficient_dev on a handle created without mass_coefficient (its kernels were
+ * bound without the mass term, and at p = 5, 6 the kernel family depends on it).  A handle created with coefficient =
+ * NULL (the built-in 1/(0.05+2|x|^2)) is updated from an explicit array like any other.                              */
+int mfgpu_update_coefficients(mfgpu_handle *h, const void *coefficient_dev, const void *mass_coefficient_dev,
+                              void *stream);
 
 /* laplace_operator_gpu.h:53-54 m() / n() */
 uint32_t mfgpu_n_dofs(const mfgpu_handle *h);
@@ -316,6 +342,10 @@ int mfgpu_level_create(const mfgpu_desc *desc, const uint32_t *edge_dofs, uint32
 mfgpu_handle *mfgpu_level_operator(mfgpu_level *level);
 int mfgpu_level_vmult_interface_down(mfgpu_level *level, void *dst_dev, const void *src_dev, void *stream); /* :306-330 */
 int mfgpu_level_vmult_interface_up(mfgpu_level *level, void *dst_dev, const void *src_dev, void *stream);   /* :332-352 */
+/* mfgpu_update_coefficients for the level operator and the operator behind the interface matrices (both carry the
+ * description's MFGPU_UPDATABLE_COEFFICIENTS); same arguments, same errors */
+int mfgpu_level_update_coefficients(mfgpu_level *level, const void *coefficient_dev, const void *mass_coefficient_dev,
+                                    void *stream);
 void mfgpu_level_destroy(mfgpu_level *level);
 
 /* copy_to_mg / copy_from_mg (mg_transfer_matrix_free_gpu.cu:690-760): dst[dst_idx[i]] = src[src_idx[i]] for the index
@@ -373,6 +403,21 @@ int mfgpu_integrator_l2_error(mfgpu_integrator *it, const void *u, const void *e
 /* the (p+2)^dim error points of every cell, [n_cells * (p+2)^dim * dim] (x, y, z per point, x fastest), so that a
  * caller can supply `exact`.  Asynchronous.                                                                       */
 int mfgpu_integrator_error_points(mfgpu_integrator *it, void *points, void *stream);
+/* The same for the Dirichlet lift of mfgpu_integrator_rhs: a and c of an integrator created with
+ * MFGPU_UPDATABLE_COEFFICIENTS (it then keeps inv_jac on the device; JxW is resident anyway).  Double device arrays;
+ * arguments, execution rules and errors as mfgpu_update_coefficients.                                                */
+int mfgpu_integrator_update_coefficients(mfgpu_integrator *it, const void *coefficient_dev,
+                                         const void *mass_coefficient_dev, void *stream);
+/* The finite element field at the description's quadrature points -- the read_dof_values + evaluate + get_value /
+ * get_gradient half of FEEvaluationGpu (fee_gpu.cuh), which the reference only uses inside its cell loop.  u: device
+ * vector [n_dofs], read on every dof a cell references, constrained dofs included, hanging-node interpolated as in
+ * mfgpu_integrator_rhs.  values_qp: [n_cells * (p+1)^dim]; gradients_qp: [n_cells * (p+1)^dim * dim], real-space
+ * gradients (J^-T applied), x, y, z per point; cell-major in the description's cell order, points x fastest.  Either
+ * output may be NULL (both: MFGPU_EINVAL).  Gradients need inv_jac on the device: gradients_qp != NULL on an
+ * integrator created without MFGPU_UPDATABLE_COEFFICIENTS is MFGPU_EINVAL; values work on every integrator.  One
+ * wave per cell, no atomics: two calls give bitwise-equal results.  Asynchronous.  With this and the BLAS-1 calls a
+ * coefficient a(u) is formed on the device and handed to the update calls (host/nonlinear.cc).                       */
+int mfgpu_integrator_evaluate(mfgpu_integrator *it, const void *u, void *values_qp, void *gradients_qp, void *stream);
 void mfgpu_integrator_destroy(mfgpu_integrator *it);
 
 /* ---- deal.II stand-in for the setup side (host only) --------------------------------------
