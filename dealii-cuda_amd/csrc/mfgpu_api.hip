@@ -129,6 +129,19 @@ struct mfgpu_handle {
     if constexpr (std::is_same<T, double>::value) return kernels_f64[which];
     else return kernels_f32[which];
   }
+  // mfgpu_vmult_multi: the fused instantiations this handle has (index = width - 2; unbound: launch[0] == nullptr),
+  // bound by create_arrays next to the batch family, and the halo buffers 2 .. multi_width of a fused group (one
+  // allocation of halo_bytes each, made by the first fused call)
+  MultiKernel<double> multi_f64[kMaxFusedWidth - 1];
+  MultiKernel<float> multi_f32[kMaxFusedWidth - 1];
+  template <typename T>
+  MultiKernel<T> &multi(int width) {
+    if constexpr (std::is_same<T, double>::value) return multi_f64[width - 2];
+    else return multi_f32[width - 2];
+  }
+  int multi_width = 1;
+  DeviceArray<void> d_halo_multi;
+  size_t halo_bytes = 0;
   uint32_t n_cus = 0, max_workgroups = 0;  // persistent grids: the chip's CUs, mfgpu_desc.max_workgroups (0: no cap)
   // profiling
   bool prof = false;
@@ -385,6 +398,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     const size_t hb = ((size_t)P.halo_off.back() + 1) * sizeof(T);  // + the always-zero slot of the untouched dofs
     if ((rc = h->d_halo.alloc(hb, true))) return rc;
     acct += hb;
+    h->halo_bytes = hb;
   }
   if (h->hn) {
     std::vector<uint32_t> cm(ncell);
@@ -469,6 +483,18 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     return MFGPU_EINVAL;
   }
   HIP_TRY(bind_batch_family);
+  // the fused instantiations of the family (fused_kernel_exists), each bound like the kernel above; a width whose
+  // batch arrays do not fit the LDS with this plan's batches stays unbound
+  if (h->twopass && h->planes == PlaneKernel::none)
+    for (const int w : kFusedWidths) {
+      if (!fused_kernel_exists(h->batches, P.n, d.number_type, h->hn, h->d_mass.get() != nullptr, w)) continue;
+      MultiKernel<T> &mk = h->multi<T>(w);
+      if (gm_bind<T>(P.n, h->hn, h->d_mass.get() != nullptr, w, P.max_batch_dofs, &mk) != hipSuccess) {
+        (void)hipGetLastError();
+        mk = MultiKernel<T>();
+      } else
+        h->multi_width = std::max(h->multi_width, w);
+    }
   return 0;
 }
 
@@ -659,6 +685,76 @@ int vmult_typed(mfgpu_handle *h, void *dst, const void *src, hipStream_t st, int
   if (!rc) rc = vmult_pass2<T>(h, 1, dst, src, st, add);
   if (!rc && timed) rc = h->t_pass2.end(st);
   return rc;
+}
+
+// ---- mfgpu_vmult_multi
+// Where the default mode fuses: measured per-vector time of fused groups against MFGPU_MULTI_LOOP on the BALL domain
+// (tools/bench_multi.py, profiles/r08_bench_multi.json, profiles/r08_notes.md).  Fused only where it won by more than
+// the run-to-run spread of that measurement; MFGPU_MULTI_FUSED reaches every bound instantiation regardless.
+bool fused_by_default(int /*n*/, int /*number_type*/) { return false; }
+
+// one fused group of nv vectors: the cell loop in one segment, then every pass-2 group, all on st
+template <typename T>
+int multi_fused_group(mfgpu_handle *h, T *dst, const T *src, int nv, size_t stride, hipStream_t st, int add) {
+  const MultiKernel<T> &k = h->multi<T>(nv);
+  if (!k.launch[0]) {
+    set_error("fused kernel not bound");
+    return MFGPU_EINVAL;
+  }
+  if (!h->d_halo_multi.get()) {
+    const size_t bytes = (size_t)(h->multi_width - 1) * h->halo_bytes;
+    if (const int rc = h->d_halo_multi.alloc(bytes, true)) return rc;  // zeroed: the untouched dofs' slot stays zero
+    HIP_TRY(hipStreamSynchronize(nullptr));  // (the memset, before a kernel on a non-blocking stream reads the slot)
+    h->device_bytes += bytes;
+  }
+  if (h->side_pending) {
+    HIP_TRY(hipStreamWaitEvent(st, h->ev_side.get(), 0));
+    h->side_pending = false;
+  }
+  MultiArgs<T> a;
+  static_cast<ApplyArgs<T> &>(a) = make_args<T>(h, dst, src, add);
+  a.stride = stride;
+  for (int v = 0; v < kMaxFusedWidth; ++v)
+    a.halos[v] = v == 0 ? a.halo
+                 : v < nv ? reinterpret_cast<T *>(static_cast<char *>(h->d_halo_multi.get()) + (size_t)(v - 1) * h->halo_bytes)
+                          : nullptr;
+  const uint32_t nbat = (uint32_t)(h->plan.batch_cell_off.size() - 1);
+  a.batch0 = 0;
+  a.batch_end = nbat;
+  uint32_t grid = (uint32_t)(k.per_cu < 1 ? 1 : k.per_cu) * h->n_cus;
+  if (h->max_workgroups && h->max_workgroups < grid) grid = h->max_workgroups;
+  HIP_TRY(k.launch[add != 0](a, h->S.data(), h->Dt.data(), k.lds, nbat < grid ? nbat : grid, st));
+  for (size_t g = 0; g < h->d_p2arr.size(); ++g)
+    HIP_TRY(reduce_classes_multi_launch<T>(nv, dst, src, stride, a.halos, h->d_p2arr[g].get(), h->d_p2tiles[g].get(),
+                                           h->n_p2tiles[g], add, st));
+  return 0;
+}
+
+template <typename T>
+int vmult_multi_typed(mfgpu_handle *h, void *dst, const void *src, uint32_t n_vectors, size_t stride, uint32_t flags,
+                      hipStream_t st) {
+  const int add = (flags & MFGPU_MULTI_ADD) ? 1 : 0;
+  const bool can_fuse = h->multi_width > 1 && !h->p2_shared && n_vectors > 1;
+  if ((flags & MFGPU_MULTI_FUSED) && !can_fuse) {
+    set_error("mfgpu_vmult_multi: MFGPU_MULTI_FUSED, but nothing to fuse (no fused instantiation for this handle, or "
+              "a single vector)");
+    return MFGPU_EUNSUPPORTED;
+  }
+  const bool fuse = can_fuse && !(flags & MFGPU_MULTI_LOOP) &&
+                    ((flags & MFGPU_MULTI_FUSED) || fused_by_default(h->n, h->number_type));
+  std::vector<uint32_t> widths;
+  if (fuse)
+    for (const int w : kFusedWidths)
+      if (h->multi<T>(w).launch[0]) widths.push_back((uint32_t)w);
+  T *d = (T *)dst;
+  const T *s = (const T *)src;
+  for (const uint32_t g : multi_groups(n_vectors, widths)) {
+    const int rc = g > 1 ? multi_fused_group<T>(h, d, s, (int)g, stride, st, add) : vmult_typed<T>(h, d, s, st, add);
+    if (rc) return rc;
+    d += (size_t)g * stride;
+    s += (size_t)g * stride;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -894,6 +990,34 @@ int mfgpu_vmult_add(mfgpu_handle *h, void *dst, const void *src, void *stream) {
   return h->number_type == MFGPU_F64 ? vmult_typed<double>(h, dst, src, (hipStream_t)stream, 1)
                                      : vmult_typed<float>(h, dst, src, (hipStream_t)stream, 1);
 }
+
+int mfgpu_vmult_multi(mfgpu_handle *h, void *dst, const void *src, uint32_t n_vectors, size_t stride, uint32_t flags,
+                      void *stream) {
+  if (!h || !dst || !src) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  const size_t nd = h->plan.n_dofs;
+  if (n_vectors == 0 || (n_vectors > 1 && stride < nd)) {
+    set_error("mfgpu_vmult_multi: n_vectors must be >= 1 and stride >= n_dofs");
+    return MFGPU_EINVAL;
+  }
+  if ((flags & ~(MFGPU_MULTI_ADD | MFGPU_MULTI_LOOP | MFGPU_MULTI_FUSED)) ||
+      ((flags & MFGPU_MULTI_LOOP) && (flags & MFGPU_MULTI_FUSED))) {
+    set_error("mfgpu_vmult_multi: bad flags (MFGPU_MULTI_LOOP and MFGPU_MULTI_FUSED exclude each other)");
+    return MFGPU_EINVAL;
+  }
+  const size_t bytes = ((size_t)(n_vectors - 1) * stride + nd) * esize(h->number_type);
+  const char *d0 = (const char *)dst, *s0 = (const char *)src;
+  if (d0 < s0 + bytes && s0 < d0 + bytes) {
+    set_error("mfgpu_vmult_multi: the dst range overlaps the src range");
+    return MFGPU_EINVAL;
+  }
+  return h->number_type == MFGPU_F64 ? vmult_multi_typed<double>(h, dst, src, n_vectors, stride, flags, (hipStream_t)stream)
+                                     : vmult_multi_typed<float>(h, dst, src, n_vectors, stride, flags, (hipStream_t)stream);
+}
+
+int mfgpu_multi_width(const mfgpu_handle *h) { return h ? h->multi_width : 0; }
 
 int mfgpu_update_coefficients(mfgpu_handle *h, const void *coefficient_dev, const void *mass_coefficient_dev,
                               void *stream) {

@@ -195,6 +195,19 @@ constexpr bool kernel_exists(PlaneKernel k, int n, int number_type, bool hn, boo
 constexpr bool kernel_exists(BatchKernel k, int n, int /*number_type*/, bool /*hn*/, bool sh, bool /*mass*/) {
   return k != BatchKernel::none && n >= 2 && n <= 7 && !sh;
 }
+// ... and of which FUSED instantiations exist (mfgpu_vmult_multi): apply_batches_gm<n, T, HN, MASS, NV> applies the
+// operator to a group of nv vectors in one sweep.  Only the g family has them: n = 2..7, both number types, HN and MASS
+// in every combination, widths kFusedWidths -- less, in double with HN, width 3 at n = 6, 7 and width 2 at n = 7, which
+// spill even with one wave per SIMD (80-488 B per lane).  gm_bind instantiates exactly these, create_arrays binds the handle's, and
+// a (family, degree, width) that is not here falls back to single applies.
+constexpr int kFusedWidths[] = {3, 2};  // widest first
+constexpr bool fused_kernel_exists(BatchKernel k, int n, int number_type, bool hn, bool /*mass*/, int nv) {
+  return k == BatchKernel::g && n >= 2 && n <= 7 && (nv == 2 || nv == 3) &&
+         !(hn && number_type == MFGPU_F64 && n >= (nv == 3 ? 6 : 7));
+}
+// n_vectors cut into groups of the given widths (descending), widest first; what is left over goes out as groups of 1
+// (single applies).  7 with {3, 2}: 3 3 1;  5: 3 2.
+std::vector<uint32_t> multi_groups(uint32_t n_vectors, const std::vector<uint32_t> &widths);
 int build_plane_records(Plan &plan, const uint32_t *constraint_mask);
 // The shared form of the plane records (Plan::sh_*), derived from pr_dofs / pr_idx at the end of build_plane_records.
 // It is used when its bytes (distinct records + per-batch table) are at most kShareMaxFraction of the expanded

@@ -54,6 +54,17 @@ struct ApplyArgs {
   const T *massp = nullptr;
 };
 
+// mfgpu_vmult_multi, fused groups (apply_batches_gm, reduce_classes_multi): the arguments of a single apply -- dst, src
+// and halo are those of vector 0 -- plus what a group adds.  A struct of its own: ApplyArgs<T> is passed by value to
+// every existing kernel and stays byte for byte what it is.
+constexpr int kMaxFusedWidth = 3;
+template <typename T>
+struct MultiArgs : ApplyArgs<T> {
+  size_t stride = 0;         // vector v starts at element v * stride of dst and of src
+  T *halos[kMaxFusedWidth];  // halo buffer of vector v (halos[0] == halo)
+};
+constexpr size_t kMaxLdsBytes = 160 * 1024;  // LDS of a gfx950 CU
+
 // 1D tables, passed by value as kernel arguments (=> scalar registers).
 template <typename T, int n>
 struct Tables {
@@ -80,17 +91,19 @@ inline Tables<T, n> make_tables(const double *S, const double *Dt) {
 // admits (else hipErrorInvalidValue) and hands it to bind_cell_kernel, which sets the dynamic-LDS attribute of
 // precisely the kernels whose launch entries it stores.  So what can be launched has been configured.
 // launch[add](a, S, Dt, lds, grid, st) runs batches [a.batch0, a.batch_end) with the 1D tables made from S, Dt.
-template <typename T>
+// (Args: the kernel's by-value argument struct -- ApplyArgs<T> for every single-vector family, MultiArgs<T> for the
+// fused family of mfgpu_vmult_multi)
+template <typename T, typename Args = ApplyArgs<T>>
 struct CellKernel {
   size_t lds = 0;  // dynamic LDS bytes per workgroup (set first, also when binding fails)
   int per_cu = 0;  // resident workgroups per CU (of launch[0])
-  hipError_t (*launch[2])(const ApplyArgs<T> &a, const double *S, const double *Dt, size_t lds, uint32_t grid,
+  hipError_t (*launch[2])(const Args &a, const double *S, const double *Dt, size_t lds, uint32_t grid,
                           hipStream_t st) = {nullptr, nullptr};
 };
 
 // MakeTab: the kernel's by-value table argument from the host tables (make_tables, make_tables_eo), or nullptr
-template <typename T, int Block, auto K, auto MakeTab>
-hipError_t launch_cell_kernel(const ApplyArgs<T> &a, const double *S, const double *Dt, size_t lds, uint32_t grid,
+template <typename T, int Block, auto K, auto MakeTab, typename Args = ApplyArgs<T>>
+hipError_t launch_cell_kernel(const Args &a, const double *S, const double *Dt, size_t lds, uint32_t grid,
                               hipStream_t st) {
   if constexpr (std::is_null_pointer_v<decltype(MakeTab)>)
     hipLaunchKernelGGL(K, dim3(grid), dim3(Block), lds, st, a);
@@ -100,13 +113,13 @@ hipError_t launch_cell_kernel(const ApplyArgs<T> &a, const double *S, const doub
 }
 
 // K0 / K1: the add = 0 / add = 1 instantiations (the same kernel where ADD is the run-time field a.add)
-template <typename T, int Block, auto K0, auto K1, auto MakeTab>
-hipError_t bind_cell_kernel(size_t lds, CellKernel<T> *k) {
+template <typename T, int Block, auto K0, auto K1, auto MakeTab, typename Args = ApplyArgs<T>>
+hipError_t bind_cell_kernel(size_t lds, CellKernel<T, Args> *k) {
   k->lds = lds;
   for (const void *f : {(const void *)K1, (const void *)K0})
     if (const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-  k->launch[0] = launch_cell_kernel<T, Block, K0, MakeTab>;
-  k->launch[1] = launch_cell_kernel<T, Block, K1, MakeTab>;
+  k->launch[0] = launch_cell_kernel<T, Block, K0, MakeTab, Args>;
+  k->launch[1] = launch_cell_kernel<T, Block, K1, MakeTab, Args>;
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(&k->per_cu, (const void *)K0, Block, lds);
 }
 
@@ -144,6 +157,12 @@ MFGPU_CELL_LOOP_FAMILY(g2)
 MFGPU_CELL_LOOP_FAMILY(p)
 MFGPU_CELL_LOOP_FAMILY(q)
 #undef MFGPU_CELL_LOOP_FAMILY
+// the fused family of the g family (mfgpu_kernels_gm.hip): the instantiation (n, hn, mass) of width nv that
+// fused_kernel_exists admits, else hipErrorInvalidValue (also where the plan's batches need more LDS than a CU has)
+template <typename T>
+using MultiKernel = CellKernel<T, MultiArgs<T>>;
+template <typename T>
+hipError_t gm_bind(int n, bool hn, bool mass, int nv, uint32_t nb_max, MultiKernel<T> *k);
 
 // pass 2, class-sorted structure-of-arrays form (mfgpu_pass2.hip)
 void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<uint32_t> &s_off,
@@ -151,6 +170,11 @@ void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<u
 template <typename T>
 hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint32_t *arr, const uint32_t *tiles,
                                  uint32_t n_tiles, int add, hipStream_t st);
+// ... for a fused group of nv = 2, 3 vectors: the class arrays are read once per tile; vector v's sums come from
+// halos[v] and go to dst + v * stride (identity rows: src + v * stride), each in reduce_classes' order
+template <typename T>
+hipError_t reduce_classes_multi_launch(int nv, T *dst, const T *src, size_t stride, T *const *halos, const uint32_t *arr,
+                                       const uint32_t *tiles, uint32_t n_tiles, int add, hipStream_t st);
 // pass 2, shared form: one workgroup per owner batch (Plan::sh_p2rec / sh_p2tab); reverse: last batch first
 template <typename T>
 hipError_t reduce_owner_batches_launch(T *dst, const T *src, const T *halo, const uint32_t *rec, const uint32_t *tab,

@@ -87,6 +87,87 @@ reduce_classes(T *__restrict__ dst, const T *__restrict__ src, const T *__restri
   }
 }
 
+// ---- Fused groups (mfgpu_vmult_multi): reduce_two for NV vectors.  The dof ids and the K halo slots of a thread's two
+// entries are loaded once; then, per vector, the sums in reduce_two's order (slot 0 first, ascending touchers) from
+// that vector's halo buffer into dst + v * stride.
+template <typename T>
+struct MultiHalos {
+  const T *h[kMaxFusedWidth];
+};
+
+template <typename T, int K, int NV>
+__device__ __forceinline__ void reduce_two_multi(T *__restrict__ dst, const T *__restrict__ src, size_t stride,
+                                                 const MultiHalos<T> &halos, const uint32_t *__restrict__ p,
+                                                 uint32_t cnt, uint32_t i0, uint32_t k, int add) {
+  const uint32_t i1 = i0 + 256u;
+  const uint32_t d0 = p[i0], d1 = p[i1];
+  constexpr int KU = K > 0 ? K : 1;
+  uint32_t s0[KU], s1[KU];
+#pragma unroll
+  for (int t = 0; t < KU; ++t) {
+    s0[t] = p[(size_t)(1 + t) * cnt + i0];
+    s1[t] = p[(size_t)(1 + t) * cnt + i1];
+  }
+  const bool on0 = d0 != 0xffffffffu, on1 = d1 != 0xffffffffu;
+  const uint32_t g0 = d0 & 0x7fffffffu, g1 = d1 & 0x7fffffffu;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const T *__restrict__ halo = halos.h[v];
+    const T *__restrict__ sv = src + (size_t)v * stride;
+    T *__restrict__ dv = dst + (size_t)v * stride;
+    T v0 = T(0), v1 = T(0), o0 = T(0), o1 = T(0);
+    if (on0) {
+      if (d0 >> 31) {
+        v0 = sv[g0];
+      } else {
+        T q[KU];
+#pragma unroll
+        for (int t = 0; t < KU; ++t) q[t] = halo[s0[t]];
+        v0 = q[0];
+#pragma unroll
+        for (int t = 1; t < KU; ++t) v0 += q[t];
+        if (K == 0)
+          for (uint32_t t = 1; t < k; ++t) v0 += halo[p[(size_t)(1 + t) * cnt + i0]];
+      }
+      if (add) o0 = dv[g0];
+    }
+    if (on1) {
+      if (d1 >> 31) {
+        v1 = sv[g1];
+      } else {
+        T q[KU];
+#pragma unroll
+        for (int t = 0; t < KU; ++t) q[t] = halo[s1[t]];
+        v1 = q[0];
+#pragma unroll
+        for (int t = 1; t < KU; ++t) v1 += q[t];
+        if (K == 0)
+          for (uint32_t t = 1; t < k; ++t) v1 += halo[p[(size_t)(1 + t) * cnt + i1]];
+      }
+      if (add) o1 = dv[g1];
+    }
+    if (on0) dv[g0] = add ? o0 + v0 : v0;
+    if (on1) dv[g1] = add ? o1 + v1 : v1;
+  }
+}
+
+template <typename T, int NV>
+__global__ void __launch_bounds__(256)
+reduce_classes_multi(T *__restrict__ dst, const T *__restrict__ src, size_t stride, const MultiHalos<T> halos,
+                     const uint32_t *__restrict__ arr, const uint4 *__restrict__ tiles, int add) {
+  const uint4 td = tiles[blockIdx.x];  // as in reduce_classes
+  const uint32_t *p = arr + td.x;
+  const uint32_t i0 = td.w + threadIdx.x;
+  switch (td.y) {  // wave-uniform
+    case 1: reduce_two_multi<T, 1, NV>(dst, src, stride, halos, p, td.z, i0, 1, add); break;
+    case 2: reduce_two_multi<T, 2, NV>(dst, src, stride, halos, p, td.z, i0, 2, add); break;
+    case 3: reduce_two_multi<T, 3, NV>(dst, src, stride, halos, p, td.z, i0, 3, add); break;
+    case 4: reduce_two_multi<T, 4, NV>(dst, src, stride, halos, p, td.z, i0, 4, add); break;
+    case 8: reduce_two_multi<T, 8, NV>(dst, src, stride, halos, p, td.z, i0, 8, add); break;
+    default: reduce_two_multi<T, 0, NV>(dst, src, stride, halos, p, td.z, i0, td.y, add); break;
+  }
+}
+
 // ---- Shared form (Plan::sh_p2rec / sh_p2tab, mfgpu_plan.cpp share_pass2_records): one workgroup per OWNER batch (the
 // batch of a dof's first partial sum).  Where the numbering repeats from batch to batch the per-dof index words of
 // reduce_classes (42 MB read once per vmult on the 54^3 mesh at p = 4) are 27 distinct records: the record is read from
@@ -200,6 +281,24 @@ hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint
                      reinterpret_cast<const uint4 *>(tiles), add);
   return hipGetLastError();
 }
+template <typename T>
+hipError_t reduce_classes_multi_launch(int nv, T *dst, const T *src, size_t stride, T *const *halos, const uint32_t *arr,
+                                       const uint32_t *tiles, uint32_t n_tiles, int add, hipStream_t st) {
+  if (n_tiles == 0) return hipSuccess;
+  if (nv != 2 && nv != 3) return hipErrorInvalidValue;
+  MultiHalos<T> mh;
+  for (int v = 0; v < kMaxFusedWidth; ++v) mh.h[v] = v < nv ? halos[v] : nullptr;
+  const uint4 *t4 = reinterpret_cast<const uint4 *>(tiles);
+  if (nv == 2)
+    hipLaunchKernelGGL((reduce_classes_multi<T, 2>), dim3(n_tiles), dim3(256), 0, st, dst, src, stride, mh, arr, t4, add);
+  else
+    hipLaunchKernelGGL((reduce_classes_multi<T, 3>), dim3(n_tiles), dim3(256), 0, st, dst, src, stride, mh, arr, t4, add);
+  return hipGetLastError();
+}
+template hipError_t reduce_classes_multi_launch<double>(int, double *, const double *, size_t, double *const *,
+                                                        const uint32_t *, const uint32_t *, uint32_t, int, hipStream_t);
+template hipError_t reduce_classes_multi_launch<float>(int, float *, const float *, size_t, float *const *,
+                                                       const uint32_t *, const uint32_t *, uint32_t, int, hipStream_t);
 template <typename T>
 hipError_t reduce_owner_batches_launch(T *dst, const T *src, const T *halo, const uint32_t *rec, const uint32_t *tab,
                                        uint32_t n_batches, uint32_t hstride, int reverse, int add, hipStream_t st) {

@@ -992,6 +992,17 @@ int choose_kernel_and_plan(const mfgpu_desc &d, PlaneKernel &pk, BatchKernel &bk
 
 }  // namespace mfgpu
 
+namespace mfgpu {
+std::vector<uint32_t> multi_groups(uint32_t n_vectors, const std::vector<uint32_t> &widths) {
+  std::vector<uint32_t> groups;
+  uint32_t left = n_vectors;
+  for (uint32_t w : widths)
+    for (; w > 1 && left >= w; left -= w) groups.push_back(w);
+  groups.insert(groups.end(), left, 1u);
+  return groups;
+}
+}  // namespace mfgpu
+
 extern "C" {
 
 const char *mfgpu_last_error(void) { return mfgpu::last_error(); }
@@ -1092,6 +1103,14 @@ int64_t mfgpu_plan_array_u32(const mfgpu_plan *p, int what, const uint32_t **ptr
   }
   *ptr = v->data();
   return (int64_t)v->size();
+}
+
+int mfgpu_plan_multi_groups(uint32_t n_vectors, const uint32_t *widths, uint32_t n_widths, uint32_t *groups,
+                            uint32_t capacity) {
+  if ((!widths && n_widths) || (!groups && capacity)) return MFGPU_EINVAL;
+  const std::vector<uint32_t> g = mfgpu::multi_groups(n_vectors, std::vector<uint32_t>(widths, widths + n_widths));
+  for (size_t i = 0; i < g.size() && i < capacity; ++i) groups[i] = g[i];
+  return (int)g.size();
 }
 
 int mfgpu_plan_shares_records(const mfgpu_plan *p) {

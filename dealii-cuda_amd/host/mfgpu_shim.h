@@ -311,6 +311,14 @@ public:
     check(mfgpu_vmult_add(data.handle, dst.getData(), src.getDataRO(), nullptr), "vmult_add");
   }
   void Tvmult_add(VectorType &dst, const VectorType &src) const { vmult_add(dst, src); }
+  // The operator on a BLOCK of n_vectors vectors (the components of a vector Laplacian, several right-hand sides):
+  // vector k is the elements [k * stride, k * stride + n()) of dst and src.  mfgpu_vmult_multi fuses groups of vectors
+  // where the handle has the kernels and they measured faster, else applies them one by one; flags: MFGPU_MULTI_*.
+  void vmult_multi(VectorType &dst, const VectorType &src, unsigned int n_vectors, std::size_t stride,
+                   unsigned int flags = 0) const {
+    check(mfgpu_vmult_multi(data.handle, dst.getData(), src.getDataRO(), n_vectors, stride, flags, nullptr), "vmult_multi");
+  }
+  int multi_width() const { return mfgpu_multi_width(data.handle); }
   Number el(unsigned int, unsigned int) const { throw std::runtime_error("matrix-free: no element access"); }
   // laplace_operator_gpu.h:401-418: inverse diagonal, constrained rows 1
   void compute_diagonal() {

@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("MFGPU_LIB") or os.path.join(os.path.dirname(_HERE), "
 
 F64, F32 = 0, 1
 OK, EINVAL = 0, -1  # MFGPU_OK, MFGPU_EINVAL
+EUNSUPPORTED = -4
+MULTI_ADD, MULTI_LOOP, MULTI_FUSED = 1, 2, 4  # flags of Operator.vmult_multi
 UNIFORM_J0, HANGING_NODES, COLORED_SCATTER, NO_SHARED_RECORDS = 1, 2, 1 << 8, 1 << 9
 UPDATABLE_COEFFICIENTS = 1 << 10  # keep what update_coefficients (and Integrator.evaluate's gradients) read on the device
 KERNEL_AUTO, KERNEL_PENCILS, KERNEL_PENCILS_X, KERNEL_PLANES, KERNEL_PLANES_2W = 0, 1, 2, 3, 4  # Desc.kernel
@@ -43,6 +45,7 @@ class Desc(C.Structure):
 
 # every symbol include/mfgpu.h declares (tests check that the library exports all of them)
 SYMBOLS = [
+    "mfgpu_vmult_multi", "mfgpu_multi_width", "mfgpu_plan_multi_groups",
     "mfgpu_create", "mfgpu_vmult", "mfgpu_vmult_add", "mfgpu_n_dofs", "mfgpu_memory_consumption",
     "mfgpu_destroy", "mfgpu_last_error", "mfgpu_plan_stats", "mfgpu_kernel_name", "mfgpu_compute_inverse_diagonal", "mfgpu_set_constrained_values",
     "mfgpu_vec_sadd", "mfgpu_vec_equ", "mfgpu_vec_scale", "mfgpu_vec_divide", "mfgpu_vec_invert", "mfgpu_vec_mul",
@@ -194,13 +197,19 @@ def lib():
         L.mfgpu_vec_copy_pairs_convert.argtypes = [vp, vp, i, vp, i, vp]
         L.mfgpu_vec_chebyshev_start.argtypes = [vp, vp, vp, vp, vp, vp, d, i, z, i, vp]
         L.mfgpu_vec_chebyshev_update.argtypes = [vp, vp, vp, vp, vp, d, d, z, i, vp]
+        L.mfgpu_vmult_multi.argtypes = [vp, vp, vp, C.c_uint32, z, C.c_uint32, vp]
+        L.mfgpu_multi_width.argtypes = [vp]
+        L.mfgpu_plan_multi_groups.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
+                                              C.c_uint32]
         _lib = L
     return _lib
 
 
 def _check(rc):
     if rc != 0:
-        raise MfgpuError(f"mfgpu error {rc}: {lib().mfgpu_last_error().decode()}")
+        err = MfgpuError(f"mfgpu error {rc}: {lib().mfgpu_last_error().decode()}")
+        err.code = rc
+        raise err
 
 
 def np_dtype(number_type):
@@ -564,6 +573,17 @@ class Operator:
     def vmult_add(self, dst, src, stream=None):
         _check(lib().mfgpu_vmult_add(self._h, _ptr(dst), _ptr(src), stream))
 
+    def vmult_multi(self, dst, src, n_vectors, stride=None, add=False, mode=None, stream=None):
+        """mfgpu_vmult_multi: dst_k = A src_k (add: +=) for k < n_vectors; vector k starts at element k * stride of dst and
+        src (default stride: n_dofs).  mode: None (the library's choice), MULTI_LOOP or MULTI_FUSED."""
+        flags = (MULTI_ADD if add else 0) | (mode or 0)
+        _check(lib().mfgpu_vmult_multi(self._h, _ptr(dst), _ptr(src), int(n_vectors),
+                                       self.n() if stride is None else int(stride), flags, stream))
+
+    def multi_width(self):
+        """widest group of vectors one fused sweep serves (1: vmult_multi applies the vectors one by one)"""
+        return int(lib().mfgpu_multi_width(self._h))
+
     def memory_consumption(self):
         return int(lib().mfgpu_memory_consumption(self._h))
 
@@ -834,6 +854,16 @@ def chebyshev_update(x, upd, r, t, dinv, f1, f2, n, number_type, stream=None, ch
     rc = lib().mfgpu_vec_chebyshev_update(_ptr(x), _ptr(upd), _ptr(r), _ptr(t), _ptr(dinv), float(f1), float(f2), n,
                                           number_type, stream)
     return _check(rc) if check else rc
+
+
+def multi_groups(n_vectors, widths):
+    """how vmult_multi cuts n_vectors into groups for the given fused widths (descending); host only"""
+    w = (C.c_uint32 * max(len(widths), 1))(*widths)
+    out = (C.c_uint32 * max(int(n_vectors), 1))()
+    n = lib().mfgpu_plan_multi_groups(int(n_vectors), w, len(widths), out, len(out))
+    if n < 0:
+        _check(n)
+    return [int(out[i]) for i in range(n)]
 
 
 def synchronize():

@@ -163,6 +163,35 @@ int mfgpu_vmult(mfgpu_handle *h, void *dst_dev, const void *src_dev, void *strea
 /* laplace_operator_gpu.h:286-303: dst += A src on free rows, dst_c += src_c on constrained rows. */
 int mfgpu_vmult_add(mfgpu_handle *h, void *dst_dev, const void *src_dev, void *stream);
 
+/* ---- the operator applied to several vectors at once (the components of a vector Laplacian, several right-hand sides,
+ * block Krylov methods).  On general geometry (3D, no MFGPU_UNIFORM_J0: apply_batches_g) an apply mostly streams the
+ * folded metric, which does not depend on the vector; a FUSED group of 2 or 3 vectors reads it, the dof lists and the
+ * index runs once (apply_batches_gm, reduce_classes_multi).  Every other handle -- 2D, the uniform-Jacobian families,
+ * coloured scatter -- has no fused instantiation and applies the vectors one by one.                                  */
+#define MFGPU_MULTI_ADD   (1u << 0) /* vmult_add semantics for every vector */
+#define MFGPU_MULTI_LOOP  (1u << 1) /* one single-vector apply per vector (tests, A/B inside one build) */
+#define MFGPU_MULTI_FUSED (1u << 2) /* fused groups or MFGPU_EUNSUPPORTED: never fall back silently */
+
+/* dst_k = A src_k (MFGPU_MULTI_ADD: dst_k += A src_k on free rows, dst_k += src_k on constrained rows), k < n_vectors;
+ * vector k starts at element k * stride of dst_dev / src_dev (handle's number type).  Asynchronous on `stream` and
+ * ordered like every call on the handle; src is never written; the elements n_dofs .. stride - 1 of every vector are
+ * never touched.  n_vectors is cut into groups of the handle's fused widths, widest first (7 = 3 + 3 + 1); a remainder of
+ * one vector and every handle without a fused instantiation go through the single-vector path.  Without
+ * MFGPU_MULTI_LOOP / _FUSED the library fuses where that measured faster per vector (table in mfgpu_api.hip) and loops
+ * elsewhere; with MFGPU_MULTI_FUSED it fuses wherever mfgpu_multi_width(h) > 1 and returns MFGPU_EUNSUPPORTED where it is
+ * 1 (n_vectors == 1 included: nothing to fuse).  A handle with cell_loop_segments > 1 runs a fused group as ONE segment,
+ * pass 2 after the cell loop on `stream`.
+ * MFGPU_EINVAL, nothing written: n_vectors == 0; stride < n_dofs with n_vectors > 1; LOOP and FUSED both set; unknown
+ * flag bits; the dst range [dst, dst + (n_vectors - 1) * stride + n_dofs) overlaps the src range.
+ * Memory: a fused group of width W sums its shared dofs through W halo buffers.  The handle owns one; the buffers
+ * 2 .. mfgpu_multi_width(h) are allocated together by the FIRST call that runs a fused group.  That is the only
+ * allocation and the only possible host synchronisation of this function: a caller that captures graphs calls it once
+ * before capturing.  The buffers count in mfgpu_memory_consumption from then on; mfgpu_destroy frees them.             */
+int mfgpu_vmult_multi(mfgpu_handle *h, void *dst_dev, const void *src_dev, uint32_t n_vectors, size_t stride,
+                      uint32_t flags, void *stream);
+/* widest group one fused sweep of this handle serves; 1 = every vector is a single apply */
+int mfgpu_multi_width(const mfgpu_handle *h);
+
 /* New coefficients for an operator created with MFGPU_UPDATABLE_COEFFICIENTS (no reference counterpart: the reference
  * evaluates its coefficient once, in reinit).  coefficient_dev / mass_coefficient_dev: DEVICE arrays [n_cells * n^dim] of
  * the handle's number type, values at the quadrature points in the description's cell order; NULL leaves that term as it
@@ -231,6 +260,10 @@ int64_t mfgpu_plan_array_u32(const mfgpu_plan *p, int what, const uint32_t **ptr
 /* bit 0: a handle of this plan reads the shared form of the cell loop's records (it is clearly smaller than 13 + 14);
  * bit 1: the same for pass 2 (20 + 21 against the class arrays built from 8-10)                                    */
 int mfgpu_plan_shares_records(const mfgpu_plan *p);
+/* How mfgpu_vmult_multi cuts n_vectors into groups for a handle with the given fused widths (descending): widest first,
+ * what is left over as groups of 1.  Writes at most `capacity` group sizes and returns their number.                */
+int mfgpu_plan_multi_groups(uint32_t n_vectors, const uint32_t *widths, uint32_t n_widths, uint32_t *groups,
+                            uint32_t capacity);
 int64_t mfgpu_plan_lmap(const mfgpu_plan *p, const uint16_t **ptr);   /* [n_cells*n^dim], plan order */
 int64_t mfgpu_plan_bflags(const mfgpu_plan *p, const uint8_t **ptr);  /* bit0 constrained, bit1 add */
 
