@@ -121,10 +121,17 @@ public:
   GpuVector() = default;
   explicit GpuVector(unsigned int s) { reinit(s); }  // zero-filled (gpu_vec.cu:24-40)
   explicit GpuVector(const std::vector<Number> &host) { *this = host; }
+  // s elements of device memory somebody else owns (the vectors mfgpu_cg hands its preconditioner callback): never
+  // freed, never resized
+  struct borrowed_t {};
+  GpuVector(void *dev, unsigned int s, borrowed_t) : vec_dev(dev), _size(s), borrowed(true) {}
   GpuVector(const GpuVector &) = delete;
   GpuVector &operator=(const GpuVector &) = delete;
-  ~GpuVector() { mfgpu_vec_free(vec_dev); }
+  ~GpuVector() {
+    if (!borrowed) mfgpu_vec_free(vec_dev);
+  }
   void reinit(unsigned int s) {  // gpu_vec.cu:166-182
+    if (borrowed) throw std::runtime_error("GpuVector::reinit: the vector's memory is borrowed");
     mfgpu_vec_free(vec_dev);
     vec_dev = nullptr;
     check(mfgpu_vec_alloc(&vec_dev, s, number_type<Number>()), "GpuVector::reinit");
@@ -150,6 +157,7 @@ public:
   void swap(GpuVector &other) {  // gpu_vec.h:164-172
     std::swap(vec_dev, other.vec_dev);
     std::swap(_size, other._size);
+    std::swap(borrowed, other.borrowed);
   }
   unsigned int memory_consumption() const { return _size * sizeof(Number); }
 
@@ -206,6 +214,7 @@ public:
 private:
   void *vec_dev = nullptr;
   unsigned int _size = 0;
+  bool borrowed = false;
 };
 
 // DiagonalMatrix<GpuVector<Number>> as poisson.cu:242-250 uses it: vmult = element-wise scaling
@@ -319,6 +328,7 @@ public:
     check(mfgpu_vmult_multi(data.handle, dst.getData(), src.getDataRO(), n_vectors, stride, flags, nullptr), "vmult_multi");
   }
   int multi_width() const { return mfgpu_multi_width(data.handle); }
+  mfgpu_handle *get_handle() const { return data.handle; }  // for the objects the C-ABI creates from an operator (mfgpu_cg)
   Number el(unsigned int, unsigned int) const { throw std::runtime_error("matrix-free: no element access"); }
   // laplace_operator_gpu.h:401-418: inverse diagonal, constrained rows 1
   void compute_diagonal() {

@@ -198,6 +198,7 @@ public:
     check(mfgpu_set_constrained_values(handle, v.getData(), (double)value, nullptr), "set_constrained_values");
   }
   std::size_t memory_consumption() const { return mfgpu_memory_consumption(handle); }
+  mfgpu_handle *get_handle() const { return handle; }
   unsigned int level = 0;
 
 private:
@@ -366,6 +367,7 @@ public:
   std::size_t memory_consumption() const {
     return r.memory_consumption() + t.memory_consumption() + upd.memory_consumption();
   }
+  const AdditionalData &get_additional_data() const { return data; }
 
 private:
   void run(VectorType &x, const VectorType &b, bool zero_start) const {

@@ -151,5 +151,79 @@ private:
   SolverControl &control;
 };
 
+// The same solver with its loop on the device (mfgpu_cg, include/mfgpu.h): the scalars stay in a device state block, the
+// host reads them once every check_every iterations.  PreconditionChebyshev maps to MFGPU_CG_CHEBYSHEV (its sweep, from
+// its lambda_max, degree and smoothing range; A must be the matrix it was initialised with), DiagonalMatrix to
+// MFGPU_CG_JACOBI, anything else with a vmult(z, r) is called back once per iteration (a V-cycle).  A must give its
+// mfgpu_handle (get_handle()).
+template <typename VectorType>
+class SolverCGDevice {
+public:
+  typedef typename VectorType::value_type Number;
+  explicit SolverCGDevice(SolverControl &control, unsigned int check_every = 10) : control(control), check_every(check_every) {}
+  template <typename MatrixType, typename ChebyshevMatrixType>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b,
+             const PreconditionChebyshev<ChebyshevMatrixType, VectorType> &prec) {
+    const auto &d = prec.get_additional_data();
+    mfgpu_cg *cg = nullptr;
+    check(mfgpu_cg_create(A.get_handle(), MFGPU_CG_CHEBYSHEV, d.preconditioner->get_vector().getDataRO(), d.degree,
+                          prec.lambda_max, d.smoothing_range, &cg), "SolverCGDevice");
+    run(cg, x, b);
+  }
+  template <typename MatrixType>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b, const DiagonalMatrix<Number> &prec) {
+    mfgpu_cg *cg = nullptr;
+    check(mfgpu_cg_create(A.get_handle(), MFGPU_CG_JACOBI, prec.get_vector().getDataRO(), 0, 0, 0, &cg), "SolverCGDevice");
+    run(cg, x, b);
+  }
+  template <typename MatrixType, typename PreconditionerType>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b, const PreconditionerType &prec) {
+    mfgpu_cg *cg = nullptr;
+    check(mfgpu_cg_create(A.get_handle(), MFGPU_CG_CALLBACK, nullptr, 0, 0, 0, &cg), "SolverCGDevice");
+    Callback<PreconditionerType> ctx{&prec, b.size(), std::string()};
+    const int rc = mfgpu_cg_set_callback(cg, &Callback<PreconditionerType>::call, &ctx);
+    if (rc != 0) {
+      mfgpu_cg_destroy(cg);
+      check(rc, "SolverCGDevice");
+    }
+    run(cg, x, b, &ctx.error);
+  }
+
+private:
+  // z = prec^-1 r on the solver's vectors; no exception crosses the C-ABI
+  template <typename PreconditionerType>
+  struct Callback {
+    const PreconditionerType *prec;
+    unsigned int n;
+    std::string error;
+    static int call(void *ctx, void *z_dev, const void *r_dev, void *) {
+      Callback *self = static_cast<Callback *>(ctx);
+      try {
+        VectorType z(z_dev, self->n, typename VectorType::borrowed_t()),
+            r(const_cast<void *>(r_dev), self->n, typename VectorType::borrowed_t());
+        self->prec->vmult(z, r);
+        return 0;
+      } catch (std::exception &e) {
+        self->error = e.what();
+        return MFGPU_EHIP;
+      }
+    }
+  };
+  void run(mfgpu_cg *cg, VectorType &x, const VectorType &b, const std::string *callback_error = nullptr) {
+    if (x.size() != b.size()) x.reinit(b.size());
+    mfgpu_cg_info info{};
+    const int rc = mfgpu_cg_solve(cg, x.getData(), b.getDataRO(), control.tolerance, control.max_steps, check_every,
+                                  nullptr, &info);
+    mfgpu_cg_destroy(cg);
+    if (rc != 0 && callback_error && !callback_error->empty()) throw std::runtime_error("SolverCGDevice: " + *callback_error);
+    check(rc, "SolverCGDevice");
+    control.steps = info.iterations;
+    if (info.status == 2) throw std::runtime_error("SolverCG: no convergence in " + std::to_string(control.max_steps) + " steps");
+    if (info.status == 3) throw std::runtime_error("SolverCG: breakdown, p.Ap is not a positive finite number");
+  }
+  SolverControl &control;
+  unsigned int check_every;
+};
+
 }  // namespace mfgpu_shim
 #endif

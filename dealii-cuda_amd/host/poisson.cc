@@ -12,6 +12,7 @@
 //             preconditioner changes the iteration count, not the solution: any fixed SPD polynomial in D^-1 A gives
 //             the same CG limit, so the L2 error column is comparable, the iteration column is not.
 //   error     u = u_b + x, L2 error on QGauss(p+2) (poisson.cu:277-292)
+//             -DPOISSON_DEVICE_CG (the -devcg binaries): the same CG with its loop on the device, SolverCGDevice
 // usage: poisson-<dim>d-p<k> [-q] [min_cycle] [max_cycle]     (default max_cycle 6 - dim)
 // -q prints one line per cycle (poisson.cu:271-272) with the L2 error appended:
 //   dim  degree  n_dofs  iterations  wall_seconds  l2_error
@@ -76,7 +77,11 @@ void run_cycle(unsigned int cycle) {
   additional_data.preconditioner = system_matrix.get_diagonal_inverse();
   preconditioner.initialize(system_matrix, additional_data);
   SolverControl solver_control(10000, 1e-12 * system_rhs.l2_norm());
+#ifdef POISSON_DEVICE_CG
+  SolverCGDevice<VectorType> cg(solver_control);  // the CG loop on the device (mfgpu_cg): the -devcg binaries
+#else
   SolverCG<VectorType> cg(solver_control);
+#endif
   mfgpu_device_synchronize();
   const auto t0 = std::chrono::steady_clock::now();
   cg.solve(system_matrix, solution_update, system_rhs, preconditioner);

@@ -19,7 +19,11 @@
 #include <limits>
 #include <type_traits>
 
+#ifdef POISSON_DEVICE_CG
+#include "mfgpu_shim_poisson.h"  // SolverCGDevice: the outer CG on the device, the V-cycle through its callback (-devcg)
+#else
 #include "mfgpu_shim_mg.h"
+#endif
 
 using namespace mfgpu_shim;
 
@@ -142,12 +146,27 @@ int run(int n_ref) {
   // x*: zero on the Dirichlet dofs; b = A x*
   std::vector<number> xs(N);
   for (unsigned int i = 0; i < N; ++i) xs[i] = std::sin(0.37 * i) + 0.5 * std::cos(0.011 * i);
-  VectorType x_star(xs), b(N), x(N), r(N), z(N), p(N), q(N);
+  VectorType x_star(xs), b(N), x(N), z(N);
   system_matrix.set_constrained_values(x_star, 0);
   system_matrix.vmult(b, x_star);
 
   mfgpu_device_synchronize();
   const auto t0 = std::chrono::steady_clock::now();
+#ifdef POISSON_DEVICE_CG
+  unsigned int it = 0;
+  {
+    SolverControl solver_control(1000, 1e-12 * b.l2_norm());
+    SolverCGDevice<VectorType> cg(solver_control);
+    try {
+      cg.solve(system_matrix, x, b, preconditioner);
+      it = solver_control.last_step();
+    } catch (std::runtime_error &) {
+      if (solver_control.last_step() < 1000) throw;
+      it = 1001;  // no convergence: what the host loop below leaves in `it`
+    }
+  }
+#else
+  VectorType r(N), p(N), q(N);
   x = number(0);
   r.equ(1, b);
   preconditioner.vmult(z, r);
@@ -166,6 +185,7 @@ int run(int n_ref) {
     p.sadd(rz_new / rz, 1, z);
     rz = rz_new;
   }
+#endif
   mfgpu_device_synchronize();
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   x.add(-1, x_star);

@@ -43,6 +43,23 @@ class Desc(C.Structure):
     ]
 
 
+CG_NONE, CG_JACOBI, CG_CHEBYSHEV, CG_CALLBACK = 0, 1, 2, 3  # preconditioner of CG (MFGPU_CG_*)
+CG_STATE_BYTES, CG_PARTIAL_BYTES = 128, 3 * 2048 * 8  # the fixed device blocks of a CG (mfgpu_cg_create)
+
+
+class CGInfo(C.Structure):
+    """mirror of struct mfgpu_cg_info; status: 0 running, 1 converged, 2 max iterations, 3 breakdown"""
+    _fields_ = [("iterations", C.c_uint32), ("status", C.c_uint32), ("residual", C.c_double),
+                ("initial_residual", C.c_double)]
+
+    def as_tuple(self):
+        return int(self.iterations), int(self.status), float(self.residual), float(self.initial_residual)
+
+
+# int fn(void *ctx, void *z_dev, const void *r_dev, void *stream)
+CG_CALLBACK_TYPE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
 # every symbol include/mfgpu.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "mfgpu_vmult_multi", "mfgpu_multi_width", "mfgpu_plan_multi_groups",
@@ -71,6 +88,8 @@ SYMBOLS = [
     "mfgpu_desc_size",
     "mfgpu_update_coefficients", "mfgpu_level_update_coefficients", "mfgpu_integrator_update_coefficients",
     "mfgpu_integrator_evaluate",
+    "mfgpu_cg_create", "mfgpu_cg_set_callback", "mfgpu_cg_begin", "mfgpu_cg_iterate", "mfgpu_cg_status", "mfgpu_cg_solve",
+    "mfgpu_cg_memory_consumption", "mfgpu_cg_destroy", "mfgpu_cg_chebyshev_scalars",
 ]
 
 _lib = None
@@ -201,6 +220,18 @@ def lib():
         L.mfgpu_multi_width.argtypes = [vp]
         L.mfgpu_plan_multi_groups.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                               C.c_uint32]
+        u32 = C.c_uint32
+        L.mfgpu_cg_create.argtypes = [vp, i, vp, u32, d, d, C.POINTER(vp)]
+        L.mfgpu_cg_set_callback.argtypes = [vp, CG_CALLBACK_TYPE, vp]
+        L.mfgpu_cg_begin.argtypes = [vp, vp, vp, d, u32, vp]
+        L.mfgpu_cg_iterate.argtypes = [vp, u32, vp]
+        L.mfgpu_cg_status.argtypes = [vp, vp, C.POINTER(CGInfo)]
+        L.mfgpu_cg_solve.argtypes = [vp, vp, vp, d, u32, u32, vp, C.POINTER(CGInfo)]
+        L.mfgpu_cg_memory_consumption.argtypes = [vp]
+        L.mfgpu_cg_memory_consumption.restype = C.c_size_t
+        L.mfgpu_cg_destroy.argtypes = [vp]
+        L.mfgpu_cg_destroy.restype = None
+        L.mfgpu_cg_chebyshev_scalars.argtypes = [u32, d, d, C.POINTER(d)]
         _lib = L
     return _lib
 
@@ -473,8 +504,15 @@ class DeviceVector:
         _check(lib().mfgpu_vec_alloc(C.byref(p), self.n, number_type))
         self.ptr = p.value
 
+    @classmethod
+    def view(cls, ptr, n, number_type=F64):
+        """n elements at a device address somebody else owns (the vectors a CG callback is handed): never freed here"""
+        v = cls.__new__(cls)
+        v.n, v.number_type, v.ptr, v._borrowed = int(n), number_type, int(ptr), True
+        return v
+
     def __del__(self):
-        if getattr(self, "ptr", None) and _lib is not None:
+        if getattr(self, "ptr", None) and _lib is not None and not getattr(self, "_borrowed", False):
             _lib.mfgpu_vec_free(self.ptr)
             self.ptr = None
 
@@ -628,6 +666,82 @@ class Operator:
         ms = C.c_double()
         _check(lib().mfgpu_profile_read_pass2(self._h, C.byref(ms)))
         return ms.value
+
+
+def cg_chebyshev_scalars(degree, lambda_max, smoothing_range):
+    """the 2 * degree - 1 scalars of the Chebyshev sweep (mfgpu_cg_chebyshev_scalars): f[0] = 1 / theta, then (f1, f2) per
+    inner step; host only"""
+    out = (C.c_double * max(2 * int(degree) - 1, 1))()
+    _check(lib().mfgpu_cg_chebyshev_scalars(int(degree), float(lambda_max), float(smoothing_range), out))
+    return np.array(out[:2 * int(degree) - 1], dtype=np.float64)
+
+
+class CG:
+    """Device-resident conjugate gradients on an Operator (mfgpu_cg_*): begin and iterate only enqueue work, status is the
+    only blocking call.  preconditioner: CG_NONE, CG_JACOBI (inv_diag), CG_CHEBYSHEV (inv_diag, degree, lambda_max,
+    smoothing_range) or CG_CALLBACK with callback(z, r, stream) -> 0 / None or an error code, where z and r are
+    DeviceVector views of the solver's vectors and the callback enqueues z = M^-1 r on `stream`.  The operator, inv_diag, x
+    and b must outlive the solve.  The methods return the raw code with check=False."""
+
+    def __init__(self, op: "Operator", preconditioner=CG_NONE, inv_diag=None, degree=0, lambda_max=0.0,
+                 smoothing_range=0.0, callback=None):
+        self._op, self._inv_diag = op, inv_diag
+        self._cb = self._cb_error = None
+        self.n, self.number_type = op.n(), op.number_type
+        h = C.c_void_p()
+        _check(lib().mfgpu_cg_create(op._h, int(preconditioner), _optr(inv_diag), int(degree), float(lambda_max),
+                                     float(smoothing_range), C.byref(h)))
+        self._h = h
+        if callback is not None:
+            self.set_callback(callback)
+
+    def set_callback(self, callback):
+        def trampoline(_ctx, z, r, stream):
+            try:
+                rc = callback(DeviceVector.view(z, self.n, self.number_type),
+                              DeviceVector.view(r, self.n, self.number_type), stream)
+                return 0 if rc is None else int(rc)
+            except Exception as e:  # no exception crosses the C-ABI: kept for _done
+                self._cb_error = e
+                return EINVAL
+
+        cb = CG_CALLBACK_TYPE(trampoline)
+        _check(lib().mfgpu_cg_set_callback(self._h, cb, None))
+        self._cb = cb  # the library keeps the function pointer: keep the ctypes object alive
+
+    def _done(self, rc, check):
+        e, self._cb_error = self._cb_error, None
+        if e is not None:
+            raise e
+        return _check(rc) if check else rc
+
+    def destroy(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_cg_destroy(self._h)
+            self._h = None
+
+    __del__ = destroy
+
+    def begin(self, x, b, tolerance, max_iterations, stream=None, check=True):
+        return self._done(lib().mfgpu_cg_begin(self._h, _optr(x), _optr(b), float(tolerance), int(max_iterations), stream),
+                          check)
+
+    def iterate(self, n_iterations=1, stream=None, check=True):
+        return self._done(lib().mfgpu_cg_iterate(self._h, int(n_iterations), stream), check)
+
+    def status(self, stream=None):
+        info = CGInfo()
+        _check(lib().mfgpu_cg_status(self._h, stream, C.byref(info)))
+        return info
+
+    def solve(self, x, b, tolerance, max_iterations, check_every=10, stream=None):
+        info = CGInfo()
+        self._done(lib().mfgpu_cg_solve(self._h, _optr(x), _optr(b), float(tolerance), int(max_iterations),
+                                        int(check_every), stream, C.byref(info)), True)
+        return info
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_cg_memory_consumption(self._h))
 
 
 class Integrator:

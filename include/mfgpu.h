@@ -408,6 +408,66 @@ int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const 
 int mfgpu_vec_chebyshev_update(void *x, void *upd, void *r, const void *t, const void *dinv, double f1, double f2,
                                size_t n, int number_type, void *stream);
 
+/* ---- device-resident conjugate gradients (no reference counterpart: the reference calls deal.II's
+ * SolverCG, whose three scalar products per iteration each stop the host).  The algorithm is SolverCG::solve of
+ * host/mfgpu_shim_poisson.h: zero start (x = 0, r = b), absolute tolerance tested against sqrt(r.r), 0 iterations when
+ * |b| <= tolerance.  Every scalar (rz, pq, rr, alpha, beta, tolerance, iteration count, status) lives in a device state
+ * block that the kernels read directly; the sums accumulate in double over a fixed grid in a fixed order; alpha and beta
+ * are formed in double and rounded to the handle's number type before any element-wise use.
+ * mfgpu_cg_begin and mfgpu_cg_iterate only enqueue work on `stream` (no allocation, no synchronisation, no host
+ * read-back: they can be captured in a graph); mfgpu_cg_status is the only blocking call.
+ * Freeze rule: the status leaves 0 when sqrt(r.r) <= tolerance (1), when the count reaches max_iterations (2) or when p.q
+ * is not a positive finite number (3).  From then on every solver kernel returns without writing (the operator and the
+ * preconditioner still run, on the unchanged p and r), so x, r, the count and the residual do not depend on how many
+ * iterations were enqueued past the end, nor on check_every.
+ * Like its handle, one mfgpu_cg is used on one stream at a time; x, b and inv_diag must stay valid and unchanged (x:
+ * untouched by others) from mfgpu_cg_begin until the solve is over.                                                    */
+#define MFGPU_CG_NONE 0       /* z = r */
+#define MFGPU_CG_JACOBI 1     /* z = inv_diag .* r, fused, z never stored */
+#define MFGPU_CG_CHEBYSHEV 2  /* z = p(A) r: the sweep PreconditionChebyshev::vmult runs with fused_updates, zero start,
+                                 on inv_diag, with (degree, lambda_max, smoothing_range) given by the caller */
+#define MFGPU_CG_CALLBACK 3   /* z = fn(ctx, z_dev, r_dev, stream): any preconditioner the caller can enqueue (a V-cycle) */
+
+typedef struct mfgpu_cg mfgpu_cg;
+typedef struct mfgpu_cg_info {
+  uint32_t iterations;
+  uint32_t status; /* 0 running 1 converged 2 max iterations 3 breakdown */
+  double residual; /* sqrt(r.r) after `iterations` iterations */
+  double initial_residual;
+} mfgpu_cg_info;
+
+/* All allocation happens here: the work vectors r, p, q (3 vectors of n_dofs numbers; MFGPU_CG_CALLBACK: + z = 4;
+ * MFGPU_CG_CHEBYSHEV: + z and the sweep's three vectors = 7), 3 * 2048 doubles of partial sums, the 128-byte state block
+ * -- mfgpu_cg_memory_consumption is exactly their sum -- and a pinned host mirror of the state block.  inv_diag_dev
+ * (handle's number type, e.g. from mfgpu_compute_inverse_diagonal) is read by JACOBI and CHEBYSHEV and not copied; the
+ * Chebyshev arguments are read by CHEBYSHEV only.  MFGPU_EINVAL, nothing created: null A / out, unknown preconditioner,
+ * inv_diag_dev missing for JACOBI / CHEBYSHEV, CHEBYSHEV with degree 0, lambda_max <= 0 or smoothing_range <= 1.       */
+int mfgpu_cg_create(mfgpu_handle *A, int preconditioner, const void *inv_diag_dev, uint32_t chebyshev_degree,
+                    double lambda_max, double smoothing_range, mfgpu_cg **out);
+/* MFGPU_CG_CALLBACK: fn enqueues z = M^-1 r on `stream` (and nothing that waits for the host, if the caller captures
+ * graphs); a non-zero return ends mfgpu_cg_begin / mfgpu_cg_iterate with that code */
+int mfgpu_cg_set_callback(mfgpu_cg *s, int (*fn)(void *ctx, void *z_dev, const void *r_dev, void *stream), void *ctx);
+/* x = 0, r = b, z = M^-1 r, p = z; status 1 with 0 iterations if |b| <= tolerance.  MFGPU_EINVAL, nothing written: null
+ * pointers, CALLBACK without a callback, x overlapping b.  16-byte accesses when x, b and inv_diag are 16-byte aligned. */
+int mfgpu_cg_begin(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations, void *stream);
+/* n_iterations more iterations (MFGPU_EINVAL before mfgpu_cg_begin): per iteration vmult, the partial sums of p.q, one
+ * kernel for alpha, x += alpha p, r -= alpha q and the partial sums of r.r (NONE, JACOBI: and of r.z), the
+ * preconditioner and the partial sums of r.z (CHEBYSHEV, CALLBACK), one kernel for count, status, beta, p = z + beta p */
+int mfgpu_cg_iterate(mfgpu_cg *s, uint32_t n_iterations, void *stream);
+/* one asynchronous copy of the state block into the pinned mirror and a stream synchronisation; at any point after
+ * mfgpu_cg_begin (MFGPU_EINVAL before) */
+int mfgpu_cg_status(mfgpu_cg *s, void *stream, mfgpu_cg_info *info);
+/* begin; { iterate(check_every); status } until the status leaves 0.  check_every == 0: MFGPU_EINVAL */
+int mfgpu_cg_solve(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations,
+                   uint32_t check_every, void *stream, mfgpu_cg_info *info);
+size_t mfgpu_cg_memory_consumption(const mfgpu_cg *s);
+void mfgpu_cg_destroy(mfgpu_cg *s);
+/* host only, no device: the scalars of the Chebyshev sweep, f[0] = 1/theta, then (f1, f2) per inner step k = 1..degree-1
+ * (lambda_min = lambda_max / smoothing_range, theta and delta the centre and half width of [lambda_min, lambda_max],
+ * sigma = theta / delta, rho_0 = 1 / sigma, rho_new = 1 / (2 sigma - rho), f1 = rho_new rho, f2 = 2 rho_new / delta).
+ * MFGPU_EINVAL: null f, degree 0, lambda_max <= 0, smoothing_range <= 1.                                               */
+int mfgpu_cg_chebyshev_scalars(uint32_t degree, double lambda_max, double smoothing_range, double *f /* [2*degree-1] */);
+
 /* ---- cell integrals of a Poisson solve (poisson.cu:152-229, 277-292) ------------------------------------------
  * A separate object created from the same description as the operator; it keeps its own device copy of the geometry
  * (loc2glob, constraint mask, quadrature points, JxW, the folded coefficient) and leaves mfgpu_handle untouched.
