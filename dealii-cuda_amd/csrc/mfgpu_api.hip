@@ -166,9 +166,8 @@ hipError_t bind_kernel(const mfgpu_handle *h, PlaneKernel pk, BatchKernel bk, bo
 
 // batches [a.batch0, a.batch_end) less the hole, nbat of them, in a bound kernel: a persistent grid of as many
 // workgroups as fit on the chip (each loops over its batches)
-template <typename T>
-int launch_bound(mfgpu_handle *h, int which, const ApplyArgs<T> &a, uint32_t nbat, hipStream_t st) {
-  const CellKernel<T> &k = h->kernel<T>(which);
+template <typename T, typename Args>
+int launch_bound(mfgpu_handle *h, const CellKernel<T, Args> &k, const Args &a, uint32_t nbat, hipStream_t st) {
   if (!k.launch[0]) {
     set_error("cell-loop kernel not bound");
     return MFGPU_EINVAL;
@@ -489,7 +488,7 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
     for (const int w : kFusedWidths) {
       if (!fused_kernel_exists(h->batches, P.n, d.number_type, h->hn, h->d_mass.get() != nullptr, w)) continue;
       MultiKernel<T> &mk = h->multi<T>(w);
-      if (gm_bind<T>(P.n, h->hn, h->d_mass.get() != nullptr, w, P.max_batch_dofs, &mk) != hipSuccess) {
+      if (g_bind_width<T>(P.n, h->hn, false, h->d_mass.get() != nullptr, w, P.max_batch_dofs, &mk) != hipSuccess) {
         (void)hipGetLastError();
         mk = MultiKernel<T>();
       } else
@@ -584,19 +583,19 @@ int launch_cells(mfgpu_handle *h, ApplyArgs<T> a, uint32_t b0, uint32_t b1, hipS
   if (b0 < nplain) {  // the batches of cells without a hanging-node mask (all batches on conforming meshes)
     a.batch0 = b0;
     a.batch_end = b1 < nplain ? b1 : nplain;
-    if (const int rc = launch_bound<T>(h, mfgpu_handle::kPlain, a, a.batch_end - a.batch0, st)) return rc;
+    if (const int rc = launch_bound(h, h->kernel<T>(mfgpu_handle::kPlain), a, a.batch_end - a.batch0, st)) return rc;
     b0 = a.batch_end;
   }
   if (b0 < npl && b0 < b1) {  // plane batches of cells WITH a mask
     a.batch0 = b0;
     a.batch_end = b1 < npl ? b1 : npl;
-    if (const int rc = launch_bound<T>(h, mfgpu_handle::kMasked, a, a.batch_end - a.batch0, st)) return rc;
+    if (const int rc = launch_bound(h, h->kernel<T>(mfgpu_handle::kMasked), a, a.batch_end - a.batch0, st)) return rc;
     b0 = a.batch_end;
   }
   if (b0 >= b1) return 0;
   a.batch0 = b0;
   a.batch_end = b1;
-  return launch_bound<T>(h, mfgpu_handle::kBatch, a, b1 - b0, st);
+  return launch_bound(h, h->kernel<T>(mfgpu_handle::kBatch), a, b1 - b0, st);
 }
 
 template <typename T>
@@ -721,9 +720,7 @@ int multi_fused_group(mfgpu_handle *h, T *dst, const T *src, int nv, size_t stri
   const uint32_t nbat = (uint32_t)(h->plan.batch_cell_off.size() - 1);
   a.batch0 = 0;
   a.batch_end = nbat;
-  uint32_t grid = (uint32_t)(k.per_cu < 1 ? 1 : k.per_cu) * h->n_cus;
-  if (h->max_workgroups && h->max_workgroups < grid) grid = h->max_workgroups;
-  HIP_TRY(k.launch[add != 0](a, h->S.data(), h->Dt.data(), k.lds, nbat < grid ? nbat : grid, st));
+  if (const int rc = launch_bound(h, k, a, nbat, st)) return rc;
   for (size_t g = 0; g < h->d_p2arr.size(); ++g)
     HIP_TRY(reduce_classes_multi_launch<T>(nv, dst, src, stride, a.halos, h->d_p2arr[g].get(), h->d_p2tiles[g].get(),
                                            h->n_p2tiles[g], add, st));
@@ -882,7 +879,8 @@ int handle_cells_two_ranges(mfgpu_handle *h, uint32_t b0, uint32_t b1, uint32_t 
     a.hole0 = b1;
     a.hole_len = c0 - b1;
     using T = typename std::remove_const<typename std::remove_pointer<decltype(a.src)>::type>::type;
-    return launch_bound<T>(h, plain ? mfgpu_handle::kPlain : mfgpu_handle::kMasked, a, (b1 - b0) + (c1 - c0), st);
+    return launch_bound(h, h->kernel<T>(plain ? mfgpu_handle::kPlain : mfgpu_handle::kMasked), a, (b1 - b0) + (c1 - c0),
+                        st);
   };
   return h->number_type == MFGPU_F64 ? run(make_args<double>(h, dst, src, add)) : run(make_args<float>(h, dst, src, add));
 }

@@ -123,6 +123,57 @@ __device__ __forceinline__ void lds_add(T *p, T v) {
   unsafeAtomicAdd(p, v);  // ds_add_f64 / ds_add_f32: no CAS loop on gfx950
 }
 
+// Load of a read-once stream (dof lists, index runs, coefficients): non-temporal, see xcd_batch_range
+template <typename U>
+__device__ __forceinline__ U stream_load(const U *p) {
+#ifdef MFGPU_PLAIN_STREAMS
+  return *p;
+#else
+  return __builtin_nontemporal_load(p);
+#endif
+}
+
+// entry i of an x-pencil index run: n 16-bit batch-local dof ids packed into (n + 1) / 2 words
+template <int n>
+__device__ __forceinline__ int ix_at(const uint32_t (&w)[(n + 1) / 2], int i) {
+  return (int)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+}
+
+// Persistent workgroups; XCD-aware batch order: this workgroup walks the batches b, b + bstride, ... < bend of the
+// launch's [batch0, batch_end).  Workgroups are dispatched round-robin over the 8 XCDs (block i runs on XCD i % 8) and
+// every XCD has its own L2.  Consecutive batches are neighbours in the mesh (two-pass plans keep the spatial creation
+// order): they share halo dofs and the 128-byte lines their 13-dof runs of src straddle.  Each XCD therefore gets ONE
+// contiguous range of batches, walked by its workgroups in steps of gridDim/8, so that the batches in flight on one
+// XCD are neighbours and hit in its L2: fabric reads 500 -> 404 MB per launch (apply_batches_x) together with the
+// spatial plan order.  (Handing each XCD the x-th eighth of every ROUND of gridDim batches instead balances better
+// when batch cost varies -- apply_batches does that for hanging-node meshes -- but leaves three XCDs idle in the
+// partial last round of a uniform mesh: 4 % slower there.)
+// (A contiguous run of batches per workgroup instead -- the same lines re-requested one batch later -- fetched 5 % more
+// and was 4 % slower: the L2 turns over in less than one batch time.)
+// The read-once streams (stream_load) are loaded non-temporally so that they do not push src lines out of the L2; the
+// result stores are plain: neighbouring batches write adjacent runs of dst at about the same time and the L2 merges
+// them into full lines (non-temporal stores: +24 % written bytes, +3 % time).
+// The plane kernels pass batch_end less the length of the launch's hole and map b past the hole themselves.
+__device__ __forceinline__ void xcd_batch_range(const uint32_t batch0, const uint32_t batch_end, uint32_t &b,
+                                                uint32_t &bend, uint32_t &bstride) {
+  const uint32_t nbt = batch_end - batch0, G = gridDim.x;
+  if (G >= 8 && nbt >= G) {
+    // XCD x runs the blocks i = x, x + 8, ...: w(x) = (G - x + 7) / 8 of them; its batch range is proportional to
+    // that count (any grid size, e.g. one that divides the batch count evenly)
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
+    const uint32_t q = G >> 3, rem = G & 7u;
+    const uint32_t wlo = xcd * q + (xcd < rem ? xcd : rem);  // blocks of the XCDs before this one
+    const uint32_t w = q + (xcd < rem ? 1u : 0u);
+    b = batch0 + (uint32_t)((uint64_t)nbt * wlo / G) + slot;
+    bend = batch0 + (uint32_t)((uint64_t)nbt * (wlo + w) / G);
+    bstride = w;
+  } else {
+    b = batch0 + blockIdx.x;
+    bend = batch_end;
+    bstride = G;
+  }
+}
+
 // Diagnostic build only (-DMFGPU_STAMPS, lib/libmfgpu_diag.so): lane 0 of every workgroup records
 // s_memtime at phase boundaries into a buffer no kernel reads.  The product build has no stamps.
 #ifdef MFGPU_STAMPS

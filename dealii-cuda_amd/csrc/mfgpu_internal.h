@@ -195,11 +195,12 @@ constexpr bool kernel_exists(PlaneKernel k, int n, int number_type, bool hn, boo
 constexpr bool kernel_exists(BatchKernel k, int n, int /*number_type*/, bool /*hn*/, bool sh, bool /*mass*/) {
   return k != BatchKernel::none && n >= 2 && n <= 7 && !sh;
 }
-// ... and of which FUSED instantiations exist (mfgpu_vmult_multi): apply_batches_gm<n, T, HN, MASS, NV> applies the
-// operator to a group of nv vectors in one sweep.  Only the g family has them: n = 2..7, both number types, HN and MASS
-// in every combination, widths kFusedWidths -- less, in double with HN, width 3 at n = 6, 7 and width 2 at n = 7, which
-// spill even with one wave per SIMD (80-488 B per lane).  gm_bind instantiates exactly these, create_arrays binds the handle's, and
-// a (family, degree, width) that is not here falls back to single applies.
+// ... and of which FUSED instantiations exist (mfgpu_vmult_multi): apply_batches_g<n, T, HN, MASS, NV> at a width
+// NV > 1 applies the operator to a group of NV vectors in one sweep (NV = 1 is the single apply above).  Only the g
+// family has a width: n = 2..7, both number types, HN and MASS in every combination, widths kFusedWidths -- less, in
+// double with HN, width 3 at n = 6, 7 and width 2 at n = 7, which spill even with one wave per SIMD (80-488 B per lane).
+// g_bind_width instantiates exactly these, create_arrays binds the handle's, and a (family, degree, width) that is not
+// here falls back to single applies.
 constexpr int kFusedWidths[] = {3, 2};  // widest first
 constexpr bool fused_kernel_exists(BatchKernel k, int n, int number_type, bool hn, bool /*mass*/, int nv) {
   return k == BatchKernel::g && n >= 2 && n <= 7 && (nv == 2 || nv == 3) &&

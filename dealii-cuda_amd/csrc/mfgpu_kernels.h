@@ -54,9 +54,9 @@ struct ApplyArgs {
   const T *massp = nullptr;
 };
 
-// mfgpu_vmult_multi, fused groups (apply_batches_gm, reduce_classes_multi): the arguments of a single apply -- dst, src
+// mfgpu_vmult_multi, fused groups (apply_batches_g at width NV = 2, 3): the arguments of a single apply -- dst, src
 // and halo are those of vector 0 -- plus what a group adds.  A struct of its own: ApplyArgs<T> is passed by value to
-// every existing kernel and stays byte for byte what it is.
+// every single-vector kernel (apply_batches_g at width 1 among them) and stays byte for byte what it is.
 constexpr int kMaxFusedWidth = 3;
 template <typename T>
 struct MultiArgs : ApplyArgs<T> {
@@ -91,8 +91,8 @@ inline Tables<T, n> make_tables(const double *S, const double *Dt) {
 // admits (else hipErrorInvalidValue) and hands it to bind_cell_kernel, which sets the dynamic-LDS attribute of
 // precisely the kernels whose launch entries it stores.  So what can be launched has been configured.
 // launch[add](a, S, Dt, lds, grid, st) runs batches [a.batch0, a.batch_end) with the 1D tables made from S, Dt.
-// (Args: the kernel's by-value argument struct -- ApplyArgs<T> for every single-vector family, MultiArgs<T> for the
-// fused family of mfgpu_vmult_multi)
+// (Args: the kernel's by-value argument struct -- ApplyArgs<T> for every single-vector kernel, MultiArgs<T> for the
+// g family at the fused widths of mfgpu_vmult_multi)
 template <typename T, typename Args = ApplyArgs<T>>
 struct CellKernel {
   size_t lds = 0;  // dynamic LDS bytes per workgroup (set first, also when binding fails)
@@ -157,12 +157,13 @@ MFGPU_CELL_LOOP_FAMILY(g2)
 MFGPU_CELL_LOOP_FAMILY(p)
 MFGPU_CELL_LOOP_FAMILY(q)
 #undef MFGPU_CELL_LOOP_FAMILY
-// the fused family of the g family (mfgpu_kernels_gm.hip): the instantiation (n, hn, mass) of width nv that
-// fused_kernel_exists admits, else hipErrorInvalidValue (also where the plan's batches need more LDS than a CU has)
+// the g family by width (mfgpu_kernels_g.hip): g_bind is width 1; with a MultiKernel<T> the fused instantiation
+// (n, hn, mass) of width nv = 2, 3 that fused_kernel_exists admits, else hipErrorInvalidValue (also where the plan's
+// batches need more LDS than a CU has)
 template <typename T>
 using MultiKernel = CellKernel<T, MultiArgs<T>>;
-template <typename T>
-hipError_t gm_bind(int n, bool hn, bool mass, int nv, uint32_t nb_max, MultiKernel<T> *k);
+template <typename T, typename Args>
+hipError_t g_bind_width(int n, bool hn, bool sh, bool mass, int nv, uint32_t nb_max, CellKernel<T, Args> *k);
 
 // pass 2, class-sorted structure-of-arrays form (mfgpu_pass2.hip)
 void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<uint32_t> &s_off,
@@ -170,8 +171,8 @@ void build_pass2_classes(const std::vector<uint32_t> &sdofs, const std::vector<u
 template <typename T>
 hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint32_t *arr, const uint32_t *tiles,
                                  uint32_t n_tiles, int add, hipStream_t st);
-// ... for a fused group of nv = 2, 3 vectors: the class arrays are read once per tile; vector v's sums come from
-// halos[v] and go to dst + v * stride (identity rows: src + v * stride), each in reduce_classes' order
+// ... the same kernel at width nv = 2, 3 for a fused group: the class arrays are read once per tile; vector v's sums
+// come from halos[v] and go to dst + v * stride (identity rows: src + v * stride), each in the single apply's order
 template <typename T>
 hipError_t reduce_classes_multi_launch(int nv, T *dst, const T *src, size_t stride, T *const *halos, const uint32_t *arr,
                                        const uint32_t *tiles, uint32_t n_tiles, int add, hipStream_t st);

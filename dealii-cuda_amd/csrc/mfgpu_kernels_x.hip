@@ -23,19 +23,6 @@
 
 namespace mfgpu {
 
-#ifdef MFGPU_PLAIN_STREAMS
-template <typename U>
-__device__ __forceinline__ U stream_load(const U *p) { return *p; }
-#else
-template <typename U>
-__device__ __forceinline__ U stream_load(const U *p) { return __builtin_nontemporal_load(p); }
-#endif
-
-template <int n>
-__device__ __forceinline__ int ix_at(const uint32_t (&w)[(n + 1) / 2], int i) {
-  return (int)((w[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-}
-
 // One chunk of cells: a thread owns pencil (pa, pb) of its cell.  u: the cell's source values along the
 // thread's x-pencil; ixw: batch-local dof ids of that pencil (packed 16-bit).  stage_next() is called
 // where the coefficient buffer is dead.
@@ -228,40 +215,8 @@ apply_batches_x(const ApplyArgs<T> A, const Tables<T, n> tab) {
   uint32_t *Gp = reinterpret_cast<uint32_t *>(Wl + n2);
 
   const int tid = threadIdx.x;
-  // Persistent workgroups; XCD-aware batch order.  Workgroups are dispatched round-robin over the 8 XCDs
-  // (block i runs on XCD i % 8) and every XCD has its own L2.  Consecutive batches are neighbours in the
-  // mesh (two-pass plans keep the spatial creation order): they share halo dofs and the 128-byte lines
-  // their 13-dof runs of src straddle.  Each XCD therefore gets ONE contiguous range of batches, walked by
-  // its workgroups in steps of gridDim/8, so that the batches in flight on one XCD are neighbours and hit
-  // in its L2: fabric reads 500 -> 404 MB per launch together with the spatial plan order.  (Handing each
-  // XCD the x-th eighth of every ROUND of gridDim batches instead balances better when batch cost varies
-  // -- apply_batches does that for hanging-node meshes -- but leaves three XCDs idle in the partial last
-  // round of a uniform mesh: 4 % slower here.)
-  // (A contiguous run of batches per workgroup instead -- the same lines re-requested one batch later --
-  // fetched 5 % more and was 4 % slower: the L2 turns over in less than one batch time.)
-  // The read-once streams (dof lists, index runs, coefficients) are loaded non-temporally so that they
-  // do not push src lines out of the L2; the result stores are plain: neighbouring batches write
-  // adjacent runs of dst at about the same time and the L2 merges them into full lines (non-temporal
-  // stores: +24 % written bytes, +3 % time).
   uint32_t b, bstride, bend;
-  {
-    const uint32_t nbt = A.batch_end - A.batch0, G = gridDim.x;
-    if (G >= 8 && nbt >= G) {
-      // XCD x runs the blocks i = x, x + 8, ...: w(x) = (G - x + 7) / 8 of them; its batch range is
-      // proportional to that count (any grid size, e.g. one that divides the batch count evenly)
-      const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-      const uint32_t q = G >> 3, rem = G & 7u;
-      const uint32_t wlo = xcd * q + (xcd < rem ? xcd : rem);  // blocks of the XCDs before this one
-      const uint32_t w = q + (xcd < rem ? 1u : 0u);
-      b = A.batch0 + (uint32_t)((uint64_t)nbt * wlo / G) + slot;
-      bend = A.batch0 + (uint32_t)((uint64_t)nbt * (wlo + w) / G);
-      bstride = w;
-    } else {
-      b = A.batch0 + blockIdx.x;
-      bend = A.batch_end;
-      bstride = G;
-    }
-  }
+  xcd_batch_range(A.batch0, A.batch_end, b, bend, bstride);  // persistent workgroups, XCD-aware batch order
   if (b >= bend) return;
 
   const int lc = tid / P;

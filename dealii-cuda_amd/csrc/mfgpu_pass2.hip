@@ -19,8 +19,29 @@ namespace mfgpu {
 
 namespace {
 
-template <typename T, int K>
-__device__ __forceinline__ void reduce_two(T *__restrict__ dst, const T *__restrict__ src, const T *__restrict__ halo,
+// Width NV (mfgpu_vmult_multi): NV = 1 is the single apply, its halo buffer a plain pointer argument; a fused group of
+// NV = 2, 3 vectors passes its halo buffers and the vectors' stride in a GroupHalos<T>.  The dof ids and the K halo
+// slots of a thread's two entries are loaded once; then, per vector, the sums in the same order (slot 0 first,
+// ascending touchers) from that vector's halo buffer into dst + v * stride (identity rows: from src + v * stride).
+template <typename T>
+struct GroupHalos {
+  size_t stride;
+  const T *h[kMaxFusedWidth];
+};
+template <typename T, typename P>
+__device__ __forceinline__ P *vec_at(const T *, P *p, int) { return p; }
+template <typename T, typename P>
+__device__ __forceinline__ P *vec_at(const GroupHalos<T> &g, P *p, int v) { return p + (size_t)v * g.stride; }
+template <typename T>
+__device__ __forceinline__ const T *vec_halo(const T *halo, int) { return halo; }
+template <typename T>
+__device__ __forceinline__ const T *vec_halo(const GroupHalos<T> &g, int v) { return g.h[v]; }
+
+template <typename T, int NV>
+using HalosArg = std::conditional_t<NV == 1, const T *__restrict__, GroupHalos<T>>;
+
+template <typename T, int K, int NV>
+__device__ __forceinline__ void reduce_two(T *__restrict__ dst0, const T *__restrict__ src0, const HalosArg<T, NV> halos,
                                            const uint32_t *__restrict__ p, uint32_t cnt, uint32_t i0, uint32_t k,
                                            int add) {
   // K > 0: compile-time number of partial sums; K == 0: run-time k (rare classes)
@@ -35,90 +56,16 @@ __device__ __forceinline__ void reduce_two(T *__restrict__ dst, const T *__restr
   }
   const bool on0 = d0 != 0xffffffffu, on1 = d1 != 0xffffffffu;
   const uint32_t g0 = d0 & 0x7fffffffu, g1 = d1 & 0x7fffffffu;
-  T v0 = T(0), v1 = T(0), o0 = T(0), o1 = T(0);
-  if (on0) {
-    if (d0 >> 31) {
-      v0 = src[g0];
-    } else {
-      T q[KU];
 #pragma unroll
-      for (int t = 0; t < KU; ++t) q[t] = halo[s0[t]];
-      v0 = q[0];
-#pragma unroll
-      for (int t = 1; t < KU; ++t) v0 += q[t];
-      if (K == 0)
-        for (uint32_t t = 1; t < k; ++t) v0 += halo[p[(size_t)(1 + t) * cnt + i0]];
-    }
-    if (add) o0 = dst[g0];
-  }
-  if (on1) {
-    if (d1 >> 31) {
-      v1 = src[g1];
-    } else {
-      T q[KU];
-#pragma unroll
-      for (int t = 0; t < KU; ++t) q[t] = halo[s1[t]];
-      v1 = q[0];
-#pragma unroll
-      for (int t = 1; t < KU; ++t) v1 += q[t];
-      if (K == 0)
-        for (uint32_t t = 1; t < k; ++t) v1 += halo[p[(size_t)(1 + t) * cnt + i1]];
-    }
-    if (add) o1 = dst[g1];
-  }
-  if (on0) dst[g0] = add ? o0 + v0 : v0;
-  if (on1) dst[g1] = add ? o1 + v1 : v1;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-reduce_classes(T *__restrict__ dst, const T *__restrict__ src, const T *__restrict__ halo,
-               const uint32_t *__restrict__ arr, const uint4 *__restrict__ tiles, int add) {
-  const uint4 td = tiles[blockIdx.x];  // {class base in arr, k, entries of the class (padded), first entry of the tile}
-  const uint32_t *p = arr + td.x;
-  const uint32_t i0 = td.w + threadIdx.x;
-  switch (td.y) {  // wave-uniform
-    case 1: reduce_two<T, 1>(dst, src, halo, p, td.z, i0, 1, add); break;
-    case 2: reduce_two<T, 2>(dst, src, halo, p, td.z, i0, 2, add); break;
-    case 3: reduce_two<T, 3>(dst, src, halo, p, td.z, i0, 3, add); break;
-    case 4: reduce_two<T, 4>(dst, src, halo, p, td.z, i0, 4, add); break;
-    case 8: reduce_two<T, 8>(dst, src, halo, p, td.z, i0, 8, add); break;
-    default: reduce_two<T, 0>(dst, src, halo, p, td.z, i0, td.y, add); break;
-  }
-}
-
-// ---- Fused groups (mfgpu_vmult_multi): reduce_two for NV vectors.  The dof ids and the K halo slots of a thread's two
-// entries are loaded once; then, per vector, the sums in reduce_two's order (slot 0 first, ascending touchers) from
-// that vector's halo buffer into dst + v * stride.
-template <typename T>
-struct MultiHalos {
-  const T *h[kMaxFusedWidth];
-};
-
-template <typename T, int K, int NV>
-__device__ __forceinline__ void reduce_two_multi(T *__restrict__ dst, const T *__restrict__ src, size_t stride,
-                                                 const MultiHalos<T> &halos, const uint32_t *__restrict__ p,
-                                                 uint32_t cnt, uint32_t i0, uint32_t k, int add) {
-  const uint32_t i1 = i0 + 256u;
-  const uint32_t d0 = p[i0], d1 = p[i1];
-  constexpr int KU = K > 0 ? K : 1;
-  uint32_t s0[KU], s1[KU];
-#pragma unroll
-  for (int t = 0; t < KU; ++t) {
-    s0[t] = p[(size_t)(1 + t) * cnt + i0];
-    s1[t] = p[(size_t)(1 + t) * cnt + i1];
-  }
-  const bool on0 = d0 != 0xffffffffu, on1 = d1 != 0xffffffffu;
-  const uint32_t g0 = d0 & 0x7fffffffu, g1 = d1 & 0x7fffffffu;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const T *__restrict__ halo = halos.h[v];
-    const T *__restrict__ sv = src + (size_t)v * stride;
-    T *__restrict__ dv = dst + (size_t)v * stride;
+  for (int iv = 0; iv < NV; ++iv) {
+    const int v = NV == 1 ? 0 : iv;  // (with the break below: no loop at NV = 1, see apply_batches_g)
+    const T *__restrict__ halo = vec_halo(halos, v);
+    const T *__restrict__ src = vec_at(halos, src0, v);
+    T *__restrict__ dst = vec_at(halos, dst0, v);
     T v0 = T(0), v1 = T(0), o0 = T(0), o1 = T(0);
     if (on0) {
       if (d0 >> 31) {
-        v0 = sv[g0];
+        v0 = src[g0];
       } else {
         T q[KU];
 #pragma unroll
@@ -129,11 +76,11 @@ __device__ __forceinline__ void reduce_two_multi(T *__restrict__ dst, const T *_
         if (K == 0)
           for (uint32_t t = 1; t < k; ++t) v0 += halo[p[(size_t)(1 + t) * cnt + i0]];
       }
-      if (add) o0 = dv[g0];
+      if (add) o0 = dst[g0];
     }
     if (on1) {
       if (d1 >> 31) {
-        v1 = sv[g1];
+        v1 = src[g1];
       } else {
         T q[KU];
 #pragma unroll
@@ -144,27 +91,28 @@ __device__ __forceinline__ void reduce_two_multi(T *__restrict__ dst, const T *_
         if (K == 0)
           for (uint32_t t = 1; t < k; ++t) v1 += halo[p[(size_t)(1 + t) * cnt + i1]];
       }
-      if (add) o1 = dv[g1];
+      if (add) o1 = dst[g1];
     }
-    if (on0) dv[g0] = add ? o0 + v0 : v0;
-    if (on1) dv[g1] = add ? o1 + v1 : v1;
+    if (on0) dst[g0] = add ? o0 + v0 : v0;
+    if (on1) dst[g1] = add ? o1 + v1 : v1;
+    if (NV == 1) break;
   }
 }
 
 template <typename T, int NV>
 __global__ void __launch_bounds__(256)
-reduce_classes_multi(T *__restrict__ dst, const T *__restrict__ src, size_t stride, const MultiHalos<T> halos,
-                     const uint32_t *__restrict__ arr, const uint4 *__restrict__ tiles, int add) {
-  const uint4 td = tiles[blockIdx.x];  // as in reduce_classes
+reduce_classes(T *__restrict__ dst, const T *__restrict__ src, const HalosArg<T, NV> halos,
+               const uint32_t *__restrict__ arr, const uint4 *__restrict__ tiles, int add) {
+  const uint4 td = tiles[blockIdx.x];  // {class base in arr, k, entries of the class (padded), first entry of the tile}
   const uint32_t *p = arr + td.x;
   const uint32_t i0 = td.w + threadIdx.x;
   switch (td.y) {  // wave-uniform
-    case 1: reduce_two_multi<T, 1, NV>(dst, src, stride, halos, p, td.z, i0, 1, add); break;
-    case 2: reduce_two_multi<T, 2, NV>(dst, src, stride, halos, p, td.z, i0, 2, add); break;
-    case 3: reduce_two_multi<T, 3, NV>(dst, src, stride, halos, p, td.z, i0, 3, add); break;
-    case 4: reduce_two_multi<T, 4, NV>(dst, src, stride, halos, p, td.z, i0, 4, add); break;
-    case 8: reduce_two_multi<T, 8, NV>(dst, src, stride, halos, p, td.z, i0, 8, add); break;
-    default: reduce_two_multi<T, 0, NV>(dst, src, stride, halos, p, td.z, i0, td.y, add); break;
+    case 1: reduce_two<T, 1, NV>(dst, src, halos, p, td.z, i0, 1, add); break;
+    case 2: reduce_two<T, 2, NV>(dst, src, halos, p, td.z, i0, 2, add); break;
+    case 3: reduce_two<T, 3, NV>(dst, src, halos, p, td.z, i0, 3, add); break;
+    case 4: reduce_two<T, 4, NV>(dst, src, halos, p, td.z, i0, 4, add); break;
+    case 8: reduce_two<T, 8, NV>(dst, src, halos, p, td.z, i0, 8, add); break;
+    default: reduce_two<T, 0, NV>(dst, src, halos, p, td.z, i0, td.y, add); break;
   }
 }
 
@@ -277,7 +225,7 @@ template <typename T>
 hipError_t reduce_classes_launch(T *dst, const T *src, const T *halo, const uint32_t *arr, const uint32_t *tiles,
                                  uint32_t n_tiles, int add, hipStream_t st) {
   if (n_tiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(reduce_classes<T>, dim3(n_tiles), dim3(256), 0, st, dst, src, halo, arr,
+  hipLaunchKernelGGL((reduce_classes<T, 1>), dim3(n_tiles), dim3(256), 0, st, dst, src, halo, arr,
                      reinterpret_cast<const uint4 *>(tiles), add);
   return hipGetLastError();
 }
@@ -286,13 +234,14 @@ hipError_t reduce_classes_multi_launch(int nv, T *dst, const T *src, size_t stri
                                        const uint32_t *tiles, uint32_t n_tiles, int add, hipStream_t st) {
   if (n_tiles == 0) return hipSuccess;
   if (nv != 2 && nv != 3) return hipErrorInvalidValue;
-  MultiHalos<T> mh;
-  for (int v = 0; v < kMaxFusedWidth; ++v) mh.h[v] = v < nv ? halos[v] : nullptr;
+  GroupHalos<T> gh;
+  gh.stride = stride;
+  for (int v = 0; v < kMaxFusedWidth; ++v) gh.h[v] = v < nv ? halos[v] : nullptr;
   const uint4 *t4 = reinterpret_cast<const uint4 *>(tiles);
   if (nv == 2)
-    hipLaunchKernelGGL((reduce_classes_multi<T, 2>), dim3(n_tiles), dim3(256), 0, st, dst, src, stride, mh, arr, t4, add);
+    hipLaunchKernelGGL((reduce_classes<T, 2>), dim3(n_tiles), dim3(256), 0, st, dst, src, gh, arr, t4, add);
   else
-    hipLaunchKernelGGL((reduce_classes_multi<T, 3>), dim3(n_tiles), dim3(256), 0, st, dst, src, stride, mh, arr, t4, add);
+    hipLaunchKernelGGL((reduce_classes<T, 3>), dim3(n_tiles), dim3(256), 0, st, dst, src, gh, arr, t4, add);
   return hipGetLastError();
 }
 template hipError_t reduce_classes_multi_launch<double>(int, double *, const double *, size_t, double *const *,

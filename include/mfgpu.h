@@ -166,7 +166,7 @@ int mfgpu_vmult_add(mfgpu_handle *h, void *dst_dev, const void *src_dev, void *s
 /* ---- the operator applied to several vectors at once (the components of a vector Laplacian, several right-hand sides,
  * block Krylov methods).  On general geometry (3D, no MFGPU_UNIFORM_J0: apply_batches_g) an apply mostly streams the
  * folded metric, which does not depend on the vector; a FUSED group of 2 or 3 vectors reads it, the dof lists and the
- * index runs once (apply_batches_gm, reduce_classes_multi).  Every other handle -- 2D, the uniform-Jacobian families,
+ * index runs once (apply_batches_g and reduce_classes at width 2 or 3).  Every other handle -- 2D, the uniform-Jacobian families,
  * coloured scatter -- has no fused instantiation and applies the vectors one by one.                                  */
 #define MFGPU_MULTI_ADD   (1u << 0) /* vmult_add semantics for every vector */
 #define MFGPU_MULTI_LOOP  (1u << 1) /* one single-vector apply per vector (tests, A/B inside one build) */

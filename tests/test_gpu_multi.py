@@ -1,5 +1,5 @@
 """mfgpu_vmult_multi on the GPU: the operator applied to several vectors in one call, in fused groups of 3 and 2 vectors
-on the 3D general-geometry path (apply_batches_gm + reduce_classes_multi) and one by one everywhere else.
+on the 3D general-geometry path (apply_batches_g + reduce_classes at width 2 or 3) and one by one everywhere else.
 
 Every vector of every call is compared with oracle.mf_oracle.vmult / vmult_add on the same arrays AND with mfgpu_vmult of
 the same handle.  Tolerances are those of this path (tests/test_gpu_ball.py): relative l2 <= 1e-12 in double, 2e-5 in

@@ -3,7 +3,7 @@
 process, between two hipEvents on the launch stream (torch.cuda.Event, as bench.py takes its stream from torch), after the
 clock ramp bench.py uses (--ramp-steps untimed applies):
 
-  fused2   MFGPU_MULTI_FUSED on 2 vectors (apply_batches_gm<.., 2> + reduce_classes_multi<.., 2>)
+  fused2   MFGPU_MULTI_FUSED on 2 vectors (apply_batches_g<.., 2> + reduce_classes<.., 2>)
   fused3   MFGPU_MULTI_FUSED on 3 vectors
   loop     MFGPU_MULTI_LOOP on 3 vectors: three single-vector applies behind one call
   vmult    plain mfgpu_vmult
