@@ -702,8 +702,8 @@ int multi_fused_group(mfgpu_handle *h, T *dst, const T *src, int nv, size_t stri
   }
   if (!h->d_halo_multi.get()) {
     const size_t bytes = (size_t)(h->multi_width - 1) * h->halo_bytes;
-    if (const int rc = h->d_halo_multi.alloc(bytes, true)) return rc;  // zeroed: the untouched dofs' slot stays zero
-    HIP_TRY(hipStreamSynchronize(nullptr));  // (the memset, before a kernel on a non-blocking stream reads the slot)
+    // zeroed (the untouched dofs' slot stays zero), and complete before a kernel on a non-blocking stream reads the slot
+    if (const int rc = h->d_halo_multi.alloc(bytes, true)) return rc;
     h->device_bytes += bytes;
   }
   if (h->side_pending) {
@@ -1204,6 +1204,7 @@ int mfgpu_vec_alloc(void **dev, size_t n, int nt) {
   if (n == 0) return 0;
   HIP_TRY(hipMalloc(dev, n * esize(nt)));
   HIP_TRY(hipMemset(*dev, 0, n * esize(nt)));
+  HIP_TRY(hipStreamSynchronize(nullptr));  // (as DeviceArray::alloc: zero for a reader on a non-blocking stream too)
   return 0;
 }
 int mfgpu_vec_free(void *dev) {

@@ -54,7 +54,13 @@ class DeviceArray {
     if (n == 0) return 0;
     HIP_TRY(hipMalloc((void **)&p_, n * elem));
     bytes_ = n * elem;
-    if (zero) HIP_TRY(hipMemset(p_, 0, bytes_));
+    if (zero) {
+      // hipMemset on device memory may return before the fill has run; it is ordered on the null stream, which a
+      // non-blocking stream does not wait for: complete it here (set-up time) so that the first kernel on any stream
+      // reads zeros
+      HIP_TRY(hipMemset(p_, 0, bytes_));
+      HIP_TRY(hipStreamSynchronize(nullptr));
+    }
     return 0;
   }
   int upload(const void *host, size_t n) {  // n = 0 leaves the array empty

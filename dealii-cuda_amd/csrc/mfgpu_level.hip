@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "mfgpu_device.h"
+#include "mfgpu_kernels.h"
 
 using namespace mfgpu;
 
@@ -68,12 +69,15 @@ __global__ void copy_indexed_kernel(T *dst, const T *src, const uint32_t *idx, u
 
 template <typename T>
 int interface_typed(mfgpu_level *L, bool down, T *dst, const T *src, hipStream_t st) {
+  // The zero fills are fill_launch, not hipMemsetAsync: with the HIP runtime this was written against, a captured memset
+  // node zeroes its target on the first replay of a graph only and leaves stale bytes there from the second replay on
+  // (tests/test_gpu_streams.py, the replayed level cases); a kernel node replays like every other launch of the call
   const size_t bytes = (size_t)L->n_dofs * sizeof(T);
   T *x = L->tmp_x.as<T>(), *y = L->tmp_y.as<T>();
   const uint32_t *c = L->d_c.get(), *e = L->d_e.get();
   const unsigned gc = (L->n_c + 255) / 256, ge = (L->n_e + 255) / 256;
   if (L->n_e == 0) {  // no refinement edge on this level: both matrices are zero
-    HIP_TRY(hipMemsetAsync(dst, 0, bytes, st));
+    HIP_TRY(fill_launch<T>(dst, L->n_dofs, T(0), st));
     return 0;
   }
   if (down) {
@@ -81,11 +85,11 @@ int interface_typed(mfgpu_level *L, bool down, T *dst, const T *src, hipStream_t
     HIP_TRY(hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(set_indexed_kernel<T>, dim3(gc), dim3(256), 0, st, x, c, L->n_c, T(0));
     if (const int rc = mfgpu_vmult(L->Ab, y, x, st)) return rc;
-    HIP_TRY(hipMemsetAsync(dst, 0, bytes, st));
+    HIP_TRY(fill_launch<T>(dst, L->n_dofs, T(0), st));
     hipLaunchKernelGGL(copy_indexed_kernel<T>, dim3(ge), dim3(256), 0, st, dst, (const T *)y, e, L->n_e);
   } else {
     // x = 0 except the edge values of src (copy_edge_values, :343); dst = K x; dst[C] = 0 (:351)
-    HIP_TRY(hipMemsetAsync(x, 0, bytes, st));
+    HIP_TRY(fill_launch<T>(x, L->n_dofs, T(0), st));
     hipLaunchKernelGGL(copy_indexed_kernel<T>, dim3(ge), dim3(256), 0, st, x, src, e, L->n_e);
     if (const int rc = mfgpu_vmult(L->Ab, dst, x, st)) return rc;
     hipLaunchKernelGGL(set_indexed_kernel<T>, dim3(gc), dim3(256), 0, st, dst, c, L->n_c, T(0));

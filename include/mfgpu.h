@@ -279,7 +279,11 @@ int mfgpu_suggest_renumbering(const mfgpu_desc *desc, uint32_t *new_index /* [n_
  * 1 / diag(A) into inv_diag[n_dofs] (device, operator's number type); the local diagonal of every cell
  * (DiagonalLocalOperator, :355-399) is distributed like a cell result, including the transposed hanging-node
  * resolution, constrained rows are set to 1 before the inversion (:412-414).  With a mass term the local diagonal is
- * K_ii + M_ii, M_ii = sum_q c_q JxW_q prod_d S[i_d][q_d]^2.                                                */
+ * K_ii + M_ii, M_ii = sum_q c_q JxW_q prod_d S[i_d][q_d]^2.
+ * Asynchronous on `stream` and ordered like every call on the handle.  Memory: the FIRST call on a handle uploads two
+ * small 1D tables (2 n^2 numbers) with a blocking copy.  That is the only allocation and the only host synchronisation
+ * of this function: a caller that captures graphs calls it once before capturing.  The bytes count in
+ * mfgpu_memory_consumption from then on; mfgpu_destroy frees them.                                         */
 int mfgpu_compute_inverse_diagonal(mfgpu_handle *h, void *inv_diag, void *stream);
 /* ConstraintHandlerGpu::set_constrained_values (constraint_handler_gpu.cu:126-137): vec[c] = value for every
  * constrained dof c of the description.                                                                   */
@@ -288,7 +292,8 @@ int mfgpu_set_constrained_values(mfgpu_handle *h, void *vec, double value, void 
 /* ---- GpuVector BLAS-1 and reductions (gpu_vec.h:105-157, gpu_vec.cu:222-617) -------
  * v, w, x: device vectors of n elements of number_type.  The element-wise operations are asynchronous on
  * `stream`; the reductions block until the result is on the host (as the reference's do, gpu_vec.cu:556-560)
- * and accumulate in double in a fixed order (deterministic).                                               */
+ * and accumulate in double in a fixed order (deterministic).  The reductions synchronise `stream` and cannot be
+ * captured in a graph; the first one on a device allocates its scratch of partial sums.                     */
 int mfgpu_vec_sadd(void *v, double s, double a, const void *w, size_t n, int number_type, void *stream);  /* v = s v + a w   gpu_vec.cu:308-314 */
 int mfgpu_vec_equ(void *v, double a, const void *w, size_t n, int number_type, void *stream);             /* v = a w         :346-352 */
 int mfgpu_vec_scale(void *v, const void *w, size_t n, int number_type, void *stream);                     /* v[i] *= w[i]    :320-325 */
@@ -302,7 +307,9 @@ int mfgpu_vec_add_and_dot(void *v, double a, const void *x, const void *w, size_
 int mfgpu_vec_all_zero(const void *v, size_t n, int number_type, void *stream, int *result);              /* :512-540 */
 
 /* ---- GpuVector pieces that are on the path (gpu_vec.h:44,69,84-88,164-172) -------------- */
-int mfgpu_vec_alloc(void **dev, size_t n, int number_type);               /* gpu_vec.cu:166-182, zero-filled */
+/* gpu_vec.cu:166-182, zero-filled; the fill is complete when the call returns, so the vector reads as zero on every
+ * stream, non-blocking ones included (a set-up call: it synchronises the null stream)                            */
+int mfgpu_vec_alloc(void **dev, size_t n, int number_type);
 int mfgpu_vec_free(void *dev);
 int mfgpu_vec_fill(void *dev, size_t n, int number_type, double value, void *stream); /* vec_init, gpu_vec.cu:281-291 */
 int mfgpu_vec_from_host(void *dev, const void *host, size_t n, int number_type);
@@ -373,6 +380,10 @@ void mfgpu_transfer_destroy(mfgpu_transfer *t);
 typedef struct mfgpu_level mfgpu_level;
 int mfgpu_level_create(const mfgpu_desc *desc, const uint32_t *edge_dofs, uint32_t n_edge, mfgpu_level **out);
 mfgpu_handle *mfgpu_level_operator(mfgpu_level *level);
+/* Both interface products are asynchronous on `stream`: a copy or fill, index kernels and one mfgpu_vmult through two
+ * temporaries of the level, all enqueued on `stream` as kernels and device-to-device copies (no memset nodes); no
+ * allocation, no host synchronisation, so they can be captured in a graph.  One level is used on one stream at a time,
+ * like a handle.                                                                                                    */
 int mfgpu_level_vmult_interface_down(mfgpu_level *level, void *dst_dev, const void *src_dev, void *stream); /* :306-330 */
 int mfgpu_level_vmult_interface_up(mfgpu_level *level, void *dst_dev, const void *src_dev, void *stream);   /* :332-352 */
 /* mfgpu_update_coefficients for the level operator and the operator behind the interface matrices (both carry the
