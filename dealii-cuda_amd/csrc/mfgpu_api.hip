@@ -209,43 +209,16 @@ int check_symmetrize(int n, std::vector<double> &S, std::vector<double> &Dt) {
   return 0;
 }
 
-// pass-2 arrays from the plan: group 0 = the dofs listed in `priority` (may be empty), group 1 = the rest.  Pass 2 also
-// writes the dofs no cell touches (hanging dofs after substitution: dst = 0, or the identity row of a constrained one):
-// listed with ONE partial sum, a halo slot behind the batches' that is zero and stays zero.
+// pass-2 arrays from the plan (pass2_groups): group 0 = the dofs listed in `priority` (may be empty), the others by the
+// cell-loop segment of their last toucher
 int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority) {
   const Plan &P = h->plan;
-  std::vector<uint8_t> prio(P.n_dofs, 0);
-  for (uint32_t i = 0; i < n_priority; ++i) {
-    if (priority[i] >= P.n_dofs) {
-      set_error("priority dof out of range");
-      return MFGPU_EINVAL;
-    }
-    prio[priority[i]] = 1;
-  }
   const size_t ng = 1 + h->seg_end.size();
   // the shared form serves the one group that matters: everything, on a one-segment plan without priority dofs
   const bool shared = P.sh_p2_use && !h->no_shared_records && n_priority == 0 && ng == 2;
-  std::vector<std::vector<uint32_t>> sd(ng), so(ng, std::vector<uint32_t>(1, 0u)), si(ng);
-  auto add = [&](uint32_t dof, const uint32_t *slots, uint32_t k, size_t seg) {
-    const size_t g = prio[dof & 0x7fffffffu] ? 0 : 1 + seg;
-    sd[g].push_back(dof);
-    si[g].insert(si[g].end(), slots, slots + k);
-    so[g].push_back((uint32_t)si[g].size());
-  };
-  for (size_t i = 0; i < P.sdofs.size(); ++i) {
-    // the slots of a dof are listed in ascending batch order: the last one belongs to its last toucher
-    size_t seg = 0;
-    if (shared && P.s_off[i + 1] > P.s_off[i]) continue;  // (in its owner batch's record)
-    if (P.s_off[i + 1] > P.s_off[i]) {
-      const uint32_t slot = P.s_idx[P.s_off[i + 1] - 1];
-      const uint32_t batch = (uint32_t)(std::upper_bound(P.halo_off.begin(), P.halo_off.end(), slot) - P.halo_off.begin()) - 1;
-      seg = (size_t)(std::upper_bound(h->seg_end.begin(), h->seg_end.end(), batch) - h->seg_end.begin());
-      if (seg >= h->seg_end.size()) seg = h->seg_end.size() - 1;
-    }
-    add(P.sdofs[i], P.s_idx.data() + P.s_off[i], P.s_off[i + 1] - P.s_off[i], seg);
-  }
-  const uint32_t zero_slot = P.halo_off.empty() ? 0u : P.halo_off.back();
-  for (uint32_t orph : P.orphans) add(orph, &zero_slot, 1, 0);  // depend on no batch
+  std::vector<Pass2Group> groups;
+  int rc;
+  if ((rc = pass2_groups(P, h->seg_end, priority, n_priority, shared, groups))) return rc;
   // built aside and moved into the handle when every group is on the device: a failure leaves the handle's arrays
   // as they were.  (These arrays are not counted in device_bytes.)
   std::vector<DeviceArray<uint32_t>> d_arr(ng), d_tiles(ng);
@@ -253,13 +226,12 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
   const bool reverse = (size_t)P.halo_off.back() * esize(h->number_type) <= ((size_t)256 << 20);  // (see below)
   DeviceArray<uint32_t> d_rec, d_tab;
   if (shared) {
-    int rc;
     if ((rc = d_rec.upload(P.sh_p2rec.data(), P.sh_p2rec.size()))) return rc;
     if ((rc = d_tab.upload(P.sh_p2tab.data(), P.sh_p2tab.size()))) return rc;
   }
   for (size_t g = 0; g < ng; ++g) {
     std::vector<uint32_t> arr, tiles;
-    build_pass2_classes(sd[g], so[g], si[g], arr, tiles);
+    build_pass2_classes(groups[g].dofs, groups[g].offsets, groups[g].slots, arr, tiles);
     n_tiles[g] = (uint32_t)(tiles.size() / 4);
     // Tile order = the order the workgroups of pass 2 are dispatched in.  The builder's order is ascending in the
     // position of a dof's first toucher; while the halo buffer fits the 256 MB Infinity Cache the REVERSE is faster --
@@ -271,7 +243,6 @@ int upload_pass2(mfgpu_handle *h, const uint32_t *priority, uint32_t n_priority)
       for (size_t a = 0, b = nt ? nt - 1 : 0; a < b; ++a, --b)
         for (int w = 0; w < 4; ++w) std::swap(tiles[4 * a + w], tiles[4 * b + w]);
     }
-    int rc;
     if ((rc = d_arr[g].upload(arr.data(), arr.size()))) return rc;
     if ((rc = d_tiles[g].upload(tiles.data(), tiles.size()))) return rc;
   }
@@ -326,39 +297,11 @@ int create_arrays(mfgpu_handle *h, const mfgpu_desc &d) {
   if ((rc = up(h->d_lmap, P.lmap.data(), P.lmap.size()))) return rc;
   const bool general = h->batches == BatchKernel::g || h->batches == BatchKernel::g2;
   if (h->batches == BatchKernel::x && !h->hn) {
-    // Lane -> pencil maps of the y- and z-stage (see apply_batches_x).  LDS rules (MI355X_MICROARCH.md): a
-    // ds_read_b64 is served in 32-lane groups, a double occupies slot (index mod 32); ds_write_b64 / ds_read2_b64
-    // in 16-lane groups, slot (index mod 16).  All n elements of a pencil shift its base by the same stride, so
-    // only the bases matter: the pencil whose base has residue r mod 32 gets lane 32 k + r (k-th pencil with that
-    // residue) -- distinct slots in every 32-lane group, and in each of its 16-lane halves.  Residue classes with
-    // more than 8 pencils (4 pencils at p=4 in the y-stage, 2 in the z-stage) overflow into the idle lanes, which
-    // all sit in the last group.
-    const int n = P.n, n2 = n * n, PP = n2, CH = 256 / PP, ndl = n2 * n;
-    std::vector<uint16_t> perm(512, 0xffff);
-    for (int layout = 0; layout < 2; ++layout) {
-      uint16_t *lanes = perm.data() + 256 * layout;
-      std::vector<int> fill(32, 0), overflow;
-      for (int q = 0; q < CH * PP; ++q) {
-        const int cell = q / PP, pen = q % PP, a = pen % n, b = pen / n;
-        const int base = cell * ndl + (layout == 0 ? a + n2 * b : a + n * b);
-        const int r = base & 31;
-        if (fill[r] < 8) lanes[32 * fill[r]++ + r] = (uint16_t)q;
-        else overflow.push_back(q);
-      }
-      for (int l = 255; l >= 0 && !overflow.empty(); --l)
-        if (lanes[l] == 0xffff) {
-          lanes[l] = (uint16_t)overflow.back();
-          overflow.pop_back();
-        }
-    }
+    const std::vector<uint16_t> perm = x_lane_permutation(P.n);  // (bank-conflict-free lanes of the y- and z-stage)
     if ((rc = up(h->d_perm, perm.data(), perm.size()))) return rc;
   }
   if (h->batches == BatchKernel::x || general) {
-    // x-pencil index runs (n contiguous entries of lmap) padded to whole 32-bit words
-    const size_t n = (size_t)P.n, np = (n + 1) & ~(size_t)1, runs = P.lmap.size() / n;
-    std::vector<uint16_t> lx(runs * np, 0);
-    for (size_t r = 0; r < runs; ++r)
-      for (size_t i = 0; i < n; ++i) lx[r * np + i] = P.lmap[r * n + i];
+    const std::vector<uint16_t> lx = x_pencil_runs(P.lmap, P.n);
     if ((rc = up(h->d_lmapx, lx.data(), lx.size()))) return rc;
   }
   if (h->batches == BatchKernel::g2) {  // apply_batches_g2: the full 1D tables [S | Dt]

@@ -220,6 +220,22 @@ void share_plane_records(Plan &plan);
 constexpr int kP2Header = 16, kP2MaxK = 12, kP2SlotBits = 12;
 void share_pass2_records(Plan &plan);
 
+// Host-only derivations of the set-up (create_arrays and upload_pass2 upload what they return):
+// the [2][256] lane -> pencil permutation of apply_batches_x (0xffff: idle lane), a function of n alone;
+std::vector<uint16_t> x_lane_permutation(int n);
+// the x-pencil index runs (n contiguous entries of lmap) padded to whole 32-bit words;
+std::vector<uint16_t> x_pencil_runs(const std::vector<uint16_t> &lmap, int n);
+// the pass-2 groups, each as the (dofs, offsets, slots) CSR build_pass2_classes consumes: group 0 = the dofs listed in
+// `priority` (may be empty), group 1 + s = the others whose last toucher runs in cell-loop segment s (seg_end: one past
+// each segment's last batch).  Pass 2 also writes the dofs no cell touches (hanging dofs after substitution: dst = 0, or
+// the identity row of a constrained one): listed with ONE partial sum, a halo slot behind the batches' that is zero and
+// stays zero.  shared: the dofs with a partial sum are left to the records of Plan::sh_p2rec.
+struct Pass2Group {
+  std::vector<uint32_t> dofs, offsets = std::vector<uint32_t>(1, 0u), slots;
+};
+int pass2_groups(const Plan &plan, const std::vector<uint32_t> &seg_end, const uint32_t *priority, uint32_t n_priority,
+                 bool shared, std::vector<Pass2Group> &groups);
+
 // Derive the kernel's 1D tables from the reference-layout tables T[dof*n+q]:
 //   S[i*n+q]  = shape_values (interpolation nodal -> quadrature points)
 //   Dt[q*n+t] = l_t'(x_q): collocation derivative on the quadrature points, from
