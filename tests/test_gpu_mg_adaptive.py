@@ -8,8 +8,9 @@ Multigrid + PreconditionMG (:199-380).
 The V-cycle schedule (where the edge matrices enter) is deal.II library code that is not in the reference tree; it is
 restated here from its published algorithm (Janssen & Kanschat, local smoothing with edge matrices) and checked by what
 it must deliver: CG preconditioned with it converges to the sparse direct solution in a number of iterations that stays
-bounded as the mesh is refined.  Parity of every PIECE with the reference's code is tested elsewhere
-(test_gpu_level.py, test_gpu_transfer.py, test_gpu.py)."""
+bounded as the mesh is refined.  Parity of every PIECE with the reference's code on such hierarchies, and of one V-cycle
+value for value, is tested in test_gpu_mg_parity.py (on cubes and synthetic edge sets: test_gpu_level.py,
+test_gpu_transfer.py, test_gpu.py)."""
 import numpy as np
 import pytest
 
