@@ -15,7 +15,9 @@
 // cg_init_kernel writes the `begin` and `direction` fields and reads none; cg_update_kernel reads the `direction`
 // fields and writes the `update` fields; cg_direction_kernel reads the `begin` and `update` fields and writes the
 // `direction` fields; cg_dot_kernel only reads.  What a kernel reads was therefore written by an earlier launch and is
-// uniform over its grid, which also makes the early returns below uniform per block.
+// uniform over its grid, which also makes the early returns below uniform per block.  The absolute tolerance of a solve
+// begun with a relative one (mfgpu_cg_begin_relative) is a `direction` field that the first launch of
+// cg_direction_kernel writes and only the later launches read.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,15 +33,18 @@ constexpr unsigned kBlocks = 2048;  // 256 CUs x 8 resident blocks of 256 thread
 
 struct CgState {
   // begin: written by cg_init_kernel
-  double tolerance;
-  uint32_t max_iterations, pad0;
+  double tolerance;  // begin_relative: the relative tolerance, see tolerance_abs
+  uint32_t max_iterations, relative;
   // direction: written by cg_direction_kernel (status and iterations also reset by cg_init_kernel)
   double rz, rr, beta, initial_residual;
   uint32_t iterations, status;
   // update: written by cg_update_kernel
   double pq, alpha, rz_old;
   uint32_t it_old, frozen, breakdown, pad1;
-  double pad2[4];
+  // direction, mfgpu_cg_begin_relative only: tolerance * sqrt(r.r) of the start, written by the FIRST launch of
+  // cg_direction_kernel of a solve (which does not read it) and read by the later ones (which do not write it)
+  double tolerance_abs;
+  double pad2[3];
 };
 static_assert(sizeof(CgState) == 128, "the state block is 128 bytes (mfgpu_cg_memory_consumption, include/mfgpu.h)");
 
@@ -102,7 +107,7 @@ template <typename T, bool VEC, int PREC>
 __global__ void __launch_bounds__(256)
 cg_init_kernel(CgState *__restrict__ s, T *__restrict__ x, T *__restrict__ r, const T *__restrict__ b,
                const T *__restrict__ dinv, double *__restrict__ prr, double *__restrict__ prz, double tolerance,
-               uint32_t max_iterations, size_t n) {
+               uint32_t relative, uint32_t max_iterations, size_t n) {
   __shared__ double red[4];
   constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
@@ -140,6 +145,7 @@ cg_init_kernel(CgState *__restrict__ s, T *__restrict__ x, T *__restrict__ r, co
     if (PREC == P_JACOBI) prz[blockIdx.x] = arz;
     if (blockIdx.x == 0) {
       s->tolerance = tolerance;
+      s->relative = relative;
       s->max_iterations = max_iterations;
       s->iterations = 0;
       s->status = 0;
@@ -264,7 +270,10 @@ cg_direction_kernel(CgState *__restrict__ s, T *__restrict__ p, const T *__restr
   const double rz = PREC == P_NONE ? rr : resum(prz, np, red);
   const uint32_t it = first ? 0u : s->it_old + 1u;
   const double res = sqrt(rr);
-  const uint32_t status = res <= s->tolerance ? 1u : it >= s->max_iterations ? 2u : 0u;
+  // relative: the first launch forms the absolute tolerance from the start residual, the later ones read it back
+  const bool relative = s->relative != 0;
+  const double tolerance = !relative ? s->tolerance : first ? s->tolerance * res : s->tolerance_abs;
+  const uint32_t status = res <= tolerance ? 1u : it >= s->max_iterations ? 2u : 0u;
   const double beta_d = first ? 0.0 : rz / s->rz_old;
   const T beta = (T)beta_d;
   if (writer) {
@@ -274,6 +283,7 @@ cg_direction_kernel(CgState *__restrict__ s, T *__restrict__ p, const T *__restr
     s->iterations = it;
     s->status = status;
     if (first) s->initial_residual = res;
+    if (first && relative) s->tolerance_abs = tolerance;
   }
   if (status != 0) return;
   constexpr int W = lanes16<T>();
@@ -407,10 +417,10 @@ int direction_launch(mfgpu_cg *s, int first, hipStream_t st) {
 }
 
 template <typename T>
-int begin_typed(mfgpu_cg *s, double tolerance, uint32_t max_iterations, hipStream_t st) {
+int begin_typed(mfgpu_cg *s, double tolerance, uint32_t relative, uint32_t max_iterations, hipStream_t st) {
   double *prr = s->partials.get() + kBlocks, *prz = prr + kBlocks;
   CG_LAUNCH(cg_init_kernel, s->state.get(), (T *)s->x, (T *)s->r.get(), (const T *)s->b, (const T *)s->dinv, prr, prz,
-            tolerance, max_iterations, s->n);
+            tolerance, relative, max_iterations, s->n);
   if (const int rc = mfgpu::hip_check(hipGetLastError(), "mfgpu_cg_begin")) return rc;
   if (const int rc = precondition<T>(s, st)) return rc;
   return direction_launch<T>(s, 1, st);
@@ -505,7 +515,9 @@ int mfgpu_cg_set_callback(mfgpu_cg *s, int (*fn)(void *ctx, void *z_dev, const v
   return MFGPU_OK;
 }
 
-int mfgpu_cg_begin(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations, void *stream) {
+namespace {
+int begin_common(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, uint32_t relative, uint32_t max_iterations,
+                 void *stream) {
   if (!s || !x_dev || !b_dev) return einval("mfgpu_cg_begin: null argument");
   if (s->prec == MFGPU_CG_CALLBACK && !s->fn) return einval("mfgpu_cg_begin: no callback set (mfgpu_cg_set_callback)");
   const size_t vbytes = s->n * mfgpu::esize(s->number_type);
@@ -518,8 +530,38 @@ int mfgpu_cg_begin(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance
   const size_t work = s->vec ? s->n / lanes + s->n % lanes : s->n, blocks = (work + 255) / 256;
   s->grid = (unsigned)(blocks == 0 ? 1 : blocks > kBlocks ? kBlocks : blocks);
   s->begun = true;
-  return s->number_type == MFGPU_F64 ? begin_typed<double>(s, tolerance, max_iterations, (hipStream_t)stream)
-                                     : begin_typed<float>(s, tolerance, max_iterations, (hipStream_t)stream);
+  return s->number_type == MFGPU_F64 ? begin_typed<double>(s, tolerance, relative, max_iterations, (hipStream_t)stream)
+                                     : begin_typed<float>(s, tolerance, relative, max_iterations, (hipStream_t)stream);
+}
+}  // namespace
+
+int mfgpu_cg_begin(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations, void *stream) {
+  return begin_common(s, x_dev, b_dev, tolerance, 0, max_iterations, stream);
+}
+
+int mfgpu_cg_begin_relative(mfgpu_cg *s, void *x_dev, const void *b_dev, double relative_tolerance,
+                            uint32_t max_iterations, void *stream) {
+  if (!(relative_tolerance >= 0.0) || !std::isfinite(relative_tolerance))
+    return einval("mfgpu_cg_begin_relative: the relative tolerance must be a finite number >= 0");
+  return begin_common(s, x_dev, b_dev, relative_tolerance, 1, max_iterations, stream);
+}
+
+// the library's own callback: z = M^-1 r is one mfgpu_vcycle_apply
+static int vcycle_callback(void *ctx, void *z_dev, const void *r_dev, void *stream) {
+  return mfgpu_vcycle_apply(static_cast<mfgpu_vcycle *>(ctx), z_dev, r_dev, stream);
+}
+
+int mfgpu_cg_set_vcycle(mfgpu_cg *s, mfgpu_vcycle *v) {
+  if (!s || !v) return einval("mfgpu_cg_set_vcycle: null argument");
+  if (s->prec != MFGPU_CG_CALLBACK) return einval("mfgpu_cg_set_vcycle: the solver was not created with MFGPU_CG_CALLBACK");
+  int active_type = 0;
+  uint32_t n_active = 0;
+  mfgpu::vcycle_active(v, &active_type, &n_active);
+  if (active_type != s->number_type || n_active != s->n)
+    return einval("mfgpu_cg_set_vcycle: the V-cycle's active vectors are not the solver's (type or length)");
+  s->fn = vcycle_callback;
+  s->ctx = v;
+  return MFGPU_OK;
 }
 
 int mfgpu_cg_iterate(mfgpu_cg *s, uint32_t n_iterations, void *stream) {

@@ -259,6 +259,10 @@ int handle_cells_two_ranges(mfgpu_handle *h, uint32_t b0, uint32_t b1, uint32_t 
                             const void *src, void *stream, int add);
 int handle_pass2_group(mfgpu_handle *h, int group, void *dst, const void *src, void *stream, int add);
 
+// what mfgpu_vcycle (mfgpu_vcycle.hip) checks of the pieces it borrows, and mfgpu_cg_set_vcycle of the V-cycle
+void transfer_sizes(const mfgpu_transfer *t, uint32_t *n_coarse_dofs, uint32_t *n_fine_dofs, int *number_type);
+void vcycle_active(const mfgpu_vcycle *v, int *active_type, uint32_t *n_active);
+
 }  // namespace mfgpu
 
 struct mfgpu_plan {

@@ -4,6 +4,7 @@
 //                                level_number in the reference's bmop_mg.cu:58-59 and poisson_mg.cu:51)
 //   mfgpu_vec_chebyshev_start    the vector updates of one PreconditionChebyshev sweep (host/mfgpu_shim_mg.h) in ONE
 //   mfgpu_vec_chebyshev_update   launch each instead of the BLAS-1 sequence r.add, t.equ, t.scale, upd.sadd, x.add
+//   mfgpu_vec_residual           t = b - t or t = b - (t + e) in one launch instead of add + sadd (the V-cycle's residual)
 // All kernels stream: grid-stride over 16-byte chunks per lane (2 doubles or 4 floats; 4 elements for the
 // conversion), a scalar loop for the tail (and for vectors that are not 16-byte aligned), no atomics, no LDS, every
 // element computed by one lane in a fixed order (deterministic).
@@ -174,6 +175,31 @@ cheb_update_kernel(T *__restrict__ x, T *__restrict__ upd, T *__restrict__ r, co
   }
 }
 
+// t = b - t (HAS_E: t = b - (t + e)): the V-cycle's residual after t = A x, the edge rows e = down x included -- the
+// operations and their order of t.add(1, e), t.sadd(-1, 1, b)
+template <typename T, bool VEC, bool HAS_E>
+__global__ void __launch_bounds__(256)
+residual_kernel(T *__restrict__ t, const T *__restrict__ b, const T *__restrict__ e, size_t n) {
+  constexpr int W = lanes16<T>();
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (VEC) {
+    const size_t nc = n / W;
+    for (size_t c = tid; c < nc; c += stride) {
+      const size_t o = c * W;
+      T tv[W], bv[W], ev[W];
+      ld16<T>(t + o, tv);
+      ld16<T>(b + o, bv);
+      if (HAS_E) ld16<T>(e + o, ev);
+#pragma unroll
+      for (int k = 0; k < W; ++k) tv[k] = HAS_E ? bv[k] - (tv[k] + ev[k]) : bv[k] - tv[k];
+      st16<T>(t + o, tv);
+    }
+    done = nc * W;
+  }
+  for (size_t i = done + tid; i < n; i += stride) t[i] = HAS_E ? b[i] - (t[i] + e[i]) : b[i] - t[i];
+}
+
 unsigned grid_for(size_t work) {
   const size_t blocks = (work + 255) / 256;
   return (unsigned)(blocks == 0 ? 1 : blocks > kBlocks ? kBlocks : blocks);
@@ -225,6 +251,20 @@ void cheb_update_launch(T *x, T *upd, T *r, const T *t, const T *dinv, T f1, T f
                        n);
 }
 
+template <typename T>
+void residual_launch(T *t, const T *b, const T *e, size_t n, hipStream_t st) {
+  const bool vec = aligned16(t) && aligned16(b) && aligned16(e);
+  const unsigned g = grid_for(vec ? n / lanes16<T>() + n % lanes16<T>() : n);
+#define RESIDUAL(VEC, HE) hipLaunchKernelGGL((residual_kernel<T, VEC, HE>), dim3(g), dim3(256), 0, st, t, b, e, n)
+  switch ((vec ? 2 : 0) + (e ? 1 : 0)) {
+    case 0: RESIDUAL(false, false); break;
+    case 1: RESIDUAL(false, true); break;
+    case 2: RESIDUAL(true, false); break;
+    default: RESIDUAL(true, true); break;
+  }
+#undef RESIDUAL
+}
+
 // the three written vectors must be distinct and must not be one of the read ones
 bool outputs_alias(const void *x, const void *upd, const void *r, const void *a, const void *b, const void *c) {
   const void *out[3] = {x, upd, r}, *in[3] = {a, b, c};
@@ -257,6 +297,23 @@ int mfgpu_vec_convert(void *dst, int dst_type, const void *src, int src_type, si
   else
     convert_launch<double, float>((double *)dst, (const float *)src, n, st);
   return mfgpu::hip_check(hipGetLastError(), "mfgpu_vec_convert");
+}
+
+int mfgpu_vec_residual(void *t, const void *b, const void *e, size_t n, int number_type, void *stream) {
+  if (!mfgpu::valid_number_type(number_type)) return einval("mfgpu_vec_residual: number type must be MFGPU_F64 or MFGPU_F32");
+  if (n == 0) return MFGPU_OK;
+  if (!t || !b) return einval("mfgpu_vec_residual: null vector");
+  const uintptr_t bytes = n * mfgpu::esize(number_type), t0 = (uintptr_t)t;
+  for (const void *in : {b, e}) {  // ranges, as mfgpu_cg_begin: the kernel reads b and e through __restrict__ pointers
+    const uintptr_t i0 = (uintptr_t)in;
+    if (in && t0 < i0 + bytes && i0 < t0 + bytes) return einval("mfgpu_vec_residual: t must not overlap b or e");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  if (number_type == MFGPU_F64)
+    residual_launch<double>((double *)t, (const double *)b, (const double *)e, n, st);
+  else
+    residual_launch<float>((float *)t, (const float *)b, (const float *)e, n, st);
+  return mfgpu::hip_check(hipGetLastError(), "mfgpu_vec_residual");
 }
 
 int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const void *t, const void *dinv, double f,

@@ -16,6 +16,9 @@
 //    prolongate (no src copy + set_mg_constrained_dofs, :607-608), skipped in restrict (no increment vector, :642-657).
 //  * restriction accumulates into the coarse vector with hardware floating-point atomics (several coarse cells share
 //    a coarse dof), as the reference does; prolongation is deterministic.
+//  * prolongate_add (dst_fine += P src_coarse, the V-cycle's coarse-grid correction) is the prolongation kernel with the
+//    ADD flag: the owner's plain store becomes a plain read-modify-write.  One owner per fine dof, so still no atomics,
+//    and a transfer that does not cover the fine level simply leaves the other entries alone (no zero pass).
 // One 256-thread workgroup per coarse cell at a time (grid-stride); the three 1D contractions go through LDS.
 // Bound: HBM (one read of the fine vector + index lists); small next to the smoother's operator applies.
 #include <hip/hip_runtime.h>
@@ -45,7 +48,7 @@ namespace {
 constexpr int ipow_c(int a, int e) { return e == 0 ? 1 : a * ipow_c(a, e - 1); }
 
 // sizes of the intermediate arrays: after contracting directions 0..k-1 the array is nf^k x nc^(dim-k)
-template <int dim, int p, typename T, bool RESTRICT>
+template <int dim, int p, typename T, bool RESTRICT, bool ADD>
 __global__ void __launch_bounds__(256)
 transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ coarse,
                 const uint32_t *__restrict__ fine, const T *__restrict__ p1, uint32_t n_cells) {
@@ -93,7 +96,7 @@ transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *
     if (!RESTRICT) {
       for (int t = tid; t < NF; t += 256) {
         const uint32_t g = fd[t];
-        if (!(g >> 31)) dst[g] = in[t];
+        if (!(g >> 31)) dst[g] = ADD ? dst[g] + in[t] : in[t];
       }
     } else {
       for (int t = tid; t < NC; t += 256) {
@@ -104,14 +107,14 @@ transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *
   }
 }
 
-template <typename T, bool RESTRICT>
+template <typename T, bool RESTRICT, bool ADD = false>
 hipError_t launch(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t st) {
   const uint32_t n = t->n_coarse_cells;
   if (n == 0) return hipSuccess;
   const unsigned grid = n < 8192u ? n : 8192u;
 #define TR_CASE(D, PP)                                                                                           \
   case D * 10 + PP:                                                                                              \
-    hipLaunchKernelGGL((transfer_kernel<D, PP, T, RESTRICT>), dim3(grid), dim3(256), 0, st, dst, src,           \
+    hipLaunchKernelGGL((transfer_kernel<D, PP, T, RESTRICT, ADD>), dim3(grid), dim3(256), 0, st, dst, src,           \
                        t->d_coarse.get(), t->d_fine.get(), t->d_p1.as<const T>(), n);                            \
     break;
   switch (t->dim * 10 + t->degree) {
@@ -146,6 +149,12 @@ void default_prolongation_1d(int p, std::vector<double> &P1) {
   for (double &v : P1)
     if (std::fabs(v) < 1e-15) v = 0.0;
     else if (std::fabs(v - 1.0) < 1e-15) v = 1.0;
+}
+
+void transfer_sizes(const mfgpu_transfer *t, uint32_t *n_coarse_dofs, uint32_t *n_fine_dofs, int *number_type) {
+  *n_coarse_dofs = t->n_coarse_dofs;
+  *n_fine_dofs = t->n_fine_dofs;
+  *number_type = t->number_type;
 }
 
 }  // namespace mfgpu
@@ -245,6 +254,20 @@ int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst_fine, (size_t)t->n_fine_dofs);
     HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
   }
+  return 0;
+}
+
+int mfgpu_transfer_prolongate_add(mfgpu_transfer *t, void *dst_fine, const void *src_coarse, void *stream) {
+  using namespace mfgpu;
+  if (!t || !dst_fine || !src_coarse) {
+    set_error("mfgpu_transfer_prolongate_add: null argument");
+    return MFGPU_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (t->number_type == MFGPU_F64)
+    HIP_TRY((launch<double, false, true>(t, (double *)dst_fine, (const double *)src_coarse, st)));
+  else
+    HIP_TRY((launch<float, false, true>(t, (float *)dst_fine, (const float *)src_coarse, st)));
   return 0;
 }
 

@@ -199,6 +199,7 @@ public:
   }
   std::size_t memory_consumption() const { return mfgpu_memory_consumption(handle); }
   mfgpu_handle *get_handle() const { return handle; }
+  mfgpu_level *get_level() const { return lev; }  // the level with its edge matrices (nullptr after reinit_active)
   unsigned int level = 0;
 
 private:
@@ -299,6 +300,10 @@ public:
     for (mfgpu_transfer *t : transfers) s += mfgpu_transfer_memory_consumption(t);
     return s;
   }
+  // the pieces as mfgpu_vcycle_level_desc takes them (MultigridPreconditionerDevice); no pairs on globally refined meshes
+  mfgpu_transfer *get_transfer(unsigned int to_level) const { return transfers.at(to_level - 1); }
+  const mfgpu_index_pairs *get_to_mg(unsigned int level) const { return to_mg.empty() ? nullptr : to_mg.at(level); }
+  const mfgpu_index_pairs *get_from_mg(unsigned int level) const { return from_mg.empty() ? nullptr : from_mg.at(level); }
 
 private:
   // dst = src between the active vector and the finest level of a globally refined hierarchy
@@ -500,6 +505,53 @@ private:
   const MGTransferMatrixFreeGpu<dim, Number> *transfer;
   const MGLevelObject<Smoother> *smoother;
   mutable MGLevelObject<VectorType> defect, solution, tmp, edge;
+};
+
+// The same preconditioner as ONE library object (mfgpu_vcycle, include/mfgpu.h): same constructor arguments, same vmult.
+// The level matrices, the transfer and the copy pairs are borrowed from the arguments; the smoothers give their degree,
+// smoothing range and lambda_max, so both classes run the same polynomial (always with fused updates); the coarse solver
+// argument is not used: level 0 is solved on the device (the dense inverse up to 2048 dofs, an enqueued CG above).  vmult
+// only enqueues work.  ActiveNumber: the type of vmult's vectors (a float V-cycle under a double CG: <..., float, ...,
+// double>).  After new coefficients on the levels a new object is needed.
+template <int dim, typename LevelMatrixType, typename Number, typename CoarseSolver, typename ActiveNumber = Number>
+class MultigridPreconditionerDevice {
+public:
+  typedef PreconditionChebyshev<LevelMatrixType, GpuVector<Number>> Smoother;
+  MultigridPreconditionerDevice(const MGDoFHandler<dim> &dh, const MGLevelObject<LevelMatrixType> &matrices,
+                                const CoarseSolver &, const MGTransferMatrixFreeGpu<dim, Number> &transfer,
+                                const MGLevelObject<Smoother> &smoother) {
+    const unsigned int top = matrices.max_level();
+    std::vector<mfgpu_vcycle_level_desc> levels(top + 1);
+    std::vector<double> lambda(top + 1);
+    for (unsigned int l = 0; l <= top; ++l) {
+      levels[l].op = matrices[l].get_handle();
+      levels[l].edges = matrices[l].has_edges() ? matrices[l].get_level() : nullptr;
+      levels[l].from_coarser = l ? transfer.get_transfer(l) : nullptr;
+      levels[l].to_mg = transfer.get_to_mg(l);
+      levels[l].from_mg = transfer.get_from_mg(l);
+      lambda[l] = smoother[l].lambda_max;
+    }
+    mfgpu_vcycle_desc d{};
+    d.n_levels = top + 1;
+    d.levels = levels.data();
+    d.active_type = number_type<ActiveNumber>();
+    d.n_active = dh.n_dofs();
+    d.smoother_degree = smoother[top].get_additional_data().degree;
+    d.smoothing_range = smoother[top].get_additional_data().smoothing_range;
+    d.lambda_max = lambda.data();
+    d.coarse = MFGPU_VCYCLE_COARSE_AUTO;
+    check(mfgpu_vcycle_create(&d, &vcycle), "MultigridPreconditionerDevice");
+  }
+  ~MultigridPreconditionerDevice() { mfgpu_vcycle_destroy(vcycle); }
+  MultigridPreconditionerDevice(const MultigridPreconditionerDevice &) = delete;
+  void vmult(GpuVector<ActiveNumber> &dst, const GpuVector<ActiveNumber> &src) const {
+    check(mfgpu_vcycle_apply(vcycle, dst.getData(), src.getDataRO(), nullptr), "MultigridPreconditionerDevice::vmult");
+  }
+  std::size_t memory_consumption() const { return mfgpu_vcycle_memory_consumption(vcycle); }
+  mfgpu_vcycle *get_vcycle() const { return vcycle; }
+
+private:
+  mfgpu_vcycle *vcycle = nullptr;
 };
 
 }  // namespace mfgpu_shim

@@ -154,8 +154,8 @@ private:
 // The same solver with its loop on the device (mfgpu_cg, include/mfgpu.h): the scalars stay in a device state block, the
 // host reads them once every check_every iterations.  PreconditionChebyshev maps to MFGPU_CG_CHEBYSHEV (its sweep, from
 // its lambda_max, degree and smoothing range; A must be the matrix it was initialised with), DiagonalMatrix to
-// MFGPU_CG_JACOBI, anything else with a vmult(z, r) is called back once per iteration (a V-cycle).  A must give its
-// mfgpu_handle (get_handle()).
+// MFGPU_CG_JACOBI, MultigridPreconditionerDevice to mfgpu_cg_set_vcycle, anything else with a vmult(z, r) is called back
+// once per iteration (a V-cycle composed in the shim).  A must give its mfgpu_handle (get_handle()).
 template <typename VectorType>
 class SolverCGDevice {
 public:
@@ -174,6 +174,19 @@ public:
   void solve(const MatrixType &A, VectorType &x, const VectorType &b, const DiagonalMatrix<Number> &prec) {
     mfgpu_cg *cg = nullptr;
     check(mfgpu_cg_create(A.get_handle(), MFGPU_CG_JACOBI, prec.get_vector().getDataRO(), 0, 0, 0, &cg), "SolverCGDevice");
+    run(cg, x, b);
+  }
+  // the library's V-cycle object: its own callback inside the library, no trip through the shim per iteration
+  template <typename MatrixType, int dim, typename LevelMatrixType, typename LevelNumber, typename CoarseSolver>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b,
+             const MultigridPreconditionerDevice<dim, LevelMatrixType, LevelNumber, CoarseSolver, Number> &prec) {
+    mfgpu_cg *cg = nullptr;
+    check(mfgpu_cg_create(A.get_handle(), MFGPU_CG_CALLBACK, nullptr, 0, 0, 0, &cg), "SolverCGDevice");
+    const int rc = mfgpu_cg_set_vcycle(cg, prec.get_vcycle());
+    if (rc != 0) {
+      mfgpu_cg_destroy(cg);
+      check(rc, "SolverCGDevice");
+    }
     run(cg, x, b);
   }
   template <typename MatrixType, typename PreconditionerType>

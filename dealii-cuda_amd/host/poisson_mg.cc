@@ -10,6 +10,9 @@
 // `typedef float level_number;`, bmop_mg.cu:58-59); -DMG_FUSED_SMOOTHER: the Chebyshev smoothers with fused vector
 // updates.  With either, two more columns:  mg_bytes (level operators, inverse diagonals, transfers, level vectors)
 // vcycle_ms (mean of 10 preconditioner applications after the solve, each between two device synchronisations)
+// -DPOISSON_DEVICE_MG (-devmg): the V-cycle is the library's mfgpu_vcycle (MultigridPreconditionerDevice: same smoothers'
+// lambda_max, the coarse level solved on the device) under the device CG, so the whole solve stops the host only in
+// mfgpu_cg_status; same arguments and output lines as the counterpart without the suffix
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -19,6 +22,9 @@
 #include <limits>
 #include <type_traits>
 
+#ifdef POISSON_DEVICE_MG
+#define POISSON_DEVICE_CG 1
+#endif
 #ifdef POISSON_DEVICE_CG
 #include "mfgpu_shim_poisson.h"  // SolverCGDevice: the outer CG on the device, the V-cycle through its callback (-devcg)
 #else
@@ -140,8 +146,13 @@ int run(int n_ref) {
 #endif
     mg_smoother[level].initialize(mg_matrices[level], sd);
   }
+#ifdef POISSON_DEVICE_MG
+  MultigridPreconditionerDevice<dim, LevelMatrixType, level_number, MGCoarseIterative<LevelMatrixType>, number> preconditioner(
+      dof_handler, mg_matrices, mg_coarse, mg_transfer, mg_smoother);
+#else
   MultigridPreconditioner<dim, LevelMatrixType, level_number, MGCoarseIterative<LevelMatrixType>> preconditioner(
       dof_handler, mg_matrices, mg_coarse, mg_transfer, mg_smoother);
+#endif
 
   // x*: zero on the Dirichlet dofs; b = A x*
   std::vector<number> xs(N);

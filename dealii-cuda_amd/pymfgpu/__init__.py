@@ -56,6 +56,24 @@ class CGInfo(C.Structure):
         return int(self.iterations), int(self.status), float(self.residual), float(self.initial_residual)
 
 
+VCYCLE_COARSE_AUTO, VCYCLE_COARSE_DENSE, VCYCLE_COARSE_CG = 0, 1, 2  # VCycleDesc.coarse (MFGPU_VCYCLE_COARSE_*)
+VCYCLE_DENSE_MAX = 2048
+
+
+class VCycleLevelDesc(C.Structure):
+    """mirror of struct mfgpu_vcycle_level_desc"""
+    _fields_ = [("op", C.c_void_p), ("edges", C.c_void_p), ("from_coarser", C.c_void_p), ("to_mg", C.c_void_p),
+                ("from_mg", C.c_void_p)]
+
+
+class VCycleDesc(C.Structure):
+    """mirror of struct mfgpu_vcycle_desc"""
+    _fields_ = [("n_levels", C.c_uint32), ("levels", C.POINTER(VCycleLevelDesc)), ("active_type", C.c_int32),
+                ("n_active", C.c_uint32), ("smoother_degree", C.c_uint32), ("smoothing_range", C.c_double),
+                ("eig_iterations", C.c_uint32), ("lambda_max", C.POINTER(C.c_double)), ("coarse", C.c_uint32),
+                ("coarse_tolerance", C.c_double), ("coarse_max_iterations", C.c_uint32)]
+
+
 # int fn(void *ctx, void *z_dev, const void *r_dev, void *stream)
 CG_CALLBACK_TYPE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
@@ -90,6 +108,9 @@ SYMBOLS = [
     "mfgpu_integrator_evaluate",
     "mfgpu_cg_create", "mfgpu_cg_set_callback", "mfgpu_cg_begin", "mfgpu_cg_iterate", "mfgpu_cg_status", "mfgpu_cg_solve",
     "mfgpu_cg_memory_consumption", "mfgpu_cg_destroy", "mfgpu_cg_chebyshev_scalars",
+    "mfgpu_cg_begin_relative", "mfgpu_cg_set_vcycle", "mfgpu_transfer_prolongate_add", "mfgpu_vec_residual",
+    "mfgpu_vcycle_create", "mfgpu_vcycle_apply", "mfgpu_vcycle_lambda_max", "mfgpu_vcycle_memory_consumption",
+    "mfgpu_vcycle_destroy", "mfgpu_estimate_lambda_max", "mfgpu_spd_inverse",
 ]
 
 _lib = None
@@ -232,6 +253,19 @@ def lib():
         L.mfgpu_cg_destroy.argtypes = [vp]
         L.mfgpu_cg_destroy.restype = None
         L.mfgpu_cg_chebyshev_scalars.argtypes = [u32, d, d, C.POINTER(d)]
+        L.mfgpu_cg_begin_relative.argtypes = [vp, vp, vp, d, u32, vp]
+        L.mfgpu_cg_set_vcycle.argtypes = [vp, vp]
+        L.mfgpu_transfer_prolongate_add.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_vec_residual.argtypes = [vp, vp, vp, z, i, vp]
+        L.mfgpu_vcycle_create.argtypes = [C.POINTER(VCycleDesc), C.POINTER(vp)]
+        L.mfgpu_vcycle_apply.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_vcycle_lambda_max.argtypes = [vp, C.POINTER(d)]
+        L.mfgpu_vcycle_memory_consumption.argtypes = [vp]
+        L.mfgpu_vcycle_memory_consumption.restype = C.c_size_t
+        L.mfgpu_vcycle_destroy.argtypes = [vp]
+        L.mfgpu_vcycle_destroy.restype = None
+        L.mfgpu_estimate_lambda_max.argtypes = [vp, vp, u32, C.POINTER(d)]
+        L.mfgpu_spd_inverse.argtypes = [u32, vp, vp]
         _lib = L
     return _lib
 
@@ -726,6 +760,18 @@ class CG:
         return self._done(lib().mfgpu_cg_begin(self._h, _optr(x), _optr(b), float(tolerance), int(max_iterations), stream),
                           check)
 
+    def begin_relative(self, x, b, relative_tolerance, max_iterations, stream=None, check=True):
+        """begin with tolerance = relative_tolerance * |b|, formed on the device (mfgpu_cg_begin_relative)"""
+        return self._done(lib().mfgpu_cg_begin_relative(self._h, _optr(x), _optr(b), float(relative_tolerance),
+                                                        int(max_iterations), stream), check)
+
+    def set_vcycle(self, vcycle: "VCycle", check=True):
+        """the library's own callback of a CG_CALLBACK solver: z = vcycle.apply(r) without a trip through Python"""
+        rc = lib().mfgpu_cg_set_vcycle(self._h, vcycle._h)
+        if rc == 0:
+            self._vcycle = vcycle  # borrowed by the library
+        return _check(rc) if check else rc
+
     def iterate(self, n_iterations=1, stream=None, check=True):
         return self._done(lib().mfgpu_cg_iterate(self._h, int(n_iterations), stream), check)
 
@@ -897,6 +943,10 @@ class Transfer:
     def prolongate(self, dst_fine, src_coarse, stream=None):
         _check(lib().mfgpu_transfer_prolongate(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
 
+    def prolongate_add(self, dst_fine, src_coarse, stream=None):
+        """dst_fine += P src_coarse"""
+        _check(lib().mfgpu_transfer_prolongate_add(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
+
     def restrict_and_add(self, dst_coarse, src_fine, stream=None):
         _check(lib().mfgpu_transfer_restrict_and_add(self._h, _ptr(dst_coarse), _ptr(src_fine), stream))
 
@@ -968,6 +1018,142 @@ def chebyshev_update(x, upd, r, t, dinv, f1, f2, n, number_type, stream=None, ch
     rc = lib().mfgpu_vec_chebyshev_update(_ptr(x), _ptr(upd), _ptr(r), _ptr(t), _ptr(dinv), float(f1), float(f2), n,
                                           number_type, stream)
     return _check(rc) if check else rc
+
+
+def vec_residual(t, b, e, n, number_type, stream=None, check=True):
+    """t = b - t (e None) or t = b - (t + e)"""
+    rc = lib().mfgpu_vec_residual(_ptr(t), _ptr(b), _optr(e), n, number_type, stream)
+    return _check(rc) if check else rc
+
+
+def estimate_lambda_max(op, inv_diag, min_iterations=15):
+    """1.2 x the power-iteration estimate of the largest eigenvalue of D^-1 A (mfgpu_estimate_lambda_max); blocks.
+    op: an Operator, a Level (its level matrix) or anything with the handle in _h"""
+    r = C.c_double()
+    _check(lib().mfgpu_estimate_lambda_max(_op_handle(op), _ptr(inv_diag), int(min_iterations), C.byref(r)))
+    return r.value
+
+
+def spd_inverse(a, check=True):
+    """the inverse of a symmetric positive definite matrix by the library's Cholesky (mfgpu_spd_inverse; only the lower
+    triangle of a is read); host only.  check=False: (code, inverse)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    assert a.ndim == 2 and a.shape[0] == a.shape[1]
+    inv = np.empty_like(a)
+    rc = lib().mfgpu_spd_inverse(a.shape[0], a.ctypes.data, inv.ctypes.data)
+    if check:
+        _check(rc)
+        return inv
+    return rc, inv
+
+
+def _op_handle(op):
+    """the mfgpu_handle of an Operator, of a Level (its level matrix) or a raw handle"""
+    if isinstance(op, Level):
+        return lib().mfgpu_level_operator(op._h)
+    return getattr(op, "_h", op)
+
+
+class VCycle:
+    """The multigrid V-cycle as one object (mfgpu_vcycle_*): z = M^-1 r with Chebyshev smoothers and a device-resident
+    coarse solve; apply only enqueues work.
+
+    levels: coarse to fine, one dict per level with "op" (an Operator, or a Level: then its level matrix with the level as
+    `edges` when has_edges is true), optional "transfer" (a Transfer from the coarser level; None on level 0), optional
+    "to_mg" / "from_mg" (IndexPairs; on every level or on none).  The pieces are borrowed by the library and kept alive
+    here.  options: smoother_degree, smoothing_range, eig_iterations, lambda_max (per level, or None = estimate),
+    coarse (VCYCLE_COARSE_*), coarse_tolerance, coarse_max_iterations."""
+
+    def __init__(self, levels, active_type, n_active, smoother_degree=0, smoothing_range=0.0, eig_iterations=0,
+                 lambda_max=None, coarse=VCYCLE_COARSE_AUTO, coarse_tolerance=0.0, coarse_max_iterations=0, keep=None):
+        self._keep = (levels, keep)
+        self.n_levels, self.active_type, self.n_active = len(levels), int(active_type), int(n_active)
+        ld = (VCycleLevelDesc * max(len(levels), 1))()
+        for l, lev in enumerate(levels):
+            op = lev.get("op")
+            if isinstance(op, Level):
+                ld[l].op = lib().mfgpu_level_operator(op._h)
+                ld[l].edges = op._h if lev.get("has_edges", False) else None
+            elif op is not None:
+                ld[l].op = getattr(op, "_h", op)
+                edges = lev.get("edges")
+                ld[l].edges = None if edges is None else edges._h
+            for key, field in (("transfer", "from_coarser"), ("to_mg", "to_mg"), ("from_mg", "from_mg")):
+                piece = lev.get(key)
+                setattr(ld[l], field, None if piece is None else piece._h)
+        d = VCycleDesc()
+        d.n_levels, d.levels = len(levels), ld
+        d.active_type, d.n_active = int(active_type), int(n_active)
+        d.smoother_degree, d.smoothing_range, d.eig_iterations = int(smoother_degree), float(smoothing_range), int(eig_iterations)
+        lam = None
+        if lambda_max is not None:
+            lam = (C.c_double * len(levels))(*[float(x) for x in lambda_max])
+            d.lambda_max = lam
+        d.coarse, d.coarse_tolerance, d.coarse_max_iterations = int(coarse), float(coarse_tolerance), int(coarse_max_iterations)
+        h = C.c_void_p()
+        _check(lib().mfgpu_vcycle_create(C.byref(d), C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def hierarchy_levels(mesh: "Mesh"):
+        """(levels, keep) of the constructor for the hierarchy of an adaptive stand-in mesh (Mesh.adaptive_mg): level
+        operators with refinement edges, transfers over the refined parents and the copy pairs of mfgpu_mg_*, all in the
+        mesh's number type"""
+        dim, p, nt = int(mesh.desc.dim), int(mesh.desc.degree), int(mesh.desc.number_type)
+        H = MgHierarchy(mesh)
+        nd, nfd = (p + 1) ** dim, (2 * p + 1) ** dim
+        meshes = [H.level_mesh(l) for l in range(H.n_levels)]
+        levels = []
+        for l, M in enumerate(meshes):
+            E = H.edge_dofs(l)
+            a, b = H.copy_pairs(l)
+            tr = None
+            if l > 0:
+                cd, fd = H.transfer_arrays(l, nd, nfd)
+                con = _view(meshes[l - 1].desc.constrained_dofs, meshes[l - 1].desc.n_constrained, np.uint32)
+                tr = Transfer.from_arrays(dim, p, cd, fd, meshes[l - 1].n_dofs, M.n_dofs, con, nt)
+            levels.append({"op": Level(M.desc, E, (M, H)), "has_edges": len(E) > 0, "n_dofs": M.n_dofs, "transfer": tr,
+                           "to_mg": IndexPairs(b, a), "from_mg": IndexPairs(a, b)})
+        return levels, (mesh, H, meshes)
+
+    @classmethod
+    def from_hierarchy(cls, mesh: "Mesh", level_type=F64, active_type=F64, **options):
+        """the local-smoothing V-cycle of an adaptive stand-in mesh (Mesh.adaptive_mg) built in level_type; the active
+        vectors are of active_type with mesh.n_dofs entries (a float V-cycle under a double CG)"""
+        if int(mesh.desc.number_type) != level_type:
+            raise MfgpuError("VCycle.from_hierarchy: build the mesh in the level number type (Mesh.adaptive_mg(..., "
+                             "number_type=level_type)); the active vectors may be of another type")
+        levels, keep = cls.hierarchy_levels(mesh)
+        return cls(levels, active_type, mesh.n_dofs, keep=keep, **options)
+
+    @classmethod
+    def from_meshes(cls, meshes, active_type=None, **options):
+        """globally refined cubes or balls, coarse to fine (uniform meshes of n, 2n, 4n ... cells per direction or balls
+        of successive n_ref): no edges, no pairs, the active vector is the finest level's"""
+        nt = int(meshes[0].desc.number_type)
+        levels = [{"op": Operator(M.desc, M), "n_dofs": M.n_dofs,
+                   "transfer": Transfer.from_meshes(meshes[l - 1], M) if l else None} for l, M in enumerate(meshes)]
+        return cls(levels, nt if active_type is None else active_type, meshes[-1].n_dofs, keep=list(meshes), **options)
+
+    def apply(self, z, r, stream=None, check=True):
+        """z = M^-1 r on active vectors (enqueued on `stream`)"""
+        rc = lib().mfgpu_vcycle_apply(self._h, _optr(z), _optr(r), stream)
+        return _check(rc) if check else rc
+
+    def lambda_max(self):
+        out = (C.c_double * self.n_levels)()
+        _check(lib().mfgpu_vcycle_lambda_max(self._h, out))
+        return np.array(out[:], dtype=np.float64)
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_vcycle_memory_consumption(self._h))
+
+    def destroy(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_vcycle_destroy(self._h)
+            self._h = None
+
+    __del__ = destroy
 
 
 def multi_groups(n_vectors, widths):

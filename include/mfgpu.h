@@ -369,6 +369,10 @@ int mfgpu_transfer_create(int dim, int degree, int number_type, uint32_t n_coars
 int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine_dev, const void *src_coarse_dev, void *stream);
 /* :631-660  dst_coarse += P^T src_fine on the non-Dirichlet coarse dofs (floating-point atomics, as the reference) */
 int mfgpu_transfer_restrict_and_add(mfgpu_transfer *t, void *dst_coarse_dev, const void *src_fine_dev, void *stream);
+/* dst_fine += P src_coarse: the coarse-grid correction of a V-cycle in one pass.  The prolongation kernel with a plain
+ * read-modify-write by the owner patch of every fine dof (no atomics: deterministic); fine dofs no patch lists are left
+ * alone.  The same numbers as mfgpu_transfer_prolongate into a temporary followed by mfgpu_vec_sadd(dst, 1, 1, tmp).    */
+int mfgpu_transfer_prolongate_add(mfgpu_transfer *t, void *dst_fine_dev, const void *src_coarse_dev, void *stream);
 size_t mfgpu_transfer_memory_consumption(const mfgpu_transfer *t); /* :333-347 */
 void mfgpu_transfer_destroy(mfgpu_transfer *t);
 
@@ -418,6 +422,10 @@ int mfgpu_vec_chebyshev_start(void *x, void *upd, void *r, const void *b, const 
                               int zero_start, size_t n, int number_type, void *stream);
 int mfgpu_vec_chebyshev_update(void *x, void *upd, void *r, const void *t, const void *dinv, double f1, double f2,
                                size_t n, int number_type, void *stream);
+/* t = b - t (e == NULL) or t = b - (t + e): the residual of a V-cycle level after t = A x, with the edge rows e = down x.
+ * One launch; the same numbers as mfgpu_vec_sadd(t, 1, 1, e) followed by mfgpu_vec_sadd(t, -1, 1, b).  16-byte accesses
+ * when every pointer is 16-byte aligned.  MFGPU_EINVAL: the range of t overlaps that of b or e.                    */
+int mfgpu_vec_residual(void *t, const void *b, const void *e, size_t n, int number_type, void *stream);
 
 /* ---- device-resident conjugate gradients (no reference counterpart: the reference calls deal.II's
  * SolverCG, whose three scalar products per iteration each stop the host).  The algorithm is SolverCG::solve of
@@ -461,6 +469,11 @@ int mfgpu_cg_set_callback(mfgpu_cg *s, int (*fn)(void *ctx, void *z_dev, const v
 /* x = 0, r = b, z = M^-1 r, p = z; status 1 with 0 iterations if |b| <= tolerance.  MFGPU_EINVAL, nothing written: null
  * pointers, CALLBACK without a callback, x overlapping b.  16-byte accesses when x, b and inv_diag are 16-byte aligned. */
 int mfgpu_cg_begin(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations, void *stream);
+/* The same with tolerance = relative_tolerance * |b|, formed on the device: the first direction launch of the solve
+ * writes it into the state block, so no norm visits the host (a solve inside a preconditioner, a captured graph).
+ * |b| = 0 ends with status 1 and 0 iterations.  MFGPU_EINVAL also for a negative or non-finite relative tolerance.    */
+int mfgpu_cg_begin_relative(mfgpu_cg *s, void *x_dev, const void *b_dev, double relative_tolerance,
+                            uint32_t max_iterations, void *stream);
 /* n_iterations more iterations (MFGPU_EINVAL before mfgpu_cg_begin): per iteration vmult, the partial sums of p.q, one
  * kernel for alpha, x += alpha p, r -= alpha q and the partial sums of r.r (NONE, JACOBI: and of r.z), the
  * preconditioner and the partial sums of r.z (CHEBYSHEV, CALLBACK), one kernel for count, status, beta, p = z + beta p */
@@ -478,6 +491,77 @@ void mfgpu_cg_destroy(mfgpu_cg *s);
  * sigma = theta / delta, rho_0 = 1 / sigma, rho_new = 1 / (2 sigma - rho), f1 = rho_new rho, f2 = 2 rho_new / delta).
  * MFGPU_EINVAL: null f, degree 0, lambda_max <= 0, smoothing_range <= 1.                                               */
 int mfgpu_cg_chebyshev_scalars(uint32_t degree, double lambda_max, double smoothing_range, double *f /* [2*degree-1] */);
+
+/* ---- the multigrid V-cycle as one object: deal.II's Multigrid::level_v_step + PreconditionMG with
+ * PreconditionChebyshev smoothers (poisson_mg.cu:343-380), composed from the level operators, transfers and copy pairs
+ * above, which it borrows: they must outlive it.  Schedule of one mfgpu_vcycle_apply: copy_to_mg; per level l > 0
+ * pre-smoothing from zero, t = defect - A x - down x, restrict_and_add into level l - 1; the coarse solve on level 0; on
+ * the way up x += P x_coarse, post-smoothing on defect - up x; copy_from_mg.  The smoother is the fused sweep of
+ * mfgpu_vec_chebyshev_start / _update on the inverse diagonal of the level matrix.
+ * mfgpu_vcycle_create is the set-up call: it may block and allocates everything -- per level l > 0 the vectors defect,
+ * solution, t, r, upd and the inverse diagonal (6 vectors of n_dofs(l) level numbers) and one more (edge) where the
+ * level has edges; on level 0, which has no smoother, defect and solution plus the coarse solver's data: DENSE the
+ * inverse in double, n0 rows of n0 rounded up to an even number of doubles; CG an internal mfgpu_cg
+ * (mfgpu_cg_memory_consumption).  mfgpu_vcycle_memory_consumption is exactly that sum.  (An estimate of level 0's
+ * lambda_max, made only when lambda_max == NULL, goes through an inverse diagonal that is freed again inside create.)
+ * mfgpu_vcycle_apply allocates nothing, synchronises nothing and reads nothing back: kernels and device-to-device copies
+ * on `stream` only, no memset nodes; it can be captured in a graph.  One object is used on one stream at a time.
+ * After mfgpu_level_update_coefficients the inverse diagonals, eigenvalue estimates and the dense inverse are stale: create
+ * a new mfgpu_vcycle.                                                                                                   */
+#define MFGPU_VCYCLE_COARSE_AUTO 0  /* DENSE when n_dofs(0) <= MFGPU_VCYCLE_DENSE_MAX, else CG */
+#define MFGPU_VCYCLE_COARSE_DENSE 1 /* x = A0^-1 b with the inverse formed at creation (host Cholesky in double): one launch */
+#define MFGPU_VCYCLE_COARSE_CG 2    /* unpreconditioned device CG, coarse_max_iterations iterations enqueued per apply.
+                                       Cost: EVERY apply enqueues all of them -- one vmult and three solver launches
+                                       each -- whether or not the solve has frozen before; the frozen ones run and write
+                                       nothing.  With the default n_dofs(0) that is thousands of launches per V-cycle
+                                       where AUTO picks this mode (above the dense cap): set coarse_max_iterations to
+                                       what the level-0 problem needs (DESIGN.md section 16 has a measured case)   */
+#define MFGPU_VCYCLE_DENSE_MAX 2048 /* 32 MB of inverse */
+
+typedef struct mfgpu_vcycle mfgpu_vcycle;
+typedef struct mfgpu_vcycle_level_desc {
+  mfgpu_handle *op;                 /* level matrix, borrowed (mfgpu_level_operator(edges) or an mfgpu_create handle) */
+  mfgpu_level *edges;               /* NULL: no refinement edges on this level; else op == mfgpu_level_operator(edges) */
+  mfgpu_transfer *from_coarser;     /* level-1 -> level; NULL on level 0 only */
+  const mfgpu_index_pairs *to_mg;   /* level <- active; NULL on EVERY level = globally refined: the active vector IS */
+  const mfgpu_index_pairs *from_mg; /* active <- level;   the finest level's vector (n_active == n_dofs(top))         */
+} mfgpu_vcycle_level_desc;
+typedef struct mfgpu_vcycle_desc {
+  uint32_t n_levels;
+  const mfgpu_vcycle_level_desc *levels;
+  int32_t active_type;            /* type and length of z and r of mfgpu_vcycle_apply; the type may differ from the    */
+  uint32_t n_active;              /* levels' (a float V-cycle under a double CG: converted in the copies)              */
+  uint32_t smoother_degree;       /* 0 = 5  */
+  double smoothing_range;         /* 0 = 15 */
+  uint32_t eig_iterations;        /* 0 = 15: minimum number of power-iteration steps */
+  const double *lambda_max;       /* [n_levels] or NULL = estimate (level 0's entry is not used by the coarse solvers) */
+  uint32_t coarse;                /* MFGPU_VCYCLE_COARSE_* */
+  double coarse_tolerance;        /* CG: relative, 0 = max(1e-10, 100 eps of the level type) */
+  uint32_t coarse_max_iterations; /* CG: 0 = n_dofs(0) */
+} mfgpu_vcycle_desc;
+/* MFGPU_EINVAL, nothing created: null pointers, n_levels == 0, a level without op, a missing transfer above level 0 or one
+ * whose sizes or type are not the two levels'; edges with an op that is not that level's operator; levels of different
+ * number types; pairs on some levels and not on others (or only one of to_mg / from_mg); no pairs and n_active !=
+ * n_dofs(top); a smoothing range <= 1 or a lambda_max <= 0 on a level above 0; an unknown coarse mode; DENSE above
+ * MFGPU_VCYCLE_DENSE_MAX; a level-0 matrix that is not positive definite (the V-cycle is an SPD preconditioner by
+ * contract; a mass term with c < 0 is the caller's business).                                                       */
+int mfgpu_vcycle_create(const mfgpu_vcycle_desc *d, mfgpu_vcycle **out);
+int mfgpu_vcycle_apply(mfgpu_vcycle *v, void *z_dev, const void *r_dev, void *stream); /* z = M^-1 r */
+/* the smoothers' lambda_max (given or estimated; with an estimate, level 0's too) */
+int mfgpu_vcycle_lambda_max(const mfgpu_vcycle *v, double *lambda /* [n_levels] */);
+size_t mfgpu_vcycle_memory_consumption(const mfgpu_vcycle *v);
+void mfgpu_vcycle_destroy(mfgpu_vcycle *v);
+/* MFGPU_CG_CALLBACK solvers: the library's own callback, z = M^-1 r = mfgpu_vcycle_apply(v, z, r, stream).  MFGPU_EINVAL:
+ * not a CALLBACK solver, or the V-cycle's active type / length are not the solver's.  v must outlive the solves.      */
+int mfgpu_cg_set_vcycle(mfgpu_cg *s, mfgpu_vcycle *v);
+/* PreconditionChebyshev's eigenvalue estimate (host/mfgpu_shim_mg.h): power iteration on D^-1 A from the start vector
+ * sin(0.7 i) + 0.3, at least max(5, min_iterations) steps, on until the estimate moves by <= 1 % per step, at most 200;
+ * *lambda_max = 1.2 x the estimate.  inv_diag_dev: the operator's number type.  A blocking set-up call (two norms per
+ * step are read back; two work vectors are allocated and freed).                                                    */
+int mfgpu_estimate_lambda_max(mfgpu_handle *op, const void *inv_diag_dev, uint32_t min_iterations, double *lambda_max);
+/* host only, no device: inv = a^-1 for a symmetric positive definite a [n * n] (row-major; only the lower triangle is
+ * read) by a Cholesky factorisation in double.  MFGPU_EINVAL on a non-positive (or non-finite) pivot; inv may not alias a. */
+int mfgpu_spd_inverse(uint32_t n, const double *a, double *inv);
 
 /* ---- cell integrals of a Poisson solve (poisson.cu:152-229, 277-292) ------------------------------------------
  * A separate object created from the same description as the operator; it keeps its own device copy of the geometry
