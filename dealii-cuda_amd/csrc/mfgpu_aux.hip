@@ -11,6 +11,7 @@
 
 #include "mfgpu_cell.h"
 #include "mfgpu_kernels.h"
+#include "mfgpu_stream.h"
 
 namespace mfgpu {
 
@@ -335,8 +336,6 @@ hipError_t set_values_launch(T *v, const uint32_t *idx, uint32_t n, T value, hip
 // ---------------------------------------------------------------------------------------------
 enum VecOp { OP_SADD, OP_EQU, OP_SCALE, OP_DIVIDE, OP_INVERT, OP_MUL };
 
-constexpr unsigned kVecBlocks = 2048;  // 256 CUs x 8 resident blocks of 256 threads, grid-stride
-
 template <int OP, typename T>
 __global__ void __launch_bounds__(256) vec_map_kernel(T *__restrict__ v, const T *__restrict__ w, T s, T a, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -353,11 +352,10 @@ __global__ void __launch_bounds__(256) vec_map_kernel(T *__restrict__ v, const T
 template <typename T>
 hipError_t vec_map_launch(int op, T *v, const T *w, T s, T a, size_t n, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > kVecBlocks) blocks = kVecBlocks;
+  const unsigned blocks = stream_grid(n, 1, false);
 #define MAP_CASE(OP)                                                                                         \
   case OP:                                                                                                   \
-    hipLaunchKernelGGL((vec_map_kernel<OP, T>), dim3((unsigned)blocks), dim3(256), 0, st, v, w, s, a, n);    \
+    hipLaunchKernelGGL((vec_map_kernel<OP, T>), dim3(blocks), dim3(256), 0, st, v, w, s, a, n);              \
     break;
   switch (op) {
     MAP_CASE(OP_SADD) MAP_CASE(OP_EQU) MAP_CASE(OP_SCALE) MAP_CASE(OP_DIVIDE) MAP_CASE(OP_INVERT) MAP_CASE(OP_MUL)
@@ -368,12 +366,6 @@ hipError_t vec_map_launch(int op, T *v, const T *w, T s, T a, size_t n, hipStrea
 }
 
 enum RedOp { RED_DOT, RED_ADD_AND_DOT, RED_NONZERO };
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
 
 // stage 1: one partial per block, accumulated in double (also for float vectors), fixed order
 template <int OP, typename T>
@@ -392,25 +384,19 @@ vec_reduce_kernel(double *__restrict__ partial, T *__restrict__ v, const T *__re
     }
     if (OP == RED_NONZERO) acc += (v[i] != T(0)) ? 1.0 : 0.0;  // all_zero           gpu_vec.cu:445-470,512-540
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  acc = block_sum<false>(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-// stage 2: one block sums the partials in a fixed order
+// stage 2: one block sums the partials in a fixed order (resum, mfgpu_stream.h)
 __global__ void __launch_bounds__(256) vec_reduce_final(double *__restrict__ result, const double *__restrict__ partial,
                                                          unsigned np) {
   __shared__ double red[4];
-  double acc = 0.0;
-  for (unsigned i = threadIdx.x; i < np; i += 256) acc += partial[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) *result = (red[0] + red[1]) + (red[2] + red[3]);
+  const double sum = resum<false>(partial, np, red);
+  if (threadIdx.x == 0) *result = sum;
 }
 
-// scratch of the reductions: kVecBlocks partials + the result, one set per device, allocated on first
+// scratch of the reductions: kStreamBlocks partials + the result, one set per device, allocated on first
 // use and kept (reductions are serialised by the mutex: they end in a blocking copy of the result anyway)
 static std::mutex g_red_mutex;
 static double *g_red_buf[64] = {};
@@ -423,16 +409,14 @@ hipError_t vec_reduce_launch(int op, T *v, const T *x, const T *w, T a, size_t n
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
   if (!g_red_buf[dev]) {
-    e = hipMalloc((void **)&g_red_buf[dev], (kVecBlocks + 1) * sizeof(double));
+    e = hipMalloc((void **)&g_red_buf[dev], (kStreamBlocks + 1) * sizeof(double));
     if (e != hipSuccess) return e;
   }
-  double *partial = g_red_buf[dev], *result = partial + kVecBlocks;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > kVecBlocks) blocks = kVecBlocks;
-  if (blocks == 0) blocks = 1;
+  double *partial = g_red_buf[dev], *result = partial + kStreamBlocks;
+  const unsigned blocks = stream_grid(n, 1, false);
 #define RED_CASE(OP)                                                                                         \
   case OP:                                                                                                   \
-    hipLaunchKernelGGL((vec_reduce_kernel<OP, T>), dim3((unsigned)blocks), dim3(256), 0, st, partial, v, x, w, a, n); \
+    hipLaunchKernelGGL((vec_reduce_kernel<OP, T>), dim3(blocks), dim3(256), 0, st, partial, v, x, w, a, n); \
     break;
   switch (op) {
     RED_CASE(RED_DOT) RED_CASE(RED_ADD_AND_DOT) RED_CASE(RED_NONZERO)
@@ -441,7 +425,7 @@ hipError_t vec_reduce_launch(int op, T *v, const T *x, const T *w, T a, size_t n
 #undef RED_CASE
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(vec_reduce_final, dim3(1), dim3(256), 0, st, result, partial, (unsigned)blocks);
+  hipLaunchKernelGGL(vec_reduce_final, dim3(1), dim3(256), 0, st, result, partial, blocks);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = hipMemcpyAsync(out, result, sizeof(double), hipMemcpyDeviceToHost, st);

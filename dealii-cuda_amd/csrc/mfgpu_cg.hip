@@ -6,11 +6,11 @@
 //   cg_update_kernel     (b) sums the p.q partials, alpha = rz / pq, x += alpha p, r -= alpha q, partial sums of r.r
 //                            (and of r.z for NONE / JACOBI)
 //   cg_direction_kernel  (c) sums the r.r / r.z partials, updates count and status, beta = rz_new / rz, p = z + beta p
-// Streaming kernels as mfgpu_mixed.hip: grid-stride over 16-byte chunks per lane, a scalar loop for the tail and for
-// unaligned vectors, at most 2048 blocks of 256 threads.  Reductions as vec_reduce_kernel (mfgpu_aux.hip): double
-// accumulation, one partial per block, fixed order; EVERY block of the consuming kernel re-sums the <= 2048 partials in
-// the order of vec_reduce_final, so all blocks hold the same bits of alpha and beta.  No atomics, no counters, no grid
-// barrier.
+// Streaming kernels on the skeleton of mfgpu_stream.h: grid-stride over 16-byte chunks per lane, the same body on single
+// elements for the tail and for unaligned vectors, at most kStreamBlocks blocks of 256 threads.  Reductions with its
+// block_sum / resum: double accumulation, one partial per block, fixed order; EVERY block of the consuming kernel
+// re-sums the <= kStreamBlocks partials with the code of vec_reduce_final (mfgpu_aux.hip), so all blocks hold the same
+// bits of alpha and beta.  No atomics, no counters, no grid barrier.
 // State block rule: no kernel reads a field that the same kernel writes (another block could see either value).
 // cg_init_kernel writes the `begin` and `direction` fields and reads none; cg_update_kernel reads the `direction`
 // fields and writes the `update` fields; cg_direction_kernel reads the `begin` and `update` fields and writes the
@@ -26,10 +26,11 @@
 #include <vector>
 
 #include "mfgpu_device.h"
+#include "mfgpu_stream.h"
+
+using namespace mfgpu;
 
 namespace {
-
-constexpr unsigned kBlocks = 2048;  // 256 CUs x 8 resident blocks of 256 threads, grid-stride (as mfgpu_aux.hip)
 
 struct CgState {
   // begin: written by cg_init_kernel
@@ -50,58 +51,6 @@ static_assert(sizeof(CgState) == 128, "the state block is 128 bytes (mfgpu_cg_me
 
 enum Prec { P_NONE = MFGPU_CG_NONE, P_JACOBI = MFGPU_CG_JACOBI, P_STORED = 2 };  // P_STORED: z is a vector (CHEBYSHEV, CALLBACK)
 
-template <typename T>
-constexpr int lanes16() {
-  return 16 / (int)sizeof(T);
-}
-
-template <typename T>
-__device__ __forceinline__ void ld16(const T *p, T (&v)[lanes16<T>()]) {
-  if constexpr (sizeof(T) == 8) {
-    const double2 a = *reinterpret_cast<const double2 *>(p);
-    v[0] = a.x;
-    v[1] = a.y;
-  } else {
-    const float4 a = *reinterpret_cast<const float4 *>(p);
-    v[0] = a.x;
-    v[1] = a.y;
-    v[2] = a.z;
-    v[3] = a.w;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void st16(T *p, const T (&v)[lanes16<T>()]) {
-  if constexpr (sizeof(T) == 8) {
-    *reinterpret_cast<double2 *>(p) = make_double2(v[0], v[1]);
-  } else {
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
-
-// the block's sum of acc over its 256 threads, on every thread (wave sums, then the four waves in a fixed order)
-__device__ __forceinline__ double block_sum(double acc, double *red) {
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  const double s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
-}
-
-// sum of np partials in the order of vec_reduce_final: the same bits in every block
-__device__ __forceinline__ double resum(const double *__restrict__ partial, unsigned np, double *red) {
-  double acc = 0.0;
-  for (unsigned i = threadIdx.x; i < np; i += 256) acc += partial[i];
-  return block_sum(acc, red);
-}
-
 // begin: x = 0, r = b; partials of r.r and, for JACOBI, of r.(dinv r)
 template <typename T, bool VEC, int PREC>
 __global__ void __launch_bounds__(256)
@@ -109,35 +58,22 @@ cg_init_kernel(CgState *__restrict__ s, T *__restrict__ x, T *__restrict__ r, co
                const T *__restrict__ dinv, double *__restrict__ prr, double *__restrict__ prz, double tolerance,
                uint32_t relative, uint32_t max_iterations, size_t n) {
   __shared__ double red[4];
-  constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
   double arr = 0.0, arz = 0.0;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / W;
-    for (size_t c = tid; c < nc; c += stride) {
-      const size_t o = c * W;
-      T bv[W], dv[W], zero[W];
-      ld16<T>(b + o, bv);
-      if (PREC == P_JACOBI) ld16<T>(dinv + o, dv);
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T bv[W], dv[W], zero[W];
+    ldw<W>(b + o, bv);
+    if (PREC == P_JACOBI) ldw<W>(dinv + o, dv);
 #pragma unroll
-      for (int k = 0; k < W; ++k) {
-        zero[k] = T(0);
-        arr += (double)bv[k] * (double)bv[k];
-        if (PREC == P_JACOBI) arz += (double)bv[k] * (double)(dv[k] * bv[k]);
-      }
-      st16<T>(x + o, zero);
-      st16<T>(r + o, bv);
+    for (int k = 0; k < W; ++k) {
+      zero[k] = T(0);
+      arr += (double)bv[k] * (double)bv[k];
+      if (PREC == P_JACOBI) arz += (double)bv[k] * (double)(dv[k] * bv[k]);
     }
-    done = nc * W;
-  }
-  for (size_t i = done + tid; i < n; i += stride) {
-    const T bi = b[i];
-    x[i] = T(0);
-    r[i] = bi;
-    arr += (double)bi * (double)bi;
-    if (PREC == P_JACOBI) arz += (double)bi * (double)(dinv[i] * bi);
-  }
+    stw<W>(x + o, zero);
+    stw<W>(r + o, bv);
+  });
   arr = block_sum(arr, red);
   if (PREC == P_JACOBI) arz = block_sum(arz, red);
   if (threadIdx.x == 0) {
@@ -160,22 +96,16 @@ cg_dot_kernel(const CgState *__restrict__ s, double *__restrict__ partial, const
               const T *__restrict__ w, size_t n) {
   __shared__ double red[4];
   if (s->status != 0) return;
-  constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
   double acc = 0.0;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / W;
-    for (size_t c = tid; c < nc; c += stride) {
-      T a[W], b[W];
-      ld16<T>(v + c * W, a);
-      ld16<T>(w + c * W, b);
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T a[W], b[W];
+    ldw<W>(v + o, a);
+    ldw<W>(w + o, b);
 #pragma unroll
-      for (int k = 0; k < W; ++k) acc += (double)a[k] * (double)b[k];
-    }
-    done = nc * W;
-  }
-  for (size_t i = done + tid; i < n; i += stride) acc += (double)v[i] * (double)w[i];
+    for (int k = 0; k < W; ++k) acc += (double)a[k] * (double)b[k];
+  });
   acc = block_sum(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
@@ -213,34 +143,22 @@ cg_update_kernel(CgState *__restrict__ s, T *__restrict__ x, T *__restrict__ r, 
     s->it_old = s->iterations;
   }
   if (!ok) return;
-  constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
   double arr = 0.0, arz = 0.0;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / W;
-    for (size_t c = tid; c < nc; c += stride) {
-      const size_t o = c * W;
-      T xv[W], rv[W], pv[W], qv[W], dv[W];
-      ld16<T>(x + o, xv);
-      ld16<T>(r + o, rv);
-      ld16<T>(p + o, pv);
-      ld16<T>(q + o, qv);
-      if (PREC == P_JACOBI) ld16<T>(dinv + o, dv);
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T xv[W], rv[W], pv[W], qv[W], dv[W];
+    ldw<W>(x + o, xv);
+    ldw<W>(r + o, rv);
+    ldw<W>(p + o, pv);
+    ldw<W>(q + o, qv);
+    if (PREC == P_JACOBI) ldw<W>(dinv + o, dv);
 #pragma unroll
-      for (int k = 0; k < W; ++k)
-        update_elem<T, PREC>(xv[k], rv[k], pv[k], qv[k], PREC == P_JACOBI ? dv[k] : T(0), alpha, arr, arz);
-      st16<T>(x + o, xv);
-      st16<T>(r + o, rv);
-    }
-    done = nc * W;
-  }
-  for (size_t i = done + tid; i < n; i += stride) {
-    T xi = x[i], ri = r[i];
-    update_elem<T, PREC>(xi, ri, p[i], q[i], PREC == P_JACOBI ? dinv[i] : T(0), alpha, arr, arz);
-    x[i] = xi;
-    r[i] = ri;
-  }
+    for (int k = 0; k < W; ++k)
+      update_elem<T, PREC>(xv[k], rv[k], pv[k], qv[k], PREC == P_JACOBI ? dv[k] : T(0), alpha, arr, arz);
+    stw<W>(x + o, xv);
+    stw<W>(r + o, rv);
+  });
   arr = block_sum(arr, red);
   if (PREC == P_JACOBI) arz = block_sum(arz, red);
   if (threadIdx.x == 0) {
@@ -286,47 +204,27 @@ cg_direction_kernel(CgState *__restrict__ s, T *__restrict__ p, const T *__restr
     if (first && relative) s->tolerance_abs = tolerance;
   }
   if (status != 0) return;
-  constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / W;
-    for (size_t c = tid; c < nc; c += stride) {
-      const size_t o = c * W;
-      T pv[W], zv[W], dv[W];
-      if (PREC == P_STORED) {
-        ld16<T>(z + o, zv);
-      } else {
-        ld16<T>(r + o, zv);
-        if (PREC == P_JACOBI) {
-          ld16<T>(dinv + o, dv);
+  const bool is_first = first != 0;  // a local: the parameter itself, captured by reference, changes the code above
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T pv[W], zv[W], dv[W];
+    ldw<W>((PREC == P_STORED ? z : r) + o, zv);
+    if (PREC == P_JACOBI) {
+      ldw<W>(dinv + o, dv);
 #pragma unroll
-          for (int k = 0; k < W; ++k) zv[k] = dv[k] * zv[k];
-        }
-      }
-      if (first) {
-        st16<T>(p + o, zv);
-      } else {
-        ld16<T>(p + o, pv);
-#pragma unroll
-        for (int k = 0; k < W; ++k) pv[k] = beta * pv[k] + zv[k];
-        st16<T>(p + o, pv);
-      }
+      for (int k = 0; k < W; ++k) zv[k] = dv[k] * zv[k];
     }
-    done = nc * W;
-  }
-  for (size_t i = done + tid; i < n; i += stride) {
-    const T zi = PREC == P_STORED ? z[i] : PREC == P_JACOBI ? dinv[i] * r[i] : r[i];
-    p[i] = first ? zi : beta * p[i] + zi;
-  }
+    if (is_first) {
+      stw<W>(p + o, zv);
+    } else {
+      ldw<W>(p + o, pv);
+#pragma unroll
+      for (int k = 0; k < W; ++k) pv[k] = beta * pv[k] + zv[k];
+      stw<W>(p + o, pv);
+    }
+  });
 }
-
-int einval(const char *msg) {
-  mfgpu::set_error(msg);
-  return MFGPU_EINVAL;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
@@ -338,7 +236,7 @@ struct mfgpu_cg {
   std::vector<double> cheb;  // mfgpu_cg_chebyshev_scalars
   uint32_t degree = 0;
   mfgpu::DeviceArray<void> r, p, q, z, cheb_r, cheb_upd, cheb_t;
-  mfgpu::DeviceArray<double> partials;  // p.q | r.r | r.z, kBlocks each
+  mfgpu::DeviceArray<double> partials;  // p.q | r.r | r.z, kStreamBlocks each
   mfgpu::DeviceArray<CgState> state;
   CgState *mirror = nullptr;  // pinned
   int (*fn)(void *, void *, const void *, void *) = nullptr;
@@ -358,28 +256,19 @@ namespace {
 
 int kernel_prec(const mfgpu_cg *s) { return s->prec == MFGPU_CG_NONE ? P_NONE : s->prec == MFGPU_CG_JACOBI ? P_JACOBI : P_STORED; }
 
-// one launch of KERNEL<T, VEC, PREC> with the solver's (vec, prec)
-#define CG_LAUNCH(KERNEL, ...)                                                                                    \
-  do {                                                                                                            \
-    const int sel = (s->vec ? 3 : 0) + kernel_prec(s);                                                            \
-    switch (sel) {                                                                                                \
-      case 0: hipLaunchKernelGGL((KERNEL<T, false, P_NONE>), dim3(s->grid), dim3(256), 0, st, __VA_ARGS__); break;   \
-      case 1: hipLaunchKernelGGL((KERNEL<T, false, P_JACOBI>), dim3(s->grid), dim3(256), 0, st, __VA_ARGS__); break; \
-      case 2: hipLaunchKernelGGL((KERNEL<T, false, P_STORED>), dim3(s->grid), dim3(256), 0, st, __VA_ARGS__); break; \
-      case 3: hipLaunchKernelGGL((KERNEL<T, true, P_NONE>), dim3(s->grid), dim3(256), 0, st, __VA_ARGS__); break;    \
-      case 4: hipLaunchKernelGGL((KERNEL<T, true, P_JACOBI>), dim3(s->grid), dim3(256), 0, st, __VA_ARGS__); break;  \
-      default: hipLaunchKernelGGL((KERNEL<T, true, P_STORED>), dim3(s->grid), dim3(256), 0, st, __VA_ARGS__); break; \
-    }                                                                                                             \
-  } while (0)
+// f(VEC, PREC) with the solver's (vec, prec) as constants: one launch of a kernel<T, VEC(), PREC()>
+template <typename F>
+void with_vec_prec(const mfgpu_cg *s, F &&f) {
+  static_assert(P_NONE == 0 && P_JACOBI == 1 && P_STORED == 2, "OneOf3 carries the Prec");
+  dispatch(f, s->vec, OneOf3{kernel_prec(s)});
+}
 
 template <typename T>
 int dot_launch(mfgpu_cg *s, double *partial, const void *v, const void *w, hipStream_t st) {
-  if (s->vec)
-    hipLaunchKernelGGL((cg_dot_kernel<T, true>), dim3(s->grid), dim3(256), 0, st, s->state.get(), partial,
+  dispatch([&](auto VEC) {
+    hipLaunchKernelGGL((cg_dot_kernel<T, VEC()>), dim3(s->grid), dim3(256), 0, st, s->state.get(), partial,
                        (const T *)v, (const T *)w, s->n);
-  else
-    hipLaunchKernelGGL((cg_dot_kernel<T, false>), dim3(s->grid), dim3(256), 0, st, s->state.get(), partial,
-                       (const T *)v, (const T *)w, s->n);
+  }, s->vec);
   return mfgpu::hip_check(hipGetLastError(), "mfgpu_cg: dot");
 }
 
@@ -405,22 +294,28 @@ int precondition(mfgpu_cg *s, hipStream_t st) {
         return rc;
     }
   }
-  return dot_launch<T>(s, s->partials.get() + 2 * kBlocks, r, z, st);
+  return dot_launch<T>(s, s->partials.get() + 2 * kStreamBlocks, r, z, st);
 }
 
 template <typename T>
 int direction_launch(mfgpu_cg *s, int first, hipStream_t st) {
-  double *prr = s->partials.get() + kBlocks, *prz = prr + kBlocks;
-  CG_LAUNCH(cg_direction_kernel, s->state.get(), (T *)s->p.get(), (const T *)s->r.get(), (const T *)s->z.get(),
-            (const T *)s->dinv, (const double *)prr, (const double *)prz, s->grid, first, s->n);
+  double *prr = s->partials.get() + kStreamBlocks, *prz = prr + kStreamBlocks;
+  with_vec_prec(s, [&](auto VEC, auto PREC) {
+    hipLaunchKernelGGL((cg_direction_kernel<T, VEC(), PREC()>), dim3(s->grid), dim3(256), 0, st, s->state.get(),
+                       (T *)s->p.get(), (const T *)s->r.get(), (const T *)s->z.get(), (const T *)s->dinv,
+                       (const double *)prr, (const double *)prz, s->grid, first, s->n);
+  });
   return mfgpu::hip_check(hipGetLastError(), "mfgpu_cg: direction update");
 }
 
 template <typename T>
 int begin_typed(mfgpu_cg *s, double tolerance, uint32_t relative, uint32_t max_iterations, hipStream_t st) {
-  double *prr = s->partials.get() + kBlocks, *prz = prr + kBlocks;
-  CG_LAUNCH(cg_init_kernel, s->state.get(), (T *)s->x, (T *)s->r.get(), (const T *)s->b, (const T *)s->dinv, prr, prz,
-            tolerance, relative, max_iterations, s->n);
+  double *prr = s->partials.get() + kStreamBlocks, *prz = prr + kStreamBlocks;
+  with_vec_prec(s, [&](auto VEC, auto PREC) {
+    hipLaunchKernelGGL((cg_init_kernel<T, VEC(), PREC()>), dim3(s->grid), dim3(256), 0, st, s->state.get(), (T *)s->x,
+                       (T *)s->r.get(), (const T *)s->b, (const T *)s->dinv, prr, prz, tolerance, relative,
+                       max_iterations, s->n);
+  });
   if (const int rc = mfgpu::hip_check(hipGetLastError(), "mfgpu_cg_begin")) return rc;
   if (const int rc = precondition<T>(s, st)) return rc;
   return direction_launch<T>(s, 1, st);
@@ -428,12 +323,15 @@ int begin_typed(mfgpu_cg *s, double tolerance, uint32_t relative, uint32_t max_i
 
 template <typename T>
 int iterate_typed(mfgpu_cg *s, uint32_t n_iterations, hipStream_t st) {
-  double *ppq = s->partials.get(), *prr = ppq + kBlocks, *prz = prr + kBlocks;
+  double *ppq = s->partials.get(), *prr = ppq + kStreamBlocks, *prz = prr + kStreamBlocks;
   for (uint32_t it = 0; it < n_iterations; ++it) {
     if (const int rc = mfgpu_vmult(s->A, s->q.get(), s->p.get(), (void *)st)) return rc;
     if (const int rc = dot_launch<T>(s, ppq, s->p.get(), s->q.get(), st)) return rc;
-    CG_LAUNCH(cg_update_kernel, s->state.get(), (T *)s->x, (T *)s->r.get(), (const T *)s->p.get(),
-              (const T *)s->q.get(), (const T *)s->dinv, (const double *)ppq, prr, prz, s->grid, s->n);
+    with_vec_prec(s, [&](auto VEC, auto PREC) {
+      hipLaunchKernelGGL((cg_update_kernel<T, VEC(), PREC()>), dim3(s->grid), dim3(256), 0, st, s->state.get(),
+                         (T *)s->x, (T *)s->r.get(), (const T *)s->p.get(), (const T *)s->q.get(), (const T *)s->dinv,
+                         (const double *)ppq, prr, prz, s->grid, s->n);
+    });
     if (const int rc = mfgpu::hip_check(hipGetLastError(), "mfgpu_cg_iterate")) return rc;
     if (const int rc = precondition<T>(s, st)) return rc;
     if (const int rc = direction_launch<T>(s, 0, st)) return rc;
@@ -495,7 +393,7 @@ int mfgpu_cg_create(mfgpu_handle *A, int preconditioner, const void *inv_diag_de
   mfgpu::DeviceArray<void> *vectors[7] = {&s->r, &s->p, &s->q, &s->z, &s->cheb_r, &s->cheb_upd, &s->cheb_t};
   const int n_vectors = preconditioner == MFGPU_CG_CHEBYSHEV ? 7 : preconditioner == MFGPU_CG_CALLBACK ? 4 : 3;
   for (int v = 0; v < n_vectors && !rc; ++v) rc = vectors[v]->alloc(vbytes, true);
-  if (!rc) rc = s->partials.alloc(3 * kBlocks, true);
+  if (!rc) rc = s->partials.alloc(3 * kStreamBlocks, true);
   if (!rc) rc = s->state.alloc(1, true);
   if (!rc) rc = mfgpu::hip_check(hipHostMalloc((void **)&s->mirror, sizeof(CgState), hipHostMallocDefault), "mfgpu_cg_create");
   if (rc) {
@@ -526,9 +424,7 @@ int begin_common(mfgpu_cg *s, void *x_dev, const void *b_dev, double tolerance, 
   s->x = x_dev;
   s->b = b_dev;
   s->vec = aligned16(x_dev) && aligned16(b_dev) && aligned16(s->dinv);
-  const size_t lanes = 16 / mfgpu::esize(s->number_type);
-  const size_t work = s->vec ? s->n / lanes + s->n % lanes : s->n, blocks = (work + 255) / 256;
-  s->grid = (unsigned)(blocks == 0 ? 1 : blocks > kBlocks ? kBlocks : blocks);
+  s->grid = stream_grid(s->n, 16 / mfgpu::esize(s->number_type), s->vec);
   s->begun = true;
   return s->number_type == MFGPU_F64 ? begin_typed<double>(s, tolerance, relative, max_iterations, (hipStream_t)stream)
                                      : begin_typed<float>(s, tolerance, relative, max_iterations, (hipStream_t)stream);

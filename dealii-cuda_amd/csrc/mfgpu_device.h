@@ -24,6 +24,12 @@ inline int hip_check(hipError_t e, const char *what) {
     if (const int rc_ = mfgpu::hip_check((expr), #expr)) return rc_;         \
   } while (0)
 
+// MFGPU_EINVAL with msg left for mfgpu_last_error()
+inline int einval(const char *msg) {
+  set_error(msg);
+  return MFGPU_EINVAL;
+}
+
 inline size_t esize(int number_type) { return number_type == MFGPU_F32 ? 4 : 8; }
 inline bool valid_number_type(int number_type) { return number_type == MFGPU_F64 || number_type == MFGPU_F32; }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "mfgpu_cell.h"
+#include "mfgpu_stream.h"
 
 using namespace mfgpu;
 
@@ -201,12 +202,6 @@ __device__ __forceinline__ void hn_resolve(double *v, unsigned mask, const doubl
   hn_dir<dim, N, TR, 0>(v, mask, W);
   hn_dir<dim, N, TR, 1>(v, mask, W);
   if constexpr (dim == 3) hn_dir<dim, N, TR, 2>(v, mask, W);
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
 }
 
 template <int N>

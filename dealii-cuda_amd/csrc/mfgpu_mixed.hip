@@ -5,89 +5,34 @@
 //   mfgpu_vec_chebyshev_start    the vector updates of one PreconditionChebyshev sweep (host/mfgpu_shim_mg.h) in ONE
 //   mfgpu_vec_chebyshev_update   launch each instead of the BLAS-1 sequence r.add, t.equ, t.scale, upd.sadd, x.add
 //   mfgpu_vec_residual           t = b - t or t = b - (t + e) in one launch instead of add + sadd (the V-cycle's residual)
-// All kernels stream: grid-stride over 16-byte chunks per lane (2 doubles or 4 floats; 4 elements for the
-// conversion), a scalar loop for the tail (and for vectors that are not 16-byte aligned), no atomics, no LDS, every
-// element computed by one lane in a fixed order (deterministic).
+// All kernels stream: grid-stride over 16-byte chunks per lane (2 doubles or 4 floats; 4 elements for the conversion),
+// single elements for the tail (and for vectors that are not 16-byte aligned), no atomics, no LDS, every element
+// computed by one lane in a fixed order (deterministic).  All but cheb_update_kernel are one body on the skeleton of
+// mfgpu_stream.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "mfgpu_device.h"
+#include "mfgpu_stream.h"
+
+using namespace mfgpu;
 
 namespace {
-
-constexpr unsigned kBlocks = 2048;  // 256 CUs x 8 resident blocks of 256 threads, grid-stride (as mfgpu_aux.hip)
-
-template <typename T>
-constexpr int lanes16() {
-  return 16 / (int)sizeof(T);
-}
-
-template <typename T>
-__device__ __forceinline__ void ld16(const T *p, T (&v)[lanes16<T>()]) {
-  if constexpr (sizeof(T) == 8) {
-    const double2 a = *reinterpret_cast<const double2 *>(p);
-    v[0] = a.x;
-    v[1] = a.y;
-  } else {
-    const float4 a = *reinterpret_cast<const float4 *>(p);
-    v[0] = a.x;
-    v[1] = a.y;
-    v[2] = a.z;
-    v[3] = a.w;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void st16(T *p, const T (&v)[lanes16<T>()]) {
-  if constexpr (sizeof(T) == 8) {
-    *reinterpret_cast<double2 *>(p) = make_double2(v[0], v[1]);
-  } else {
-    *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-// four elements per chunk: one 16-byte access on the float side, two on the double side
-template <typename T>
-__device__ __forceinline__ void ld4(const T *p, T (&v)[4]) {
-  if constexpr (sizeof(T) == 8) {
-    T a[2], b[2];
-    ld16<T>(p, a);
-    ld16<T>(p + 2, b);
-    v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1];
-  } else {
-    ld16<T>(p, v);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void st4(T *p, const T (&v)[4]) {
-  if constexpr (sizeof(T) == 8) {
-    const T a[2] = {v[0], v[1]}, b[2] = {v[2], v[3]};
-    st16<T>(p, a);
-    st16<T>(p + 2, b);
-  } else {
-    st16<T>(p, v);
-  }
-}
 
 // dst[i] = (D) src[i]; double -> float rounds to nearest even (overflow gives +-inf), float -> double is exact
 template <typename D, typename S, bool VEC>
 __global__ void __launch_bounds__(256) convert_kernel(D *__restrict__ dst, const S *__restrict__ src, size_t n) {
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / 4;
-    for (size_t c = tid; c < nc; c += stride) {
-      S a[4];
-      D b[4];
-      ld4<S>(src + 4 * c, a);
+  stream_chunks<4, VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    S a[W];
+    D b[W];
+    ldw<W>(src + o, a);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) b[k] = (D)a[k];
-      st4<D>(dst + 4 * c, b);
-    }
-    done = nc * 4;
-  }
-  for (size_t i = done + tid; i < n; i += stride) dst[i] = (D)src[i];
+    for (int k = 0; k < W; ++k) b[k] = (D)a[k];
+    stw<W>(dst + o, b);
+  });
 }
 
 // r = b - t (t == nullptr: r = b); upd = (f r) dinv; x = upd (ZERO) or x += upd.  The operations and their order are
@@ -103,33 +48,20 @@ template <typename T, bool VEC, bool HAS_T, bool ZERO>
 __global__ void __launch_bounds__(256)
 cheb_start_kernel(T *__restrict__ x, T *__restrict__ upd, T *__restrict__ r, const T *__restrict__ b,
                   const T *__restrict__ t, const T *__restrict__ dinv, T f, size_t n) {
-  constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / W;
-    for (size_t c = tid; c < nc; c += stride) {
-      const size_t o = c * W;
-      T xv[W], uv[W], rv[W], bv[W], tv[W], dv[W];
-      ld16<T>(b + o, bv);
-      if (HAS_T) ld16<T>(t + o, tv);
-      ld16<T>(dinv + o, dv);
-      if (!ZERO) ld16<T>(x + o, xv);
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T xv[W], uv[W], rv[W], bv[W], tv[W], dv[W];
+    ldw<W>(b + o, bv);
+    if (HAS_T) ldw<W>(t + o, tv);
+    ldw<W>(dinv + o, dv);
+    if (!ZERO) ldw<W>(x + o, xv);
 #pragma unroll
-      for (int k = 0; k < W; ++k) cheb_start_elem<T, HAS_T, ZERO>(xv[k], uv[k], rv[k], bv[k], HAS_T ? tv[k] : T(0), dv[k], f);
-      st16<T>(r + o, rv);
-      st16<T>(upd + o, uv);
-      st16<T>(x + o, xv);
-    }
-    done = nc * W;
-  }
-  for (size_t i = done + tid; i < n; i += stride) {
-    T xi = ZERO ? T(0) : x[i], ui, ri;
-    cheb_start_elem<T, HAS_T, ZERO>(xi, ui, ri, b[i], HAS_T ? t[i] : T(0), dinv[i], f);
-    r[i] = ri;
-    upd[i] = ui;
-    x[i] = xi;
-  }
+    for (int k = 0; k < W; ++k) cheb_start_elem<T, HAS_T, ZERO>(xv[k], uv[k], rv[k], bv[k], HAS_T ? tv[k] : T(0), dv[k], f);
+    stw<W>(r + o, rv);
+    stw<W>(upd + o, uv);
+    stw<W>(x + o, xv);
+  });
 }
 
 // r -= t; upd = f1 upd + (f2 r) dinv; x += upd  (r.add(-1, t), t.equ(f2, r), t.scale(dinv), upd.sadd(f1, 1, t),
@@ -141,6 +73,9 @@ __device__ __forceinline__ void cheb_update_elem(T &x, T &u, T &r, T t, T d, T f
   x = x + u;
 }
 
+// Not on stream_chunks: f1 upd + (f2 r) dinv has two products that the optimiser may contract into the sum, and it
+// fuses f1 upd here (in the float tail neither) but (f2 r) dinv in a body called from the skeleton, which changes the
+// last bit of upd and x (profiles/r12_notes.md).  Whoever changes the formula changes it in both loops.
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256)
 cheb_update_kernel(T *__restrict__ x, T *__restrict__ upd, T *__restrict__ r, const T *__restrict__ t,
@@ -180,89 +115,53 @@ cheb_update_kernel(T *__restrict__ x, T *__restrict__ upd, T *__restrict__ r, co
 template <typename T, bool VEC, bool HAS_E>
 __global__ void __launch_bounds__(256)
 residual_kernel(T *__restrict__ t, const T *__restrict__ b, const T *__restrict__ e, size_t n) {
-  constexpr int W = lanes16<T>();
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  size_t done = 0;
-  if (VEC) {
-    const size_t nc = n / W;
-    for (size_t c = tid; c < nc; c += stride) {
-      const size_t o = c * W;
-      T tv[W], bv[W], ev[W];
-      ld16<T>(t + o, tv);
-      ld16<T>(b + o, bv);
-      if (HAS_E) ld16<T>(e + o, ev);
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, n, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T tv[W], bv[W], ev[W];
+    ldw<W>(t + o, tv);
+    ldw<W>(b + o, bv);
+    if (HAS_E) ldw<W>(e + o, ev);
 #pragma unroll
-      for (int k = 0; k < W; ++k) tv[k] = HAS_E ? bv[k] - (tv[k] + ev[k]) : bv[k] - tv[k];
-      st16<T>(t + o, tv);
-    }
-    done = nc * W;
-  }
-  for (size_t i = done + tid; i < n; i += stride) t[i] = HAS_E ? b[i] - (t[i] + e[i]) : b[i] - t[i];
-}
-
-unsigned grid_for(size_t work) {
-  const size_t blocks = (work + 255) / 256;
-  return (unsigned)(blocks == 0 ? 1 : blocks > kBlocks ? kBlocks : blocks);
-}
-
-bool aligned16(const void *p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
-
-int einval(const char *msg) {
-  mfgpu::set_error(msg);
-  return MFGPU_EINVAL;
+    for (int k = 0; k < W; ++k) tv[k] = HAS_E ? bv[k] - (tv[k] + ev[k]) : bv[k] - tv[k];
+    stw<W>(t + o, tv);
+  });
 }
 
 template <typename D, typename S>
 void convert_launch(D *dst, const S *src, size_t n, hipStream_t st) {
-  if (aligned16(dst) && aligned16(src))
-    hipLaunchKernelGGL((convert_kernel<D, S, true>), dim3(grid_for(n / 4 + n % 4)), dim3(256), 0, st, dst, src, n);
-  else
-    hipLaunchKernelGGL((convert_kernel<D, S, false>), dim3(grid_for(n)), dim3(256), 0, st, dst, src, n);
+  const bool vec = aligned16(dst) && aligned16(src);
+  dispatch([&](auto VEC) {
+    hipLaunchKernelGGL((convert_kernel<D, S, VEC()>), dim3(stream_grid(n, 4, vec)), dim3(256), 0, st, dst, src, n);
+  }, vec);
 }
 
 template <typename T>
 void cheb_start_launch(T *x, T *upd, T *r, const T *b, const T *t, const T *dinv, T f, bool zero, size_t n,
                        hipStream_t st) {
   const bool vec = aligned16(x) && aligned16(upd) && aligned16(r) && aligned16(b) && aligned16(t) && aligned16(dinv);
-  const unsigned g = grid_for(vec ? n / lanes16<T>() + n % lanes16<T>() : n);
-#define CHEB_START(VEC, HT, Z)                                                                                    \
-  hipLaunchKernelGGL((cheb_start_kernel<T, VEC, HT, Z>), dim3(g), dim3(256), 0, st, x, upd, r, b, t, dinv, f, n)
-  const int sel = (vec ? 4 : 0) + (t ? 2 : 0) + (zero ? 1 : 0);
-  switch (sel) {
-    case 0: CHEB_START(false, false, false); break;
-    case 1: CHEB_START(false, false, true); break;
-    case 2: CHEB_START(false, true, false); break;
-    case 3: CHEB_START(false, true, true); break;
-    case 4: CHEB_START(true, false, false); break;
-    case 5: CHEB_START(true, false, true); break;
-    case 6: CHEB_START(true, true, false); break;
-    default: CHEB_START(true, true, true); break;
-  }
-#undef CHEB_START
+  dispatch([&](auto VEC, auto HAS_T, auto ZERO) {
+    hipLaunchKernelGGL((cheb_start_kernel<T, VEC(), HAS_T(), ZERO()>), dim3(stream_grid(n, lanes16<T>(), vec)),
+                       dim3(256), 0, st, x, upd, r, b, t, dinv, f, n);
+  }, vec, t != nullptr, zero);
 }
 
 template <typename T>
 void cheb_update_launch(T *x, T *upd, T *r, const T *t, const T *dinv, T f1, T f2, size_t n, hipStream_t st) {
-  if (aligned16(x) && aligned16(upd) && aligned16(r) && aligned16(t) && aligned16(dinv))
-    hipLaunchKernelGGL((cheb_update_kernel<T, true>), dim3(grid_for(n / lanes16<T>() + n % lanes16<T>())), dim3(256), 0,
-                       st, x, upd, r, t, dinv, f1, f2, n);
-  else
-    hipLaunchKernelGGL((cheb_update_kernel<T, false>), dim3(grid_for(n)), dim3(256), 0, st, x, upd, r, t, dinv, f1, f2,
-                       n);
+  const bool vec = aligned16(x) && aligned16(upd) && aligned16(r) && aligned16(t) && aligned16(dinv);
+  dispatch([&](auto VEC) {
+    hipLaunchKernelGGL((cheb_update_kernel<T, VEC()>), dim3(stream_grid(n, lanes16<T>(), vec)), dim3(256), 0, st, x,
+                       upd, r, t, dinv, f1, f2, n);
+  }, vec);
 }
 
 template <typename T>
 void residual_launch(T *t, const T *b, const T *e, size_t n, hipStream_t st) {
   const bool vec = aligned16(t) && aligned16(b) && aligned16(e);
-  const unsigned g = grid_for(vec ? n / lanes16<T>() + n % lanes16<T>() : n);
-#define RESIDUAL(VEC, HE) hipLaunchKernelGGL((residual_kernel<T, VEC, HE>), dim3(g), dim3(256), 0, st, t, b, e, n)
-  switch ((vec ? 2 : 0) + (e ? 1 : 0)) {
-    case 0: RESIDUAL(false, false); break;
-    case 1: RESIDUAL(false, true); break;
-    case 2: RESIDUAL(true, false); break;
-    default: RESIDUAL(true, true); break;
-  }
-#undef RESIDUAL
+  dispatch([&](auto VEC, auto HAS_E) {
+    hipLaunchKernelGGL((residual_kernel<T, VEC(), HAS_E()>), dim3(stream_grid(n, lanes16<T>(), vec)), dim3(256), 0, st,
+                       t, b, e, n);
+  }, vec, e != nullptr);
 }
 
 // the three written vectors must be distinct and must not be one of the read ones

@@ -21,16 +21,11 @@
 #include <vector>
 
 #include "mfgpu_device.h"
+#include "mfgpu_stream.h"
 
 using namespace mfgpu;
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
 
 // x = inv b.  inv: n rows of ld doubles, ld = n rounded up to even with a zero in the padding column, so every row
 // starts on 16 bytes and is read as double2.  One wave per row, the lanes stride the row by 128 columns; each lane
@@ -53,11 +48,6 @@ dense_solve_kernel(T *__restrict__ x, const double *__restrict__ inv, const T *_
   }
   acc = wave_sum(acc);
   if (lane == 0) x[row] = (T)acc;
-}
-
-int einval(const char *msg) {
-  set_error(msg);
-  return MFGPU_EINVAL;
 }
 
 struct VLevel {
