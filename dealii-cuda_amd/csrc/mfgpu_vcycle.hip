@@ -3,6 +3,8 @@
 // SURVEY's poisson_mg.cu:365-380), on the level operators, transfers and copy pairs of the C-ABI, which it borrows.
 //   mfgpu_vcycle_create   set-up: level vectors, inverse diagonals, eigenvalue estimates, the coarse solver's data
 //   mfgpu_vcycle_apply    z = M^-1 r: only enqueues kernels and device-to-device copies on the caller's stream
+//   mfgpu_vcycle_refresh  the set-up's values again after a coefficient update, enqueue-only (the pieces
+//                         are in mfgpu_refresh.hip); from the first one on the smoother reads its scalars from the device
 // New kernel here: dense_solve_kernel, x = A0^-1 b on the coarsest level from the inverse formed at creation, which
 // replaces a CG loop with two blocking reductions per iteration.  The other new launches of the schedule are
 // mfgpu_transfer_prolongate_add (mfgpu_transfer.hip) and mfgpu_vec_residual (mfgpu_mixed.hip).
@@ -13,14 +15,17 @@
 // `solution`, and without copy pairs the finest defect is a full copy of r.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <new>
 #include <vector>
 
 #include "mfgpu_device.h"
+#include "mfgpu_refresh.h"
 #include "mfgpu_stream.h"
 
 using namespace mfgpu;
@@ -50,6 +55,30 @@ dense_solve_kernel(T *__restrict__ x, const double *__restrict__ inv, const T *_
   if (lane == 0) x[row] = (T)acc;
 }
 
+// the unit vectors e_0 .. e_{n-1}, one after the other: what the level-0 operator is applied to (refresh)
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) identity_kernel(T *__restrict__ e, uint32_t n, size_t nn) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  stream_chunks<lanes16<T>(), VEC>(tid, stride, nn, [&](size_t o, auto width) {
+    constexpr int W = width;
+    T v[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = (o + k) / n == (o + k) % n ? T(1) : T(0);
+    stw<W>(e + o, v);
+  });
+}
+
+// y[j n + i] = (A0 e_j)[i] = A0[i][j] in the level type -> a[i][j] = a[j][i] = (double) A0[max(i, j)][min(i, j)]: the
+// conversion and the lower triangle that create_dense hands to mfgpu_spd_inverse.  Every entry written by one lane.
+template <typename T>
+__global__ void __launch_bounds__(256) lower_to_double_kernel(double *__restrict__ a, const T *__restrict__ y, uint32_t n) {
+  const size_t nn = (size_t)n * n, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < nn; e += stride) {
+    const uint32_t i = (uint32_t)(e / n), j = (uint32_t)(e % n), lo = i < j ? i : j, hi = i < j ? j : i;
+    a[e] = (double)y[(size_t)lo * n + hi];
+  }
+}
+
 struct VLevel {
   mfgpu_handle *op = nullptr;
   mfgpu_level *edges = nullptr;
@@ -57,7 +86,11 @@ struct VLevel {
   const mfgpu_index_pairs *to_mg = nullptr, *from_mg = nullptr;
   uint32_t n = 0;
   double lambda_max = 0.0;
+  uint32_t eig_steps = 0;    // the steps the estimate at creation took
   std::vector<double> cheb;  // mfgpu_cg_chebyshev_scalars
+  // refresh (inside mfgpu_vcycle::refresh): the state block of the device estimate and the scalar table
+  EigState *state = nullptr;
+  double *table = nullptr;
   DeviceArray<void> defect, solution, t, r, upd, dinv, edge;
 };
 
@@ -73,6 +106,15 @@ struct mfgpu_vcycle {
   DeviceArray<double> inverse;  // DENSE
   mfgpu_cg *cg = nullptr;       // CG
   size_t device_bytes = 0;
+  // refresh: what creation was told, and the one allocation of the first mfgpu_vcycle_refresh with the pieces in it
+  bool estimated = false;
+  uint32_t eig_iterations = 15;
+  double range = 15.0;
+  DeviceArray<void> refresh;       // coarse status | state blocks | scalar tables | partial sums | dense coarse pieces
+  uint32_t *coarse_status = nullptr;
+  double *partials = nullptr, *a_double = nullptr, *spd_workspace = nullptr;
+  void *identity = nullptr, *a_level = nullptr;
+  std::vector<char> mirror;        // host copy of coarse status + state blocks (mfgpu_vcycle_refresh_status)
   ~mfgpu_vcycle() { mfgpu_cg_destroy(cg); }
 };
 
@@ -155,6 +197,17 @@ int smooth(mfgpu_vcycle *v, VLevel &L, const void *b, bool zero_start, void *str
   void *x = L.solution.get(), *upd = L.upd.get(), *r = L.r.get(), *t = L.t.get();
   if (!zero_start)
     if (const int rc = mfgpu_vmult(L.op, t, x, stream)) return rc;
+  if (L.table) {  // after the first refresh: the same sweep on the device table
+    if (const int rc = mfgpu_vec_chebyshev_start_dev(x, upd, r, b, zero_start ? nullptr : t, L.dinv.get(), L.table,
+                                                     zero_start ? 1 : 0, L.n, nt, stream))
+      return rc;
+    for (uint32_t k = 1; k < v->degree; ++k) {
+      if (const int rc = mfgpu_vmult(L.op, t, upd, stream)) return rc;
+      if (const int rc = mfgpu_vec_chebyshev_update_dev(x, upd, r, t, L.dinv.get(), L.table + (2 * k - 1), L.n, nt, stream))
+        return rc;
+    }
+    return 0;
+  }
   if (const int rc = mfgpu_vec_chebyshev_start(x, upd, r, b, zero_start ? nullptr : t, L.dinv.get(), L.cheb[0],
                                                zero_start ? 1 : 0, L.n, nt, stream))
     return rc;
@@ -216,6 +269,9 @@ int validate(const mfgpu_vcycle_desc *d, mfgpu_vcycle *v) {
   v->pairs = d->levels[0].to_mg != nullptr;
   v->degree = d->smoother_degree ? d->smoother_degree : 5;
   const double range = d->smoothing_range != 0.0 ? d->smoothing_range : 15.0;
+  v->range = range;
+  v->estimated = d->lambda_max == nullptr;
+  v->eig_iterations = d->eig_iterations ? d->eig_iterations : 15u;
   for (uint32_t l = 0; l < nl; ++l) {
     const mfgpu_vcycle_level_desc &ld = d->levels[l];
     VLevel &L = v->levels[l];
@@ -257,6 +313,60 @@ int validate(const mfgpu_vcycle_desc *d, mfgpu_vcycle *v) {
                                                 : (double)std::numeric_limits<float>::epsilon();
   v->coarse_tolerance = d->coarse_tolerance != 0.0 ? d->coarse_tolerance : std::max(1e-10, 100.0 * eps);
   v->coarse_max_iterations = d->coarse_max_iterations ? d->coarse_max_iterations : n0;
+  return 0;
+}
+
+size_t round16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+// the one allocation of the first refresh (sizes: include/mfgpu.h) and what has to be in it before the first kernel
+int refresh_allocate(mfgpu_vcycle *v, hipStream_t st) {
+  const uint32_t nl = (uint32_t)v->levels.size(), n0 = v->levels[0].n;
+  const size_t es = esize(v->level_type), nn = (size_t)n0 * n0;
+  const size_t table = round16(sizeof(double) * (2 * v->degree - 1));
+  const bool dense = v->coarse == MFGPU_VCYCLE_COARSE_DENSE;
+  size_t bytes = 16 + (nl - 1) * (kEigStateBytes + table);
+  if (v->estimated) bytes += 2 * kStreamBlocks * sizeof(double);
+  if (dense) bytes += 2 * round16(nn * es) + round16(nn * sizeof(double)) + round16(2 * nn * sizeof(double));
+  DeviceArray<void> block;
+  if (const int rc = block.alloc(bytes, true)) return rc;
+  char *p = block.as<char>();
+  uint32_t *coarse_status = reinterpret_cast<uint32_t *>(p);
+  p += 16;
+  std::vector<EigState> states(nl - 1);
+  for (uint32_t l = 1; l < nl; ++l) {
+    states[l - 1] = EigState();
+    states[l - 1].result.lambda_max = v->levels[l].lambda_max;  // an estimate that fails keeps it
+  }
+  if (nl > 1) HIP_TRY(hipMemcpy(p, states.data(), (nl - 1) * kEigStateBytes, hipMemcpyHostToDevice));
+  EigState *state0 = reinterpret_cast<EigState *>(p);
+  p += (nl - 1) * kEigStateBytes;
+  char *table0 = p;
+  for (uint32_t l = 1; l < nl; ++l, p += table)  // the scalars in use: those of a given lambda_max stay for good
+    HIP_TRY(hipMemcpy(p, v->levels[l].cheb.data(), v->levels[l].cheb.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (v->estimated) {
+    v->partials = reinterpret_cast<double *>(p);
+    p += 2 * kStreamBlocks * sizeof(double);
+  }
+  if (dense) {
+    v->identity = p;
+    v->a_level = p + round16(nn * es);
+    v->a_double = reinterpret_cast<double *>(p + 2 * round16(nn * es));
+    v->spd_workspace = reinterpret_cast<double *>(p + 2 * round16(nn * es) + round16(nn * sizeof(double)));
+    const unsigned grid = stream_grid(nn, 16 / es, true);
+    if (v->level_type == MFGPU_F64)
+      hipLaunchKernelGGL((identity_kernel<double, true>), dim3(grid), dim3(256), 0, st, (double *)v->identity, n0, nn);
+    else
+      hipLaunchKernelGGL((identity_kernel<float, true>), dim3(grid), dim3(256), 0, st, (float *)v->identity, n0, nn);
+    if (const int rc = hip_check(hipGetLastError(), "mfgpu_vcycle_refresh: unit vectors")) return rc;
+  }
+  for (uint32_t l = 1; l < nl; ++l) {  // from here on smooth() runs the _dev forms
+    v->levels[l].state = state0 + (l - 1);
+    v->levels[l].table = reinterpret_cast<double *>(table0 + (l - 1) * table);
+  }
+  v->coarse_status = coarse_status;
+  v->mirror.assign(16 + (nl - 1) * kEigStateBytes, 0);
+  v->refresh = std::move(block);
+  v->device_bytes += bytes;
   return 0;
 }
 
@@ -317,7 +427,13 @@ int mfgpu_spd_inverse(uint32_t n, const double *a, double *inv) {
 }
 
 int mfgpu_estimate_lambda_max(mfgpu_handle *op, const void *inv_diag_dev, uint32_t min_iterations, double *lambda_max) {
-  if (!op || !inv_diag_dev || !lambda_max) return einval("mfgpu_estimate_lambda_max: null argument");
+  uint32_t steps = 0;
+  return mfgpu_estimate_lambda_max_steps(op, inv_diag_dev, min_iterations, lambda_max, &steps);
+}
+
+int mfgpu_estimate_lambda_max_steps(mfgpu_handle *op, const void *inv_diag_dev, uint32_t min_iterations, double *lambda_max,
+                                    uint32_t *steps) {
+  if (!op || !inv_diag_dev || !lambda_max || !steps) return einval("mfgpu_estimate_lambda_max: null argument");
   const uint32_t n = mfgpu_n_dofs(op);
   const int nt = handle_number_type(op);
   if (n == 0) return einval("mfgpu_estimate_lambda_max: an operator without dofs");
@@ -347,6 +463,7 @@ int mfgpu_estimate_lambda_max(mfgpu_handle *op, const void *inv_diag_dev, uint32
     lam = nw / nv;
     const double scale = nt == MFGPU_F64 ? 1.0 / nw : (double)(float)(1.0 / nw);
     if ((rc = mfgpu_vec_equ(v.get(), scale, w.get(), n, nt, nullptr))) return rc;
+    *steps = k + 1;
     if (k + 1 >= min_steps && std::fabs(lam - prev) <= 0.01 * lam) break;
     prev = lam;
   }
@@ -382,8 +499,7 @@ int mfgpu_vcycle_create(const mfgpu_vcycle_desc *d, mfgpu_vcycle **out) {
     void *dinv = l == 0 ? dinv0.get() : L.dinv.get();
     if ((rc = mfgpu_compute_inverse_diagonal(L.op, dinv, nullptr))) return rc;
     if (!d->lambda_max) {
-      if ((rc = mfgpu_estimate_lambda_max(L.op, dinv, d->eig_iterations ? d->eig_iterations : 15u, &L.lambda_max)))
-        return rc;
+      if ((rc = mfgpu_estimate_lambda_max_steps(L.op, dinv, v->eig_iterations, &L.lambda_max, &L.eig_steps))) return rc;
       if (l > 0) {
         L.cheb.resize(2 * v->degree - 1);
         if ((rc = mfgpu_cg_chebyshev_scalars(v->degree, L.lambda_max, range, L.cheb.data()))) return rc;
@@ -426,6 +542,59 @@ int mfgpu_vcycle_apply(mfgpu_vcycle *v, void *z_dev, const void *r_dev, void *st
   if ((rc = mfgpu_vec_fill(z_dev, v->n_active, at, 0.0, stream))) return rc;
   for (uint32_t l = 0; l <= top; ++l)
     if ((rc = mfgpu_vec_copy_pairs_convert(v->levels[l].from_mg, z_dev, at, v->levels[l].solution.get(), lt, stream))) return rc;
+  return MFGPU_OK;
+}
+
+int mfgpu_vcycle_refresh(mfgpu_vcycle *v, uint32_t eig_steps, void *stream) {
+  if (!v) return einval("mfgpu_vcycle_refresh: null argument");
+  VLevel &L0 = v->levels[0];
+  const bool dense = v->coarse == MFGPU_VCYCLE_COARSE_DENSE;
+  if (dense && L0.n > MFGPU_SPD_INVERSE_DEVICE_MAX) {
+    set_error("mfgpu_vcycle_refresh: MFGPU_VCYCLE_COARSE_DENSE above MFGPU_SPD_INVERSE_DEVICE_MAX level-0 dofs: re-create "
+              "the object or use MFGPU_VCYCLE_COARSE_CG");
+    return MFGPU_EUNSUPPORTED;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (!v->refresh.get() && (rc = refresh_allocate(v, st))) return rc;
+  const uint32_t nl = (uint32_t)v->levels.size();
+  for (uint32_t l = 1; l < nl; ++l)
+    if ((rc = mfgpu_compute_inverse_diagonal(v->levels[l].op, v->levels[l].dinv.get(), stream))) return rc;
+  if (v->estimated)
+    for (uint32_t l = 1; l < nl; ++l) {
+      VLevel &L = v->levels[l];  // t and r are scratch between applies
+      if ((rc = eig_enqueue(L.op, L.dinv.get(), v->eig_iterations, eig_steps ? eig_steps : L.eig_steps, L.state, v->partials,
+                            L.t.get(), L.r.get(), stream)))
+        return rc;
+      if ((rc = mfgpu_cg_chebyshev_scalars_dev(v->degree, &L.state->result.lambda_max, v->range, L.table, stream))) return rc;
+    }
+  if (!dense) return MFGPU_OK;
+  const uint32_t n0 = L0.n;
+  if ((rc = mfgpu_vmult_multi(L0.op, v->a_level, v->identity, n0, n0, MFGPU_MULTI_LOOP, stream))) return rc;
+  const unsigned grid = stream_grid((size_t)n0 * n0, 1, false);
+  if (v->level_type == MFGPU_F64)
+    hipLaunchKernelGGL(lower_to_double_kernel<double>, dim3(grid), dim3(256), 0, st, v->a_double, (const double *)v->a_level, n0);
+  else
+    hipLaunchKernelGGL(lower_to_double_kernel<float>, dim3(grid), dim3(256), 0, st, v->a_double, (const float *)v->a_level, n0);
+  if ((rc = hip_check(hipGetLastError(), "mfgpu_vcycle_refresh: level-0 matrix"))) return rc;
+  return mfgpu_spd_inverse_enqueue(n0, v->a_double, n0, v->inverse.get(), v->ld, v->spd_workspace, v->coarse_status, stream);
+}
+
+int mfgpu_vcycle_refresh_status(mfgpu_vcycle *v, void *stream, mfgpu_vcycle_refresh_info *info) {
+  if (!v || !info) return einval("mfgpu_vcycle_refresh_status: null argument");
+  if (!v->refresh.get()) return einval("mfgpu_vcycle_refresh_status: call mfgpu_vcycle_refresh first");
+  HIP_TRY(hipMemcpyAsync(v->mirror.data(), v->refresh.get(), v->mirror.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *info = mfgpu_vcycle_refresh_info();
+  std::memcpy(&info->coarse_status, v->mirror.data(), sizeof(uint32_t));
+  if (!v->estimated) return MFGPU_OK;
+  for (size_t l = 1; l < v->levels.size(); ++l) {
+    EigState s;
+    std::memcpy(&s, v->mirror.data() + 16 + (l - 1) * kEigStateBytes, sizeof s);
+    info->eig_status_max = std::max(info->eig_status_max, s.result.status);
+    info->eig_steps_max = std::max(info->eig_steps_max, s.result.steps);
+    if (s.result.status == 1u || s.result.status == 2u) v->levels[l].lambda_max = s.result.lambda_max;
+  }
   return MFGPU_OK;
 }
 

@@ -512,7 +512,7 @@ private:
 // smoothing range and lambda_max, so both classes run the same polynomial (always with fused updates); the coarse solver
 // argument is not used: level 0 is solved on the device (the dense inverse up to 2048 dofs, an enqueued CG above).  vmult
 // only enqueues work.  ActiveNumber: the type of vmult's vectors (a float V-cycle under a double CG: <..., float, ...,
-// double>).  After new coefficients on the levels a new object is needed.
+// double>).  After new coefficients on the levels, refresh() brings the object up to date without a new one.
 template <int dim, typename LevelMatrixType, typename Number, typename CoarseSolver, typename ActiveNumber = Number>
 class MultigridPreconditionerDevice {
 public:
@@ -546,6 +546,18 @@ public:
   MultigridPreconditionerDevice(const MultigridPreconditionerDevice &) = delete;
   void vmult(GpuVector<ActiveNumber> &dst, const GpuVector<ActiveNumber> &src) const {
     check(mfgpu_vcycle_apply(vcycle, dst.getData(), src.getDataRO(), nullptr), "MultigridPreconditionerDevice::vmult");
+  }
+  // After mfgpu_level_update_coefficients on the level matrices: the inverse diagonals and the coarse inverse again from
+  // what the levels hold now, enqueued on the null stream like vmult (mfgpu_vcycle_refresh).  The smoothers' lambda_max
+  // was handed over at construction, so the bounds and the polynomial stay; a caller whose coefficient moves the
+  // spectrum of D^-1 A builds the object from re-initialised smoothers instead.  The first call allocates.  Throws where
+  // the library cannot refresh (a dense level 0 above MFGPU_SPD_INVERSE_DEVICE_MAX dofs).
+  void refresh() { check(mfgpu_vcycle_refresh(vcycle, 0, nullptr), "MultigridPreconditionerDevice::refresh"); }
+  // blocking: false if the level-0 matrix was no longer positive definite (the old coarse inverse is then kept)
+  bool refresh_succeeded() {
+    mfgpu_vcycle_refresh_info info{};
+    check(mfgpu_vcycle_refresh_status(vcycle, nullptr, &info), "MultigridPreconditionerDevice::refresh_succeeded");
+    return info.coarse_status == 0;
   }
   std::size_t memory_consumption() const { return mfgpu_vcycle_memory_consumption(vcycle); }
   mfgpu_vcycle *get_vcycle() const { return vcycle; }

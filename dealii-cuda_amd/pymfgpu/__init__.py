@@ -58,6 +58,20 @@ class CGInfo(C.Structure):
 
 VCYCLE_COARSE_AUTO, VCYCLE_COARSE_DENSE, VCYCLE_COARSE_CG = 0, 1, 2  # VCycleDesc.coarse (MFGPU_VCYCLE_COARSE_*)
 VCYCLE_DENSE_MAX = 2048
+SPD_INVERSE_DEVICE_MAX = 512  # MFGPU_SPD_INVERSE_DEVICE_MAX
+EIG_STATE_BYTES, EIG_PARTIAL_BYTES = 64, 2 * 2048 * 8  # the fixed blocks of mfgpu_eig_workspace_bytes
+
+
+class EigResult(C.Structure):
+    """mirror of struct mfgpu_eig_result, the head of the workspace of estimate_lambda_max_enqueue; status: 0 running,
+    1 stopped by the 1 % rule, 2 n_steps used up, 3 a norm was not a positive finite number"""
+    _fields_ = [("lambda_max", C.c_double), ("estimate", C.c_double), ("steps", C.c_uint32), ("status", C.c_uint32)]
+
+
+class VCycleRefreshInfo(C.Structure):
+    """mirror of struct mfgpu_vcycle_refresh_info"""
+    _fields_ = [("coarse_status", C.c_uint32), ("eig_status_max", C.c_uint32), ("eig_steps_max", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class VCycleLevelDesc(C.Structure):
@@ -111,6 +125,9 @@ SYMBOLS = [
     "mfgpu_cg_begin_relative", "mfgpu_cg_set_vcycle", "mfgpu_transfer_prolongate_add", "mfgpu_vec_residual",
     "mfgpu_vcycle_create", "mfgpu_vcycle_apply", "mfgpu_vcycle_lambda_max", "mfgpu_vcycle_memory_consumption",
     "mfgpu_vcycle_destroy", "mfgpu_estimate_lambda_max", "mfgpu_spd_inverse",
+    "mfgpu_vec_chebyshev_start_dev", "mfgpu_vec_chebyshev_update_dev", "mfgpu_cg_chebyshev_scalars_dev",
+    "mfgpu_eig_workspace_bytes", "mfgpu_estimate_lambda_max_enqueue", "mfgpu_spd_inverse_workspace_bytes",
+    "mfgpu_spd_inverse_enqueue", "mfgpu_vcycle_refresh", "mfgpu_vcycle_refresh_status", "mfgpu_estimate_lambda_max_steps",
 ]
 
 _lib = None
@@ -266,6 +283,18 @@ def lib():
         L.mfgpu_vcycle_destroy.restype = None
         L.mfgpu_estimate_lambda_max.argtypes = [vp, vp, u32, C.POINTER(d)]
         L.mfgpu_spd_inverse.argtypes = [u32, vp, vp]
+        L.mfgpu_vec_chebyshev_start_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, z, i, vp]
+        L.mfgpu_vec_chebyshev_update_dev.argtypes = [vp, vp, vp, vp, vp, vp, z, i, vp]
+        L.mfgpu_cg_chebyshev_scalars_dev.argtypes = [u32, vp, d, vp, vp]
+        L.mfgpu_eig_workspace_bytes.argtypes = [u32, i]
+        L.mfgpu_eig_workspace_bytes.restype = C.c_size_t
+        L.mfgpu_estimate_lambda_max_enqueue.argtypes = [vp, vp, u32, u32, vp, vp]
+        L.mfgpu_spd_inverse_workspace_bytes.argtypes = [u32]
+        L.mfgpu_spd_inverse_workspace_bytes.restype = C.c_size_t
+        L.mfgpu_spd_inverse_enqueue.argtypes = [u32, vp, u32, vp, u32, vp, vp, vp]
+        L.mfgpu_vcycle_refresh.argtypes = [vp, u32, vp]
+        L.mfgpu_estimate_lambda_max_steps.argtypes = [vp, vp, u32, C.POINTER(d), C.POINTER(u32)]
+        L.mfgpu_vcycle_refresh_status.argtypes = [vp, vp, C.POINTER(VCycleRefreshInfo)]
         _lib = L
     return _lib
 
@@ -1020,18 +1049,74 @@ def chebyshev_update(x, upd, r, t, dinv, f1, f2, n, number_type, stream=None, ch
     return _check(rc) if check else rc
 
 
+def chebyshev_start_dev(x, upd, r, b, t, dinv, f_dev, zero_start, n, number_type, stream=None, check=True):
+    """chebyshev_start with f read from device memory: f_dev is a device address (or vector) of one double"""
+    rc = lib().mfgpu_vec_chebyshev_start_dev(_ptr(x), _ptr(upd), _ptr(r), _ptr(b), None if t is None else _ptr(t),
+                                             _ptr(dinv), _optr(f_dev), 1 if zero_start else 0, n, number_type, stream)
+    return _check(rc) if check else rc
+
+
+def chebyshev_update_dev(x, upd, r, t, dinv, f12_dev, n, number_type, stream=None, check=True):
+    """chebyshev_update with (f1, f2) read from device memory: f12_dev is a device address (or vector) of two doubles"""
+    rc = lib().mfgpu_vec_chebyshev_update_dev(_ptr(x), _ptr(upd), _ptr(r), _ptr(t), _ptr(dinv), _optr(f12_dev), n,
+                                              number_type, stream)
+    return _check(rc) if check else rc
+
+
+def chebyshev_scalars_dev(degree, lambda_max_dev, smoothing_range, f_dev, stream=None, check=True):
+    """cg_chebyshev_scalars on a lambda_max in device memory into f_dev [2 * degree - 1] doubles; one small launch"""
+    rc = lib().mfgpu_cg_chebyshev_scalars_dev(int(degree), _optr(lambda_max_dev), float(smoothing_range), _optr(f_dev),
+                                              stream)
+    return _check(rc) if check else rc
+
+
+def eig_workspace_bytes(n_dofs, number_type):
+    """bytes of the workspace of estimate_lambda_max_enqueue (mfgpu_eig_workspace_bytes); host only"""
+    return int(lib().mfgpu_eig_workspace_bytes(int(n_dofs), int(number_type)))
+
+
+def estimate_lambda_max_enqueue(op, inv_diag, min_iterations, n_steps, workspace, stream=None, check=True):
+    """the power iteration of estimate_lambda_max, enqueued: n_steps steps with the host's stopping rule as a freeze rule;
+    the workspace (eig_workspace_bytes, a device vector or address) starts with an EigResult (eig_result reads it)"""
+    rc = lib().mfgpu_estimate_lambda_max_enqueue(None if op is None else _op_handle(op), _optr(inv_diag),
+                                                 int(min_iterations), int(n_steps), _optr(workspace), stream)
+    return _check(rc) if check else rc
+
+
+def eig_result(workspace):
+    """the EigResult at the head of a workspace of estimate_lambda_max_enqueue (blocking copy)"""
+    r = EigResult()
+    _check(lib().mfgpu_vec_to_host(C.addressof(r), _ptr(workspace), C.sizeof(r) // 8, F64))  # 24 bytes
+    return r
+
+
+def spd_inverse_workspace_bytes(n):
+    """bytes of the workspace of spd_inverse_enqueue (mfgpu_spd_inverse_workspace_bytes); host only"""
+    return int(lib().mfgpu_spd_inverse_workspace_bytes(int(n)))
+
+
+def spd_inverse_enqueue(n, a, lda, inv, ld, workspace, status, stream=None, check=True):
+    """spd_inverse on the device: a [n rows of lda doubles, lower triangle read] -> inv [n rows of ld doubles, columns
+    n .. ld - 1 zero]; status: device address of a uint32 that gets 0, or 1 for a matrix that is not positive definite
+    (inv then keeps its contents).  All arguments are device vectors or addresses; only enqueues"""
+    rc = lib().mfgpu_spd_inverse_enqueue(int(n), _optr(a), int(lda), _optr(inv), int(ld), _optr(workspace), _optr(status),
+                                         stream)
+    return _check(rc) if check else rc
+
+
 def vec_residual(t, b, e, n, number_type, stream=None, check=True):
     """t = b - t (e None) or t = b - (t + e)"""
     rc = lib().mfgpu_vec_residual(_ptr(t), _ptr(b), _optr(e), n, number_type, stream)
     return _check(rc) if check else rc
 
 
-def estimate_lambda_max(op, inv_diag, min_iterations=15):
+def estimate_lambda_max(op, inv_diag, min_iterations=15, with_steps=False):
     """1.2 x the power-iteration estimate of the largest eigenvalue of D^-1 A (mfgpu_estimate_lambda_max); blocks.
-    op: an Operator, a Level (its level matrix) or anything with the handle in _h"""
-    r = C.c_double()
-    _check(lib().mfgpu_estimate_lambda_max(_op_handle(op), _ptr(inv_diag), int(min_iterations), C.byref(r)))
-    return r.value
+    op: an Operator, a Level (its level matrix) or anything with the handle in _h.  with_steps: (estimate, steps taken)"""
+    r, steps = C.c_double(), C.c_uint32()
+    _check(lib().mfgpu_estimate_lambda_max_steps(_op_handle(op), _ptr(inv_diag), int(min_iterations), C.byref(r),
+                                                 C.byref(steps)))
+    return (r.value, int(steps.value)) if with_steps else r.value
 
 
 def spd_inverse(a, check=True):
@@ -1095,10 +1180,17 @@ class VCycle:
         self._h = h
 
     @staticmethod
-    def hierarchy_levels(mesh: "Mesh"):
+    def _flagged(desc, flags):
+        """a copy of the description with `flags` added (UPDATABLE_COEFFICIENTS for levels that refresh() follows)"""
+        d = Desc.from_buffer_copy(desc)
+        d.flags |= int(flags)
+        return d
+
+    @staticmethod
+    def hierarchy_levels(mesh: "Mesh", flags=0):
         """(levels, keep) of the constructor for the hierarchy of an adaptive stand-in mesh (Mesh.adaptive_mg): level
         operators with refinement edges, transfers over the refined parents and the copy pairs of mfgpu_mg_*, all in the
-        mesh's number type"""
+        mesh's number type; `flags` are added to every level's description"""
         dim, p, nt = int(mesh.desc.dim), int(mesh.desc.degree), int(mesh.desc.number_type)
         H = MgHierarchy(mesh)
         nd, nfd = (p + 1) ** dim, (2 * p + 1) ** dim
@@ -1112,26 +1204,26 @@ class VCycle:
                 cd, fd = H.transfer_arrays(l, nd, nfd)
                 con = _view(meshes[l - 1].desc.constrained_dofs, meshes[l - 1].desc.n_constrained, np.uint32)
                 tr = Transfer.from_arrays(dim, p, cd, fd, meshes[l - 1].n_dofs, M.n_dofs, con, nt)
-            levels.append({"op": Level(M.desc, E, (M, H)), "has_edges": len(E) > 0, "n_dofs": M.n_dofs, "transfer": tr,
+            levels.append({"op": Level(VCycle._flagged(M.desc, flags), E, (M, H)), "has_edges": len(E) > 0, "n_dofs": M.n_dofs, "transfer": tr,
                            "to_mg": IndexPairs(b, a), "from_mg": IndexPairs(a, b)})
         return levels, (mesh, H, meshes)
 
     @classmethod
-    def from_hierarchy(cls, mesh: "Mesh", level_type=F64, active_type=F64, **options):
+    def from_hierarchy(cls, mesh: "Mesh", level_type=F64, active_type=F64, flags=0, **options):
         """the local-smoothing V-cycle of an adaptive stand-in mesh (Mesh.adaptive_mg) built in level_type; the active
         vectors are of active_type with mesh.n_dofs entries (a float V-cycle under a double CG)"""
         if int(mesh.desc.number_type) != level_type:
             raise MfgpuError("VCycle.from_hierarchy: build the mesh in the level number type (Mesh.adaptive_mg(..., "
                              "number_type=level_type)); the active vectors may be of another type")
-        levels, keep = cls.hierarchy_levels(mesh)
+        levels, keep = cls.hierarchy_levels(mesh, flags)
         return cls(levels, active_type, mesh.n_dofs, keep=keep, **options)
 
     @classmethod
-    def from_meshes(cls, meshes, active_type=None, **options):
+    def from_meshes(cls, meshes, active_type=None, flags=0, **options):
         """globally refined cubes or balls, coarse to fine (uniform meshes of n, 2n, 4n ... cells per direction or balls
         of successive n_ref): no edges, no pairs, the active vector is the finest level's"""
         nt = int(meshes[0].desc.number_type)
-        levels = [{"op": Operator(M.desc, M), "n_dofs": M.n_dofs,
+        levels = [{"op": Operator(cls._flagged(M.desc, flags), M), "n_dofs": M.n_dofs,
                    "transfer": Transfer.from_meshes(meshes[l - 1], M) if l else None} for l, M in enumerate(meshes)]
         return cls(levels, nt if active_type is None else active_type, meshes[-1].n_dofs, keep=list(meshes), **options)
 
@@ -1139,6 +1231,19 @@ class VCycle:
         """z = M^-1 r on active vectors (enqueued on `stream`)"""
         rc = lib().mfgpu_vcycle_apply(self._h, _optr(z), _optr(r), stream)
         return _check(rc) if check else rc
+
+    def refresh(self, eig_steps=0, stream=None, check=True):
+        """mfgpu_vcycle_refresh: recompute the inverse diagonals, the eigenvalue estimates with the smoothers' scalars
+        (where lambda_max was estimated at creation; eig_steps steps per level, 0 = as many as at creation) and the dense
+        coarse inverse from what the level operators hold now.  Only enqueues on `stream`; the first call allocates"""
+        rc = lib().mfgpu_vcycle_refresh(self._h, int(eig_steps), stream)
+        return _check(rc) if check else rc
+
+    def refresh_status(self, stream=None):
+        """mfgpu_vcycle_refresh_status (blocking): the VCycleRefreshInfo of the last refresh; lambda_max() follows"""
+        info = VCycleRefreshInfo()
+        _check(lib().mfgpu_vcycle_refresh_status(self._h, stream, C.byref(info)))
+        return info
 
     def lambda_max(self):
         out = (C.c_double * self.n_levels)()

@@ -506,8 +506,8 @@ int mfgpu_cg_chebyshev_scalars(uint32_t degree, double lambda_max, double smooth
  * lambda_max, made only when lambda_max == NULL, goes through an inverse diagonal that is freed again inside create.)
  * mfgpu_vcycle_apply allocates nothing, synchronises nothing and reads nothing back: kernels and device-to-device copies
  * on `stream` only, no memset nodes; it can be captured in a graph.  One object is used on one stream at a time.
- * After mfgpu_level_update_coefficients the inverse diagonals, eigenvalue estimates and the dense inverse are stale: create
- * a new mfgpu_vcycle.                                                                                                   */
+ * After mfgpu_level_update_coefficients the inverse diagonals, eigenvalue estimates and the dense inverse are stale:
+ * mfgpu_vcycle_refresh (below) recomputes them in place on the caller's stream, without stopping the host.             */
 #define MFGPU_VCYCLE_COARSE_AUTO 0  /* DENSE when n_dofs(0) <= MFGPU_VCYCLE_DENSE_MAX, else CG */
 #define MFGPU_VCYCLE_COARSE_DENSE 1 /* x = A0^-1 b with the inverse formed at creation (host Cholesky in double): one launch */
 #define MFGPU_VCYCLE_COARSE_CG 2    /* unpreconditioned device CG, coarse_max_iterations iterations enqueued per apply.
@@ -559,9 +559,99 @@ int mfgpu_cg_set_vcycle(mfgpu_cg *s, mfgpu_vcycle *v);
  * *lambda_max = 1.2 x the estimate.  inv_diag_dev: the operator's number type.  A blocking set-up call (two norms per
  * step are read back; two work vectors are allocated and freed).                                                    */
 int mfgpu_estimate_lambda_max(mfgpu_handle *op, const void *inv_diag_dev, uint32_t min_iterations, double *lambda_max);
+/* the same call, which also reports how many steps the iteration took (what mfgpu_vcycle_refresh enqueues by default) */
+int mfgpu_estimate_lambda_max_steps(mfgpu_handle *op, const void *inv_diag_dev, uint32_t min_iterations, double *lambda_max,
+                                    uint32_t *steps);
 /* host only, no device: inv = a^-1 for a symmetric positive definite a [n * n] (row-major; only the lower triangle is
  * read) by a Cholesky factorisation in double.  MFGPU_EINVAL on a non-positive (or non-finite) pivot; inv may not alias a. */
 int mfgpu_spd_inverse(uint32_t n, const double *a, double *inv);
+
+/* ---- refreshing a V-cycle after a coefficient update.  The three set-up pieces above as calls that
+ * only enqueue on `stream` -- no allocation, no synchronisation, nothing read back, capturable in a graph -- and
+ * mfgpu_vcycle_refresh, which runs them on an existing object.                                                         */
+/* mfgpu_vec_chebyshev_start / _update with the scalars in device memory: f_dev[0] = f, f12_dev[0..1] = f1, f2, doubles,
+ * read by the kernel when the stream gets there and rounded to number_type as the by-value forms round theirs, so the
+ * two forms give equal bits on equal scalars.  Aliasing rules and errors as the by-value forms; MFGPU_EINVAL also for a
+ * null scalar pointer or one that is not 8-byte aligned.                                                             */
+int mfgpu_vec_chebyshev_start_dev(void *x, void *upd, void *r, const void *b, const void *t, const void *dinv,
+                                  const double *f_dev, int zero_start, size_t n, int number_type, void *stream);
+int mfgpu_vec_chebyshev_update_dev(void *x, void *upd, void *r, const void *t, const void *dinv,
+                                   const double *f12_dev /* f1, f2 */, size_t n, int number_type, void *stream);
+/* mfgpu_cg_chebyshev_scalars on a lambda_max in device memory: one small launch, the same recurrence in double, f_dev
+ * [2 * degree - 1].  MFGPU_EINVAL: null pointers, degree 0, smoothing_range <= 1 (lambda_max cannot be checked: a value
+ * <= 0 gives the non-finite scalars the formulas give).                                                              */
+int mfgpu_cg_chebyshev_scalars_dev(uint32_t degree, const double *lambda_max_dev, double smoothing_range,
+                                   double *f_dev /* [2*degree-1] */, void *stream);
+/* The power iteration of mfgpu_estimate_lambda_max without the host: the start vector is written by a kernel, then
+ * n_steps steps are enqueued, each one mfgpu_vmult and two launches (w = inv_diag .* w with the partial sums of w.w and
+ * v.v; estimate = |w| / |v| and v = w / |w|).  The host's stopping rule is a freeze rule: after at least
+ * max(5, min_iterations) steps, once the estimate moved by at most 1 % in the last step, status = 1 and the solver
+ * kernels of the later steps return without writing (the operator applies still run).  status 2: n_steps used up,
+ * lambda_max = 1.2 x the last estimate; status 3: a norm was not a positive finite number, lambda_max is not written; 0
+ * while running.  lambda_max = 1.2 x estimate for status 1 and 2; steps = the steps that counted.
+ * The workspace (16-byte aligned, MFGPU_EINVAL otherwise) is, in this order: the 64-byte state block, which starts with
+ * an mfgpu_eig_result the caller copies out when it wants it; 2 * 2048 doubles of partial sums; the two work vectors,
+ * each n_dofs numbers of number_type rounded up to a multiple of 16 bytes:
+ *   mfgpu_eig_workspace_bytes = 64 + 32768 + 2 * round16(n_dofs * sizeof(number))       (0 for an unknown number type)
+ * MFGPU_EINVAL, nothing enqueued: null pointers, n_steps == 0, an operator without dofs.                              */
+typedef struct mfgpu_eig_result {
+  double lambda_max, estimate;
+  uint32_t steps, status;
+} mfgpu_eig_result;
+size_t mfgpu_eig_workspace_bytes(uint32_t n_dofs, int number_type); /* host only */
+int mfgpu_estimate_lambda_max_enqueue(mfgpu_handle *op, const void *inv_diag_dev, uint32_t min_iterations, uint32_t n_steps,
+                                      void *workspace_dev, void *stream);
+/* mfgpu_spd_inverse on the device, in double: Cholesky of the lower triangle of a_dev (n rows of lda doubles; only the
+ * lower triangle is read), L^-1, inv = L^-T L^-1 into inv_dev, n rows of ld doubles; the columns n .. ld - 1 of every row
+ * get zeros (with ld = n rounded up to even that is the layout of the V-cycle's dense coarse solve).  Three launches:
+ * one workgroup factorises (the matrix stays in global memory, i.e. in L2), one wave per column inverts L, one workgroup
+ * per row forms the product; no atomics, two calls give equal bits.  A pivot that is not a positive finite number sets
+ * *status_dev = 1 and the two later kernels return without writing, so inv_dev keeps its contents; otherwise *status_dev
+ * = 0.  Workspace: mfgpu_spd_inverse_workspace_bytes = 2 * n * n * 8 (L and L^-1), 8-byte aligned.
+ * MFGPU_EINVAL, nothing enqueued: n == 0 or n > MFGPU_SPD_INVERSE_DEVICE_MAX (the factorisation keeps a column in
+ * LDS), null pointers, lda or ld < n, misaligned or overlapping a, inv and workspace.                                */
+#define MFGPU_SPD_INVERSE_DEVICE_MAX 512
+size_t mfgpu_spd_inverse_workspace_bytes(uint32_t n); /* host only */
+int mfgpu_spd_inverse_enqueue(uint32_t n, const double *a_dev, uint32_t lda, double *inv_dev, uint32_t ld,
+                              void *workspace_dev, uint32_t *status_dev, void *stream);
+/* Recompute, from whatever the level operators hold now, (a) the inverse diagonal of every level above 0, (b) where the
+ * object estimated its own lambda_max at creation (desc.lambda_max == NULL) the estimate of every level above 0 by
+ * mfgpu_estimate_lambda_max_enqueue with the object's eig_iterations, and from it the smoother's Chebyshev scalars by
+ * mfgpu_cg_chebyshev_scalars_dev -- eig_steps steps are enqueued per level, 0 = as many as that level's estimate took at
+ * creation; with a lambda_max given at creation the values and the scalars stay -- and (c) in COARSE_DENSE mode the
+ * inverse: the level-0 operator applied to the unit vectors, converted to double and symmetrised from the lower triangle
+ * as at creation, then mfgpu_spd_inverse_enqueue into the object's inverse.  COARSE_CG has nothing to refresh.  Level
+ * 0's lambda_max, which no coarse solver reads, keeps its creation value.  Legal on levels created without
+ * MFGPU_UPDATABLE_COEFFICIENTS (it recomputes the same values).
+ * Everything is enqueued on `stream`; nothing is read back.  The FIRST refresh of an object allocates, once and
+ * together, what refreshes need beyond the level vectors (t, r and upd are scratch between applies and serve as work
+ * vectors) -- the only allocation and the only possible host synchronisation of the function:
+ *   16                                           the coarse status word
+ *   + (n_levels - 1) * (64 + round16(8 * (2 * smoother_degree - 1)))    per level above 0: state block, scalar table
+ *   + 32768                                      partial sums, only with desc.lambda_max == NULL
+ *   + 2 * round16(n0 * n0 * sizeof(level number)) + round16(8 * n0 * n0) + round16(16 * n0 * n0)
+ *                                                only COARSE_DENSE: identity block, A0 in the level type, A0 in
+ *                                                double, the workspace of mfgpu_spd_inverse_enqueue; n0 = n_dofs(0)
+ * (round16 = up to a multiple of 16).  mfgpu_vcycle_memory_consumption grows by exactly that from then on and
+ * mfgpu_vcycle_destroy frees it.  Until the first refresh mfgpu_vcycle_apply and mfgpu_vcycle_memory_consumption are
+ * unchanged; from the first refresh on the smoother reads its scalars from the device table (the _dev forms above), so
+ * a graph captured AFTER the first refresh -- of apply alone or of "update coefficients, refresh, apply" -- stays valid
+ * across later refreshes.  Capture after the first refresh, and with the same eig_steps if the refresh is inside.
+ * MFGPU_EINVAL: null object.  MFGPU_EUNSUPPORTED, nothing enqueued or allocated: COARSE_DENSE with n_dofs(0) >
+ * MFGPU_SPD_INVERSE_DEVICE_MAX (re-create the object, or use the CG coarse mode).
+ * A level-0 matrix that is no longer positive definite cannot be an error code of a call that only enqueues: the old
+ * inverse stays and mfgpu_vcycle_refresh_status reports coarse_status = 1.                                           */
+int mfgpu_vcycle_refresh(mfgpu_vcycle *v, uint32_t eig_steps, void *stream);
+typedef struct mfgpu_vcycle_refresh_info {
+  uint32_t coarse_status;  /* 0, or 1: the level-0 matrix was not positive definite, the inverse is the old one */
+  uint32_t eig_status_max; /* the largest status of the estimates (mfgpu_eig_result; 0 with a given lambda_max) */
+  uint32_t eig_steps_max;  /* the largest step count of the estimates */
+  uint32_t reserved;
+} mfgpu_vcycle_refresh_info;
+/* blocking: copies the result blocks of the last refresh back (one copy and a synchronisation of `stream`) and updates
+ * what mfgpu_vcycle_lambda_max reports; before this call it reports the previous values.  MFGPU_EINVAL: null pointers,
+ * or no refresh yet.                                                                                                 */
+int mfgpu_vcycle_refresh_status(mfgpu_vcycle *v, void *stream, mfgpu_vcycle_refresh_info *info);
 
 /* ---- cell integrals of a Poisson solve (poisson.cu:152-229, 277-292) ------------------------------------------
  * A separate object created from the same description as the operator; it keeps its own device copy of the geometry
