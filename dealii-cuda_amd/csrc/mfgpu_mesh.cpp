@@ -181,6 +181,9 @@ int build_uniform(Mesh &M, const uint32_t *nper, double lo, double hi, uint32_t 
   ncl[dim - 1] = se - sb;
   M.mg_kind = (sb == 0 && se == nc[dim - 1]) ? 0 : -1;
   for (int d = 0; d < 3; ++d) M.nper[d] = nc[d];
+  M.cells_kind = 0;
+  M.slab[0] = sb;
+  M.slab[1] = se;
   uint64_t ndofs64 = 1, ncells64 = 1;
   for (int d = 0; d < dim; ++d) {
     ng[d] = ncl[d] * p + 1;

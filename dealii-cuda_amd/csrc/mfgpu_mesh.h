@@ -22,6 +22,11 @@ struct Mesh {
   // 1 refinement tree in depth-first order with lexicographic children (ball), -1 anything else
   int mg_kind = -1;
   uint32_t nper[3] = {1, 1, 1};
+  // which cells the mesh has, whatever the degree and the dof numbering (the p-transfer's "same cells" test; it survives
+  // a renumbering, unlike mg_kind): 0 cube of nper cells per direction, cells [slab[0], slab[1]) of the last one;
+  // 1 ball refined n_ref times; -1 anything else (adaptive, from leaves)
+  int cells_kind = -1, n_ref = 0;
+  uint32_t slab[2] = {0, 0};
   std::vector<double> nodes, xq, wq;  // 1D support points / Gauss points / weights on [0,1]
   std::vector<double> shape_values, shape_gradients, weights;
   std::vector<uint32_t> loc2glob, constraint_mask, constrained;

@@ -271,6 +271,8 @@ int build_ball(Mesh &M, int n_ref) {
   M.n_cells = (uint32_t)nc;
   M.general = true;
   M.mg_kind = 1;  // refinement-tree order, children lexicographic
+  M.cells_kind = 1;
+  M.n_ref = n_ref;
   M.init_tables();
   M.loc2glob.assign(nc * nd, 0u);
   M.constraint_mask.clear();

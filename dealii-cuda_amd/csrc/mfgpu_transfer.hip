@@ -21,6 +21,8 @@
 //    and a transfer that does not cover the fine level simply leaves the other entries alone (no zero pass).
 // One 256-thread workgroup per coarse cell at a time (grid-stride); the three 1D contractions go through LDS.
 // Bound: HBM (one read of the fine vector + index lists); small next to the smoother's operator applies.
+// The same object and entry points also serve the transfer between two DEGREES on one mesh (p-multigrid): created by
+// mfgpu_transfer_create_p, kernels in mfgpu_transfer_p.hip (one wave per cell), dispatched here on t->degree_coarse.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,15 +33,7 @@
 
 #include "mfgpu_device.h"
 #include "mfgpu_mesh.h"
-
-struct mfgpu_transfer {
-  int dim = 0, degree = 0, number_type = MFGPU_F64;
-  uint32_t n_coarse_cells = 0, n_coarse_dofs = 0, n_fine_dofs = 0;
-  mfgpu::DeviceArray<uint32_t> d_coarse, d_fine;  // [cells][(p+1)^dim], [cells][(2p+1)^dim]
-  mfgpu::DeviceArray<void> d_p1;                  // P1[(2p+1) * (p+1)], X-major
-  bool covers_all = true;                         // every fine dof is listed by some patch
-  size_t device_bytes = 0;
-};
+#include "mfgpu_transfer.h"
 
 namespace mfgpu {
 
@@ -249,11 +243,12 @@ int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src
   hipStream_t st = (hipStream_t)stream;
   if (t->number_type == MFGPU_F64) {
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<double>, dim3(2048), dim3(256), 0, st, (double *)dst_fine, (size_t)t->n_fine_dofs);
-    HIP_TRY((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
+    if (!t->degree_coarse) HIP_TRY((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
   } else {
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst_fine, (size_t)t->n_fine_dofs);
-    HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
+    if (!t->degree_coarse) HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
   }
+  if (t->degree_coarse) HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE, st));
   return 0;
 }
 
@@ -264,7 +259,9 @@ int mfgpu_transfer_prolongate_add(mfgpu_transfer *t, void *dst_fine, const void 
     return MFGPU_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (t->number_type == MFGPU_F64)
+  if (t->degree_coarse)
+    HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE_ADD, st));
+  else if (t->number_type == MFGPU_F64)
     HIP_TRY((launch<double, false, true>(t, (double *)dst_fine, (const double *)src_coarse, st)));
   else
     HIP_TRY((launch<float, false, true>(t, (float *)dst_fine, (const float *)src_coarse, st)));
@@ -278,7 +275,9 @@ int mfgpu_transfer_restrict_and_add(mfgpu_transfer *t, void *dst_coarse, const v
     return MFGPU_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (t->number_type == MFGPU_F64)
+  if (t->degree_coarse)
+    HIP_TRY(launch_p_transfer(t, dst_coarse, src_fine, TRANSFER_RESTRICT_ADD, st));
+  else if (t->number_type == MFGPU_F64)
     HIP_TRY((launch<double, true>(t, (double *)dst_coarse, (const double *)src_fine, st)));
   else
     HIP_TRY((launch<float, true>(t, (float *)dst_coarse, (const float *)src_fine, st)));

@@ -128,6 +128,7 @@ SYMBOLS = [
     "mfgpu_vec_chebyshev_start_dev", "mfgpu_vec_chebyshev_update_dev", "mfgpu_cg_chebyshev_scalars_dev",
     "mfgpu_eig_workspace_bytes", "mfgpu_estimate_lambda_max_enqueue", "mfgpu_spd_inverse_workspace_bytes",
     "mfgpu_spd_inverse_enqueue", "mfgpu_vcycle_refresh", "mfgpu_vcycle_refresh_status", "mfgpu_estimate_lambda_max_steps",
+    "mfgpu_transfer_create_p", "mfgpu_transfer_create_p_from_meshes", "mfgpu_transfer_p_prolongation_1d",
 ]
 
 _lib = None
@@ -295,6 +296,9 @@ def lib():
         L.mfgpu_vcycle_refresh.argtypes = [vp, u32, vp]
         L.mfgpu_estimate_lambda_max_steps.argtypes = [vp, vp, u32, C.POINTER(d), C.POINTER(u32)]
         L.mfgpu_vcycle_refresh_status.argtypes = [vp, vp, C.POINTER(VCycleRefreshInfo)]
+        L.mfgpu_transfer_create_p.argtypes = [i, i, i, i, u32, vp, vp, u32, u32, vp, u32, vp, C.POINTER(vp)]
+        L.mfgpu_transfer_create_p_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
+        L.mfgpu_transfer_p_prolongation_1d.argtypes = [i, i, vp]
         _lib = L
     return _lib
 
@@ -943,7 +947,8 @@ class Level:
 
 
 class Transfer:
-    """MGTransferMatrixFreeGpu between two globally refined levels (mfgpu_transfer_*)."""
+    """MGTransferMatrixFreeGpu between two globally refined levels (mfgpu_transfer_*), or between two degrees on one mesh
+    (p_from_arrays / p_from_meshes: p-multigrid); the calls are the same for both."""
 
     def __init__(self, handle):
         self._h = handle
@@ -969,6 +974,34 @@ class Transfer:
         _check(lib().mfgpu_transfer_create_from_meshes(coarse._h, fine._h, C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def p_from_arrays(cls, dim, degree_coarse, degree_fine, coarse_cell_dofs, fine_cell_dofs, n_coarse_dofs, n_fine_dofs,
+                      coarse_dirichlet, number_type=F64, prolongation_1d=None):
+        """the p-multigrid transfer between FE_Q(degree_coarse) and FE_Q(degree_fine) on the same cells
+        (mfgpu_transfer_create_p): the two descriptions' loc2glob, same cell order"""
+        cd = np.ascontiguousarray(coarse_cell_dofs, dtype=np.uint32)
+        fd = np.ascontiguousarray(fine_cell_dofs, dtype=np.uint32)
+        di = np.ascontiguousarray(coarse_dirichlet, dtype=np.uint32)
+        p1 = None if prolongation_1d is None else np.ascontiguousarray(prolongation_1d, dtype=np.float64)
+        ncd, nfd = (max(int(degree_coarse), 0) + 1) ** dim, (max(int(degree_fine), 0) + 1) ** dim
+        n_cells = cd.size // ncd
+        if 1 <= degree_coarse < degree_fine <= 6:  # (any other pair is the library's MFGPU_EINVAL)
+            assert cd.size == n_cells * ncd and fd.size == n_cells * nfd
+            assert p1 is None or p1.size == (degree_coarse + 1) * (degree_fine + 1)
+        h = C.c_void_p()
+        _check(lib().mfgpu_transfer_create_p(dim, degree_coarse, degree_fine, number_type, n_cells,
+                                             cd.ctypes.data if cd.size else None, fd.ctypes.data if fd.size else None,
+                                             n_coarse_dofs, n_fine_dofs, di.ctypes.data if di.size else None, di.size,
+                                             None if p1 is None else p1.ctypes.data, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def p_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
+        """mfgpu_transfer_create_p_from_meshes: two stand-in meshes of the same cells, the degree rises"""
+        h = C.c_void_p()
+        _check(lib().mfgpu_transfer_create_p_from_meshes(coarse._h, fine._h, C.byref(h)))
+        return cls(h)
+
     def prolongate(self, dst_fine, src_coarse, stream=None):
         _check(lib().mfgpu_transfer_prolongate(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
 
@@ -986,6 +1019,14 @@ class Transfer:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mfgpu_transfer_destroy(self._h)
             self._h = None
+
+
+def p_prolongation_1d(degree_coarse, degree_fine):
+    """the default 1D matrix of the p-transfer, [degree_fine + 1, degree_coarse + 1] (mfgpu_transfer_p_prolongation_1d);
+    host only"""
+    out = np.zeros((max(int(degree_fine), 0) + 1, max(int(degree_coarse), 0) + 1), dtype=np.float64)
+    _check(lib().mfgpu_transfer_p_prolongation_1d(int(degree_coarse), int(degree_fine), out.ctypes.data))
+    return out
 
 
 def _ptr(v):
@@ -1226,6 +1267,31 @@ class VCycle:
         levels = [{"op": Operator(cls._flagged(M.desc, flags), M), "n_dofs": M.n_dofs,
                    "transfer": Transfer.from_meshes(meshes[l - 1], M) if l else None} for l, M in enumerate(meshes)]
         return cls(levels, nt if active_type is None else active_type, meshes[-1].n_dofs, keep=list(meshes), **options)
+
+    @staticmethod
+    def level_mesh_levels(meshes, flags=0):
+        """the `levels` of the constructor for any coarse-to-fine list of conforming stand-in meshes (cubes, balls): between
+        two consecutive meshes the h-transfer when the degrees are equal (the finer one is the global refinement), the
+        p-transfer when the degree rises (then the cells must be the same); anything else raises"""
+        levels = []
+        for l, M in enumerate(meshes):
+            tr = None
+            if l:
+                pc, pf = int(meshes[l - 1].desc.degree), int(M.desc.degree)
+                if pc > pf:
+                    raise MfgpuError(f"VCycle.level_mesh_levels: the degree falls from {pc} to {pf} between levels "
+                                     f"{l - 1} and {l}")
+                tr = Transfer.from_meshes(meshes[l - 1], M) if pc == pf else Transfer.p_from_meshes(meshes[l - 1], M)
+            levels.append({"op": Operator(VCycle._flagged(M.desc, flags), M), "n_dofs": M.n_dofs, "transfer": tr})
+        return levels
+
+    @classmethod
+    def from_level_meshes(cls, meshes, active_type=None, flags=0, **options):
+        """h- and p-multigrid over level_mesh_levels(meshes): no edges, no pairs, the active vector is the finest level's.
+        h-levels at degree 1 followed by 1 -> 2 -> 4 on the finest mesh is the hybrid hierarchy of host/poisson_pmg.cc"""
+        nt = int(meshes[0].desc.number_type)
+        return cls(cls.level_mesh_levels(meshes, flags), nt if active_type is None else active_type, meshes[-1].n_dofs,
+                   keep=list(meshes), **options)
 
     def apply(self, z, r, stream=None, check=True):
         """z = M^-1 r on active vectors (enqueued on `stream`)"""

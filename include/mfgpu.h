@@ -376,6 +376,30 @@ int mfgpu_transfer_prolongate_add(mfgpu_transfer *t, void *dst_fine_dev, const v
 size_t mfgpu_transfer_memory_consumption(const mfgpu_transfer *t); /* :333-347 */
 void mfgpu_transfer_destroy(mfgpu_transfer *t);
 
+/* ---- p-multigrid: the transfer between FE_Q(degree_coarse) and FE_Q(degree_fine) on the SAME
+ * cells, 1 <= degree_coarse < degree_fine <= 6, for callers who have one mesh and no coarser meshes behind it: the same
+ * triangulation with a second DoFHandler of lower degree is the coarse level.  Per cell its (pc+1)^dim
+ * coarse dofs and its (pf+1)^dim fine dofs, both lexicographic in the cell's own frame (the two descriptions' loc2glob,
+ * same cell order).  prolongation_1d [(pf+1) * (pc+1)], fine index major, or NULL = the coarse FE_Q Lagrange basis
+ * (Gauss-Lobatto nodes) evaluated at the fine FE_Q nodes.  Conforming meshes only (no hanging-node masks).  The object
+ * is an mfgpu_transfer: prolongate / prolongate_add / restrict_and_add / memory_consumption / destroy and mfgpu_vcycle
+ * take it like an h-transfer, with the same semantics -- every fine dof is owned by the first cell that lists it;
+ * prolongate is the owner's plain store with the coarse Dirichlet dofs read as 0 (fine dofs no cell lists are zeroed);
+ * prolongate_add the owner's plain read-modify-write; restrict_and_add reads a fine dof through its owner, skips the
+ * coarse Dirichlet dofs and accumulates with floating-point atomics.  All three only enqueue work.  h- and p-transfers
+ * mix freely in one V-cycle (h-levels at degree 1, then degree 1 -> 2 -> 4 on the finest mesh).
+ * MFGPU_EINVAL, nothing created: degree_coarse >= degree_fine, a degree outside 1..6, null arrays, a dof index outside
+ * its vector, dof counts >= 2^31.                                                                                     */
+int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int number_type, uint32_t n_cells,
+                            const uint32_t *coarse_cell_dofs /* [n_cells * (pc+1)^dim] */,
+                            const uint32_t *fine_cell_dofs /* [n_cells * (pf+1)^dim] */, uint32_t n_coarse_dofs,
+                            uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                            const double *prolongation_1d /* [(pf+1) * (pc+1)], fine index major, or NULL */,
+                            mfgpu_transfer **out);
+/* host only: the default matrix of mfgpu_transfer_create_p, [(pf+1) * (pc+1)]; rows of fine nodes that are coarse nodes
+ * (the end points; 1/2 when both degrees are even) hold exact zeros and a one                                        */
+int mfgpu_transfer_p_prolongation_1d(int degree_coarse, int degree_fine, double *p1);
+
 /* Level operator with refinement edges (laplace_operator_gpu.h:154-186, 306-352): `desc` describes the level mesh with
  * the level's Dirichlet dofs as constrained_dofs (no hanging nodes on a level mesh, :174-176), edge_dofs are the level's
  * refinement-edge dofs (MGConstrainedDoFs::get_refinement_edge_indices).  mfgpu_level_operator is the level matrix
@@ -719,6 +743,11 @@ int mfgpu_mesh_create_ball(int dim, int degree, int n_ref, int number_type, mfgp
 /* MGTransferMatrixFreeGpu::build for two stand-in meshes (uniform cubes n and 2n cells per direction, or ball meshes
  * of n_ref and n_ref + 1): the transfer between them, in the fine mesh's number type                               */
 int mfgpu_transfer_create_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
+/* mfgpu_transfer_create_p for two stand-in meshes of the same cells and two degrees, in the fine mesh's number type, with
+ * the coarse mesh's Dirichlet dofs; the meshes' current loc2glob is used as it is, so renumbered meshes work.
+ * MFGPU_EINVAL: not the same cells (dimension, kind, cells per direction and slab of a cube, n_ref of a ball, cell
+ * count) or degree_coarse >= degree_fine; MFGPU_EUNSUPPORTED: a mesh with hanging nodes (adaptive, from leaves)      */
+int mfgpu_transfer_create_p_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
 /* the index arrays that call hands to mfgpu_transfer_create, on the host (no GPU needed): coarse_cell_dofs
  * [n_cells * (p+1)^dim], fine_patch_dofs [n_cells * (2p+1)^dim], n_cells = the coarse mesh's; returns n_cells     */
 int64_t mfgpu_mesh_transfer_patches(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, uint32_t *coarse_cell_dofs,
