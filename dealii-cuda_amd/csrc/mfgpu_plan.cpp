@@ -405,7 +405,9 @@ class BatchGrower {
     }
   }
   // ---- the box the batch starts as: the first shape whose cells exist from the seed in +x, +y, +z, are unassigned
-  // and of the seed's kind, and which keeps every bound
+  // and of the seed's kind, and which keeps every bound.  On a periodic mesh a walk can come back to a cell it has
+  // already taken (a ring of 2 cells under a shape 3 cells long): cell_batch_ is only set by add_cell, so such a
+  // shape is rejected against box_ itself (at most max_cells entries).
   bool try_box(uint32_t seed) {
     for (const Shape &sh : shapes_) {
       box_.clear();
@@ -416,7 +418,8 @@ class BatchGrower {
         for (uint32_t j = 0; j < sh.b && ok; ++j) {
           uint32_t cx = cy;
           for (uint32_t i = 0; i < sh.a && ok; ++i) {
-            if (cx == NONE || cell_batch_[cx] != NONE || R_.masked(cx) != cls_) {
+            if (cx == NONE || cell_batch_[cx] != NONE || R_.masked(cx) != cls_ ||
+                std::find(box_.begin(), box_.end(), cx) != box_.end()) {
               ok = false;
               break;
             }

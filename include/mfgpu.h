@@ -88,7 +88,18 @@ typedef struct mfgpu_desc {
   uint32_t n_dofs;  /* vector length                              (matrix_free_gpu.cu:494)     */
   uint32_t n_cells; /* active cells                               (matrix_free_gpu.cu:495)     */
   const uint32_t *loc2glob;        /* [n_cells * n^dim] lexicographic (x fastest), hanging-node
-                                      entries already substituted   (matrix_free_gpu.cu:287-300) */
+                                      entries already substituted   (matrix_free_gpu.cu:287-300).
+                                      ANY cell-to-dof map with entries < n_dofs is accepted; the operator is
+                                      A = sum_cells P_c^T K_c P_c with P_c the gather through the cell's entries.
+                                      In particular: dofs identified across periodic boundaries (rings of 1, 2, ...
+                                      cells and tori included), one dof listed several times by one cell, any
+                                      numbering of the dofs, any order of the cells, ids no cell lists (rows of
+                                      zeros, or identity rows where constrained), and a vertex with more than 8
+                                      cells.  The one limit: the batches that list one dof must get different
+                                      colours (both scatter modes), and there are 64 colours -- a dof listed by
+                                      cells of more than 64 batches (a vertex of valence 125 under
+                                      max_cells_per_batch = 1) is refused with MFGPU_EUNSUPPORTED, "more than 64
+                                      batch colours needed".  Larger batches lift such a case below the limit.   */
   const uint32_t *constraint_mask; /* [n_cells] or NULL              (hanging_nodes.cuh:23-53)   */
   const void *JxW;                 /* [n_cells * n^dim]              (matrix_free_gpu.cu:315-322) */
   const void *inv_jac;             /* UNIFORM_J0: [n_cells]; else [n_cells * n^dim * dim*dim],

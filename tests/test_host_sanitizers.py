@@ -1,5 +1,6 @@
 """The host code of the library (planner, mesh stand-ins, multigrid hierarchy: plain C++, no HIP) compiled with
-AddressSanitizer + UndefinedBehaviorSanitizer and driven over every mesh kind and degree (tests/sanitize/plan_driver.cpp).
+AddressSanitizer + UndefinedBehaviorSanitizer and driven over every mesh kind and degree, and over periodic rings and tori,
+shuffled numberings and cell orders and a pinched vertex made from a uniform mesh's arrays (tests/sanitize/plan_driver.cpp).
 Sanitizers run on the CPU build only; the kernels' indexing is covered by the parity tests on the GPU."""
 import os
 import shutil
