@@ -106,6 +106,18 @@ void lagrange_eval(const std::vector<double> &nodes, double x, std::vector<doubl
   }
 }
 
+// W[i][j] = phi_j(x_i / 2)   (hanging_nodes.cuh:580-598)
+void fe_q_constraint_weights(int degree, std::vector<double> &W) {
+  const int n = degree + 1;
+  std::vector<double> nodes, v, d;
+  gll_01(degree, nodes);
+  W.assign(n * n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    lagrange_eval(nodes, 0.5 * nodes[i], v, d);
+    for (int j = 0; j < n; ++j) W[i * n + j] = v[j];
+  }
+}
+
 void Mesh::init_tables() {
   const int n = degree + 1;
   gll_01(degree, nodes);
@@ -120,12 +132,7 @@ void Mesh::init_tables() {
       shape_gradients[i * n + q] = d[i];
     }
   }
-  // W[i][j] = phi_j(x_i / 2)   (hanging_nodes.cuh:580-598)
-  weights.assign(n * n, 0.0);
-  for (int i = 0; i < n; ++i) {
-    lagrange_eval(nodes, 0.5 * nodes[i], v, d);
-    for (int j = 0; j < n; ++j) weights[i * n + j] = v[j];
-  }
+  fe_q_constraint_weights(degree, weights);
 }
 
 template <typename T>

@@ -13,6 +13,8 @@ void gauss_01(int n, std::vector<double> &x, std::vector<double> &w);
 void gll_01(int p, std::vector<double> &x);
 void lagrange_eval(const std::vector<double> &nodes, double x, std::vector<double> &val,
                    std::vector<double> &der);
+// the hanging-node weight matrix of FE_Q(degree), [(degree+1)^2] row-major (mfgpu_desc.constraint_weights)
+void fe_q_constraint_weights(int degree, std::vector<double> &W);
 
 struct Mesh {
   int dim = 0, degree = 0, number_type = MFGPU_F64;

@@ -19,6 +19,13 @@
 // Byte model per cell (T = 8 or 4 bytes, NC = (pc+1)^dim, NF = (pf+1)^dim): 4 (NC + NF) index bytes; prolongate reads NC T
 // and writes the owned part of NF T (prolongate_add reads it too); restrict_and_add reads the owned part of NF T and
 // issues up to NC atomic adds.  Index and vector traffic: the contractions are (pc+1 + pf+1) NF-sized passes through LDS.
+//
+// Cells with hanging nodes (mfgpu_transfer_create_p_hn): the kernel's HN = true instantiations.  The
+// cell's constraint mask (4 more bytes per cell) is requested one cell ahead like the index lists, the weight matrix of
+// the COARSE degree sits in LDS behind P1, and a masked cell runs resolve_hanging_nodes on its coarse values in its wave's
+// LDS slice: after the gather (prolongate), before the atomics (restrict, transposed).  Cells without a mask skip it on a
+// scalar branch.  The fine side needs nothing: a constrained fine position is a bit-31 entry made on the host
+// (p_owner_list).  HN = false is the code as it was.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,16 +53,89 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int dim, int pf, typename T, bool RESTRICT, bool ADD>
+// Run-time-n form of hn_flag3 / hn_flag2 (mfgpu_cell.h), for the host's owner rule and the kernel alike: does
+// resolve_hanging_nodes interpolate the pencil along `dir` whose other coordinates are f1 (direction (dir+1)%3; in 2D
+// the other direction) and f2 (direction (dir+2)%3), and from which half of the parent's line (type)?
+__host__ __device__ inline bool hn_flag_rt(int dim, int p, unsigned m, int dir, int f1, int f2, bool &type) {
+  type = (m >> dir) & 1u;  // TYPE x, y, z: bits 0..2; FACE x, y, z: bits 3..5; EDGE xy, yz, zx: bits 6..8
+  if (dim == 2) {
+    const int o = 1 - dir;
+    const bool on = ((m >> o) & 1u) ? f1 == 0 : f1 == p;
+    return ((m >> (3 + o)) & 1u) && on;
+  }
+  const int d1 = (dir + 1) % 3, d2 = (dir + 2) % 3;
+  const bool on1 = ((m >> d1) & 1u) ? f1 == 0 : f1 == p;
+  const bool on2 = ((m >> d2) & 1u) ? f2 == 0 : f2 == p;
+  const int edge = dir == 0 ? 7 : dir == 1 ? 8 : 6;  // the edge along dir: yz, zx, xy
+  return (((m >> (3 + d1)) & 1u) && on1) || (((m >> (3 + d2)) & 1u) && on2) || (((m >> edge) & 1u) && on1 && on2);
+}
+// the same for the pencil along `dir` through local position t of n^dim (x fastest); q = t's coordinate along dir
+__host__ __device__ inline bool hn_flag_at(int dim, int n, unsigned m, int dir, int t, bool &type, int &q) {
+  const int c[3] = {t % n, (t / n) % n, dim == 3 ? t / (n * n) : 0};
+  q = c[dir];
+  return dim == 2 ? hn_flag_rt(2, n - 1, m, dir, c[1 - dir], 0, type)
+                  : hn_flag_rt(3, n - 1, m, dir, c[(dir + 1) % 3], c[(dir + 2) % 3], type);
+}
+// the bits of a mask that make resolve_hanging_nodes touch pencils along dir (none set: the pass is the identity)
+__host__ __device__ inline unsigned hn_dir_bits(int dim, int dir) {
+  if (dim == 2) return 1u << (3 + 1 - dir);
+  return (1u << (3 + (dir + 1) % 3)) | (1u << (3 + (dir + 2) % 3)) | (1u << (dir == 0 ? 7 : dir == 1 ? 8 : 6));
+}
+
+// resolve_hanging_nodes (TR: its transpose) at run-time n = pc + 1 on the n^dim values v of ONE wave's cell, with the
+// weight matrix W[n * n] in LDS: the passes x, y, z of oracle hn_resolve (transpose: z, y, x, so that it is the exact
+// transpose).  The pencils of one pass are disjoint, but an output reads its whole pencil: every lane computes the new
+// values of its entries (lane + 64 j) into registers, then the wave writes them.  KC slots cover pf^dim >= n^dim entries.
+template <int dim, bool TR, int KC, typename T>
+__device__ __forceinline__ void hn_resolve_wave(T *v, const T *W, int n, unsigned mask, int lane) {
+  const int NC = dim == 3 ? n * n * n : n * n;
+#pragma unroll
+  for (int s = 0; s < dim; ++s) {
+    const int dir = TR ? dim - 1 - s : s;
+    if (!(mask & hn_dir_bits(dim, dir))) continue;  // (uniform)
+    const int stride = dir == 0 ? 1 : dir == 1 ? n : n * n;
+    T r[KC];
+    unsigned hit = 0;
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      const int t = lane + 64 * j;
+      bool type;
+      int q;
+      r[j] = T(0);
+      if (t < NC && hn_flag_at(dim, n, mask, dir, t, type, q)) {
+        hit |= 1u << j;
+        // type: w = TR ? W[i][q] : W[q][i]; otherwise the mirrored entry W[p-i][p-q] / W[p-q][p-i] (hn_pencil), which
+        // sits at n * n - 1 - (the index of the unmirrored one)
+        const T *w = type ? W + (TR ? q : q * n) : W + (TR ? n * n - 1 - q : n * n - 1 - q * n);
+        const int ws = (TR ? n : 1) * (type ? 1 : -1);
+        const T *x = v + (t - q * stride);
+        T sum = T(0);
+        for (int i = 0; i < n; ++i) sum += w[i * ws] * x[i * stride];
+        r[j] = sum;
+      }
+    }
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < KC; ++j)
+      if ((hit >> j) & 1u) v[lane + 64 * j] = r[j];
+    wave_sync();
+  }
+}
+
+template <int dim, int pf, typename T, bool RESTRICT, bool ADD, bool HN>
 __global__ void __launch_bounds__(64 * kWaves)
 p_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ coarse,
-                  const uint32_t *__restrict__ fine, const T *__restrict__ p1, uint32_t n_cells, int pc) {
+                  const uint32_t *__restrict__ fine, const T *__restrict__ p1, uint32_t n_cells, int pc,
+                  const uint32_t *__restrict__ cmask, const T *__restrict__ hn_weights) {
   constexpr int nf = pf + 1, NF = ipow_c(nf, dim);
   const int nc = pc + 1;                         // 2 .. pf
   const int NC = dim == 3 ? nc * nc * nc : nc * nc;  // <= NF; every intermediate array has at most NF entries too
-  __shared__ T buf[kWaves][2][NF], P[nf * pf];
+  __shared__ T buf[kWaves][2][NF], P[nf * pf + (HN ? pf * pf : 0)];  // HN: W[nc * nc] of the coarse degree behind P1
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int t = threadIdx.x; t < nf * nc; t += 64 * kWaves) P[t] = p1[t];
+  const T *W = P + nf * pf;
+  if (HN)
+    for (int t = threadIdx.x; t < nc * nc; t += 64 * kWaves) P[nf * pf + t] = hn_weights[t];
   __syncthreads();
   // A cell's two index lists sit in registers (entry lane + 64 j in slot j; past the end: bit 31, "skip") and are
   // requested ONE CELL AHEAD: index -> value is a dependent pair of global loads at both ends of a cell, and a wave
@@ -71,6 +151,8 @@ p_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t
     gc[j] = (cell < n_cells && t < NC) ? coarse[cell * NC + t] : kSkip;
     gf[j] = (cell < n_cells && t < NF) ? fine[cell * NF + t] : kSkip;
   }
+  uint32_t mask = (HN && cell < n_cells) ? cmask[cell] : 0u;  // requested one cell ahead like the index lists
+  constexpr int KC = (ipow_c(pf, dim) + 63) / 64;
   for (; cell < n_cells; cell += stride) {
     T *in = buf[wave][0], *out = buf[wave][1];
     wave_sync();  // the previous cell's last reads of its arrays come first
@@ -91,7 +173,11 @@ p_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t
       next_gc[j] = (next < n_cells && t < NC) ? coarse[next * NC + t] : kSkip;
       next_gf[j] = (next < n_cells && t < NF) ? fine[next * NF + t] : kSkip;
     }
+    const uint32_t next_mask = (HN && next < n_cells) ? cmask[next] : 0u;
+    // one wave owns one cell: the mask is the same in all lanes, say so (a scalar branch; cells without a mask skip)
+    const uint32_t m = HN ? (uint32_t)__builtin_amdgcn_readfirstlane((int)mask) : 0u;
     wave_sync();
+    if (HN && !RESTRICT && m) hn_resolve_wave<dim, false, KC>(in, W, nc, m, lane);  // C_pc on the gathered coarse values
 #pragma unroll
     for (int k = 0; k < dim; ++k) {
       if (!RESTRICT) {
@@ -125,6 +211,7 @@ p_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t
       in = out;
       out = tmp;
     }
+    if (HN && RESTRICT && m) hn_resolve_wave<dim, true, KC>(in, W, nc, m, lane);  // C_pc^T before the atomics
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
       const int t = lane + 64 * j;
@@ -138,10 +225,11 @@ p_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t
       gc[j] = next_gc[j];
       gf[j] = next_gf[j];
     }
+    mask = next_mask;
   }
 }
 
-template <typename T, bool RESTRICT, bool ADD>
+template <typename T, bool RESTRICT, bool ADD, bool HN>
 hipError_t launch_p(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t st) {
   const uint32_t n = t->n_coarse_cells;
   if (n == 0) return hipSuccess;
@@ -149,8 +237,9 @@ hipError_t launch_p(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t s
   const unsigned grid = groups < kMaxGrid ? groups : kMaxGrid;
 #define TRP_CASE(D, PF)                                                                                          \
   case D * 10 + PF:                                                                                              \
-    hipLaunchKernelGGL((p_transfer_kernel<D, PF, T, RESTRICT, ADD>), dim3(grid), dim3(64 * kWaves), 0, st, dst, src, \
-                       t->d_coarse.get(), t->d_fine.get(), t->d_p1.as<const T>(), n, t->degree_coarse);          \
+    hipLaunchKernelGGL((p_transfer_kernel<D, PF, T, RESTRICT, ADD, HN>), dim3(grid), dim3(64 * kWaves), 0, st, dst, src, \
+                       t->d_coarse.get(), t->d_fine.get(), t->d_p1.as<const T>(), n, t->degree_coarse,           \
+                       HN ? t->d_mask.get() : nullptr, HN ? t->d_weights.as<const T>() : nullptr);               \
     break;
   switch (t->dim * 10 + t->degree) {
     TRP_CASE(2, 2) TRP_CASE(2, 3) TRP_CASE(2, 4) TRP_CASE(2, 5) TRP_CASE(2, 6)
@@ -161,12 +250,12 @@ hipError_t launch_p(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t s
   return hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool HN>
 hipError_t launch_mode(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {
   switch (mode) {
-    case TRANSFER_PROLONGATE: return launch_p<T, false, false>(t, (T *)dst, (const T *)src, st);
-    case TRANSFER_PROLONGATE_ADD: return launch_p<T, false, true>(t, (T *)dst, (const T *)src, st);
-    case TRANSFER_RESTRICT_ADD: return launch_p<T, true, false>(t, (T *)dst, (const T *)src, st);
+    case TRANSFER_PROLONGATE: return launch_p<T, false, false, HN>(t, (T *)dst, (const T *)src, st);
+    case TRANSFER_PROLONGATE_ADD: return launch_p<T, false, true, HN>(t, (T *)dst, (const T *)src, st);
+    case TRANSFER_RESTRICT_ADD: return launch_p<T, true, false, HN>(t, (T *)dst, (const T *)src, st);
   }
   return hipErrorInvalidValue;
 }
@@ -193,10 +282,72 @@ void p_prolongation_1d(int pc, int pf, std::vector<double> &P1) {
   }
 }
 
+// the 9 bits of a constraint mask (hanging_nodes.cuh:38-50); in 2D only TYPE x, y and FACE x, y
+bool valid_mask(int dim, uint32_t m) { return !(m & ~(dim == 3 ? 0x1ffu : 0x1bu)); }
+
+// can resolve_hanging_nodes with mask m write local position t of a cell of n^dim entries?
+bool constrained_position(int dim, int n, uint32_t m, int t) {
+  bool type;
+  int q;
+  for (int dir = 0; dir < dim; ++dir)
+    if (hn_flag_at(dim, n, m, dir, t, type, q)) return true;
+  return false;
+}
+
+// The fine index list as it is uploaded: bit 31 on every entry but the owner's.  The owner of a fine dof is the first
+// cell, in cell order, that lists it at a position that is not constrained (without a mask: the first that lists it).
+// `covered` = the number of fine dofs with an owner.  A dof that is listed but has no owner is an error: the kernels would
+// drop it without a word.
+int p_owner_list(const char *who, int dim, int degree_fine, uint32_t n_cells, const uint32_t *fine_cell_dofs,
+                 const uint32_t *mask, uint32_t n_fine_dofs, uint32_t *out, size_t &covered) {
+  const int nf = degree_fine + 1;
+  const size_t NF = (size_t)ipow(nf, dim);
+  std::vector<uint8_t> seen(n_fine_dofs, 0);  // 1: listed, 2: owned
+  std::vector<uint8_t> con;                   // the constrained positions of the current cell's mask
+  uint32_t con_mask = 0;
+  covered = 0;
+  size_t listed = 0;
+  for (uint32_t c = 0; c < n_cells; ++c) {
+    const uint32_t m = mask ? mask[c] : 0u;
+    if (!valid_mask(dim, m)) {
+      set_error(std::string(who) + ": a constraint mask has bits outside the defined ones (9 in 3D; TYPE x, y and FACE x, y "
+                "in 2D)");
+      return MFGPU_EINVAL;
+    }
+    if (m && (con.empty() || m != con_mask)) {
+      con.resize(NF);
+      for (size_t i = 0; i < NF; ++i) con[i] = constrained_position(dim, nf, m, (int)i);
+      con_mask = m;
+    }
+    for (size_t i = 0; i < NF; ++i) {
+      const uint32_t g = fine_cell_dofs[c * NF + i];
+      if (g >= n_fine_dofs) {
+        set_error(std::string(who) + ": fine dof out of range");
+        return MFGPU_EINVAL;
+      }
+      const bool owns = seen[g] < 2 && !(m && con[i]);
+      out[c * NF + i] = g | (owns ? 0u : 0x80000000u);
+      if (!seen[g]) ++listed;
+      if (owns) ++covered;
+      seen[g] = owns ? 2 : (seen[g] ? seen[g] : 1);
+    }
+  }
+  if (covered != listed) {
+    set_error(std::string(who) + ": a fine dof is listed only at constrained positions, so no cell owns it (the masks and "
+              "fine_cell_dofs do not belong together)");
+    return MFGPU_EINVAL;
+  }
+  return 0;
+}
+
 }  // namespace
 
 hipError_t launch_p_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {
-  return t->number_type == MFGPU_F64 ? launch_mode<double>(t, dst, src, mode, st) : launch_mode<float>(t, dst, src, mode, st);
+  if (t->hanging_nodes)
+    return t->number_type == MFGPU_F64 ? launch_mode<double, true>(t, dst, src, mode, st)
+                                       : launch_mode<float, true>(t, dst, src, mode, st);
+  return t->number_type == MFGPU_F64 ? launch_mode<double, false>(t, dst, src, mode, st)
+                                     : launch_mode<float, false>(t, dst, src, mode, st);
 }
 
 }  // namespace mfgpu
@@ -215,10 +366,33 @@ int mfgpu_transfer_p_prolongation_1d(int degree_coarse, int degree_fine, double 
   return 0;
 }
 
+int mfgpu_transfer_p_owner_list(int dim, int degree_fine, uint32_t n_cells, const uint32_t *fine_cell_dofs,
+                                const uint32_t *constraint_mask, uint32_t n_fine_dofs, uint32_t *out) {
+  using namespace mfgpu;
+  if ((dim != 2 && dim != 3) || degree_fine < 1 || degree_fine > 6 || (n_cells && (!fine_cell_dofs || !out)) ||
+      n_fine_dofs >= (1u << 31)) {
+    set_error("mfgpu_transfer_p_owner_list: bad argument (1 <= degree_fine <= 6, dim 2 or 3, dof count < 2^31, arrays)");
+    return MFGPU_EINVAL;
+  }
+  size_t covered;
+  return p_owner_list("mfgpu_transfer_p_owner_list", dim, degree_fine, n_cells, fine_cell_dofs, constraint_mask, n_fine_dofs,
+                      out, covered);
+}
+
 int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int number_type, uint32_t n_cells,
                             const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, uint32_t n_coarse_dofs,
                             uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
                             const double *prolongation_1d, mfgpu_transfer **out) {
+  return mfgpu_transfer_create_p_hn(dim, degree_coarse, degree_fine, number_type, n_cells, coarse_cell_dofs, fine_cell_dofs,
+                                    n_coarse_dofs, n_fine_dofs, coarse_dirichlet, n_coarse_dirichlet, prolongation_1d, nullptr,
+                                    nullptr, out);
+}
+
+int mfgpu_transfer_create_p_hn(int dim, int degree_coarse, int degree_fine, int number_type, uint32_t n_cells,
+                               const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, uint32_t n_coarse_dofs,
+                               uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                               const double *prolongation_1d, const uint32_t *constraint_mask,
+                               const double *coarse_constraint_weights, mfgpu_transfer **out) {
   using namespace mfgpu;
   if (!out || (dim != 2 && dim != 3) || !valid_degree_pair(degree_coarse, degree_fine) ||
       (n_cells && (!coarse_cell_dofs || !fine_cell_dofs)) || (n_coarse_dirichlet && !coarse_dirichlet) ||
@@ -228,7 +402,7 @@ int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int num
   }
   const int nc = degree_coarse + 1, nf = degree_fine + 1;
   const size_t NC = (size_t)ipow(nc, dim), NF = (size_t)ipow(nf, dim);
-  std::vector<uint8_t> dir(n_coarse_dofs, 0), seen(n_fine_dofs, 0);
+  std::vector<uint8_t> dir(n_coarse_dofs, 0);
   for (uint32_t i = 0; i < n_coarse_dirichlet; ++i) {
     if (coarse_dirichlet[i] >= n_coarse_dofs) {
       set_error("mfgpu_transfer_create_p: Dirichlet dof out of range");
@@ -246,16 +420,10 @@ int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int num
     cd[i] = g | (dir[g] ? 0x80000000u : 0u);
   }
   size_t covered = 0;
-  for (size_t i = 0; i < fd.size(); ++i) {
-    const uint32_t g = fine_cell_dofs[i];
-    if (g >= n_fine_dofs) {
-      set_error("mfgpu_transfer_create_p: fine dof out of range");
-      return MFGPU_EINVAL;
-    }
-    fd[i] = g | (seen[g] ? 0x80000000u : 0u);  // the first cell that lists a fine dof owns it
-    if (!seen[g]) ++covered;
-    seen[g] = 1;
-  }
+  int rc;
+  if ((rc = p_owner_list("mfgpu_transfer_create_p", dim, degree_fine, n_cells, fine_cell_dofs, constraint_mask, n_fine_dofs,
+                         fd.data(), covered)))
+    return rc;
   std::vector<double> P1;
   if (prolongation_1d)
     P1.assign(prolongation_1d, prolongation_1d + (size_t)nf * nc);
@@ -272,11 +440,23 @@ int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int num
   t->covers_all = covered == n_fine_dofs;
   std::vector<float> P1f(P1.begin(), P1.end());
   const void *p1src = number_type == MFGPU_F64 ? (const void *)P1.data() : (const void *)P1f.data();
-  int rc;
   if ((rc = t->d_coarse.upload(cd.data(), cd.size())) || (rc = t->d_fine.upload(fd.data(), fd.size())) ||
       (rc = t->d_p1.upload(p1src, P1.size() * esize(number_type))))
     return rc;
   t->device_bytes = t->d_coarse.bytes() + t->d_fine.bytes() + t->d_p1.bytes();
+  if (constraint_mask) {  // (NULL: the conforming object, the HN = false kernels)
+    std::vector<double> W;
+    if (coarse_constraint_weights)
+      W.assign(coarse_constraint_weights, coarse_constraint_weights + (size_t)nc * nc);
+    else
+      fe_q_constraint_weights(degree_coarse, W);
+    std::vector<float> Wf(W.begin(), W.end());
+    const void *wsrc = number_type == MFGPU_F64 ? (const void *)W.data() : (const void *)Wf.data();
+    if ((rc = t->d_mask.upload(constraint_mask, n_cells)) || (rc = t->d_weights.upload(wsrc, W.size() * esize(number_type))))
+      return rc;
+    t->hanging_nodes = true;
+    t->device_bytes += t->d_mask.bytes() + t->d_weights.bytes();
+  }
   *out = t.release();
   return 0;
 }
@@ -303,6 +483,27 @@ int mfgpu_transfer_create_p_from_meshes(const mfgpu_mesh *coarse, const mfgpu_me
   }
   return mfgpu_transfer_create_p(C.dim, C.degree, F.degree, F.number_type, C.n_cells, C.loc2glob.data(), F.loc2glob.data(),
                                  C.n_dofs, F.n_dofs, C.constrained.data(), (uint32_t)C.constrained.size(), nullptr, out);
+}
+
+int mfgpu_transfer_create_p_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
+  using namespace mfgpu;
+  if (!coarse || !fine || !out) {
+    set_error("mfgpu_transfer_create_p_hn_from_meshes: null argument");
+    return MFGPU_EINVAL;
+  }
+  const Mesh &C = coarse->mesh, &F = fine->mesh;
+  if (C.cells_kind >= 0 && F.cells_kind >= 0 && C.constraint_mask.empty() && F.constraint_mask.empty())
+    return mfgpu_transfer_create_p_from_meshes(coarse, fine, out);
+  // adaptive meshes and meshes from leaves: the same leaves in the same order; the masks are geometric, so equal too
+  if (C.cells_kind != -1 || F.cells_kind != -1 || C.dim != F.dim || C.n_cells != F.n_cells || C.cell_levels.empty() ||
+      C.cell_levels != F.cell_levels || C.constraint_mask != F.constraint_mask) {
+    set_error("mfgpu_transfer_create_p_hn_from_meshes: the two meshes are not the same cells (dimension, cell count, the "
+              "leaves and their order, constraint masks)");
+    return MFGPU_EINVAL;
+  }
+  return mfgpu_transfer_create_p_hn(C.dim, C.degree, F.degree, F.number_type, C.n_cells, C.loc2glob.data(), F.loc2glob.data(),
+                                    C.n_dofs, F.n_dofs, C.constrained.data(), (uint32_t)C.constrained.size(), nullptr,
+                                    C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(), C.weights.data(), out);
 }
 
 }  // extern "C"

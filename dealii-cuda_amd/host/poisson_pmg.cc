@@ -1,13 +1,18 @@
 // poisson_pmg: the problem of poisson_mg.cc -- CG to 1e-12 |b| on the variable-coefficient Laplacian, b = A x* for a known
 // x* -- preconditioned by one V-cycle over a HYBRID hierarchy: h-levels at degree 1 up to the mesh
 // of n_ref, then on that mesh the degrees that halve down from DEGREE_FE (rounding down) until 1, e.g. 1 -> 2 -> 4.  The
-// p-steps are mfgpu_transfer_create_p_from_meshes, the h-steps mfgpu_transfer_create_from_meshes; the V-cycle is the
+// p-steps are mfgpu_transfer_create_p_hn_from_meshes (on conforming meshes mfgpu_transfer_create_p_from_meshes), the h-steps mfgpu_transfer_create_from_meshes; the V-cycle is the
 // library's mfgpu_vcycle (Chebyshev(5, range 15) smoothers with estimated lambda_max, level 0 solved on the device) under
 // the device CG, so the solve stops the host only in mfgpu_cg_status.  Written on the C-ABI: the shim's classes are
 // templated on one degree.
 // CUBE: the h-levels run from 2 cells per direction (one cell at degree 1 has no free dof); BALL (-DBALL_GRID): from
 // n_ref 0.
-// Output:  dim  degree  n_dofs  levels  cg_iterations  wall_seconds  rel_error        usage: poisson-pmg-<dim>d-p<k> n_ref
+// ADAPTIVE (-DADAPTIVE_GRID): the adaptively refined cube of bmop / poisson with its hanging nodes,
+// an active mesh without a level hierarchy.  No h-levels: the levels are that ONE mesh at the halving degrees, 1 -> 2 -> 4,
+// joined by mfgpu_transfer_create_p_hn_from_meshes.  Level 0 is the whole mesh at degree 1, so above
+// MFGPU_VCYCLE_DENSE_MAX dofs its solve is the unpreconditioned device CG, capped by the second argument.
+// Output:  dim  degree  n_dofs  levels  cg_iterations  wall_seconds  rel_error
+// usage: poisson-pmg-<dim>d-p<k>[-ball] n_ref          poisson-pmg-<dim>d-p<k>-adaptive n_ref [coarse_max_iterations]
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -32,7 +37,9 @@ namespace {
 
 mfgpu_mesh *create_mesh(int dim, int degree, int n_ref) {
   mfgpu_mesh *m = nullptr;
-#ifdef BALL_GRID
+#if defined(ADAPTIVE_GRID)
+  check(mfgpu_mesh_create_adaptive(dim, degree, n_ref, MFGPU_F64, &m), "level mesh");
+#elif defined(BALL_GRID)
   check(mfgpu_mesh_create_ball(dim, degree, n_ref, MFGPU_F64, &m), "level mesh");
 #else
   const uint32_t nper[3] = {1u << n_ref, 1u << n_ref, 1u << n_ref};
@@ -57,8 +64,10 @@ struct Hierarchy {
   }
 };
 
-int run(int dim, int fe_degree, int n_ref) {
-#ifdef BALL_GRID
+int run(int dim, int fe_degree, int n_ref, unsigned int coarse_max_iterations) {
+#if defined(ADAPTIVE_GRID)
+  const int first_ref = n_ref;  // the one mesh at degree 1
+#elif defined(BALL_GRID)
   const int first_ref = 0;
 #else
   const int first_ref = 1;
@@ -86,7 +95,7 @@ int run(int dim, int fe_degree, int n_ref) {
     check(mfgpu_create(&d, &op), "level operator");
     H.ops.push_back(op);
     if (l > 0)
-      check(p_step[l] ? mfgpu_transfer_create_p_from_meshes(H.meshes[l - 1], H.meshes[l], &H.transfers[l])
+      check(p_step[l] ? mfgpu_transfer_create_p_hn_from_meshes(H.meshes[l - 1], H.meshes[l], &H.transfers[l])
                       : mfgpu_transfer_create_from_meshes(H.meshes[l - 1], H.meshes[l], &H.transfers[l]),
             "level transfer");
     levels[l] = mfgpu_vcycle_level_desc{};
@@ -106,6 +115,7 @@ int run(int dim, int fe_degree, int n_ref) {
   vd.eig_iterations = 15;
   vd.lambda_max = nullptr;  // estimated, as PreconditionChebyshev does in poisson_mg.cc
   vd.coarse = MFGPU_VCYCLE_COARSE_AUTO;
+  vd.coarse_max_iterations = coarse_max_iterations;  // (0: n_dofs(0); read by the CG mode only)
   check(mfgpu_vcycle_create(&vd, &H.vcycle), "mfgpu_vcycle_create");
   check(mfgpu_cg_create(system_matrix, MFGPU_CG_CALLBACK, nullptr, 0, 0, 0, &H.cg), "mfgpu_cg_create");
   check(mfgpu_cg_set_vcycle(H.cg, H.vcycle), "mfgpu_cg_set_vcycle");
@@ -135,7 +145,8 @@ int run(int dim, int fe_degree, int n_ref) {
 int main(int argc, char **argv) {
   try {
     const int n_ref = argc > 1 ? atoi(argv[1]) : 3;
-    return run(DIMENSION, DEGREE_FE, n_ref);
+    const int coarse_cap = argc > 2 ? atoi(argv[2]) : 0;
+    return run(DIMENSION, DEGREE_FE, n_ref, coarse_cap > 0 ? (unsigned int)coarse_cap : 0u);
   } catch (std::exception &exc) {
     std::cerr << "Exception on processing: " << exc.what() << std::endl;
     return 1;

@@ -129,6 +129,7 @@ SYMBOLS = [
     "mfgpu_eig_workspace_bytes", "mfgpu_estimate_lambda_max_enqueue", "mfgpu_spd_inverse_workspace_bytes",
     "mfgpu_spd_inverse_enqueue", "mfgpu_vcycle_refresh", "mfgpu_vcycle_refresh_status", "mfgpu_estimate_lambda_max_steps",
     "mfgpu_transfer_create_p", "mfgpu_transfer_create_p_from_meshes", "mfgpu_transfer_p_prolongation_1d",
+    "mfgpu_transfer_create_p_hn", "mfgpu_transfer_create_p_hn_from_meshes", "mfgpu_transfer_p_owner_list",
 ]
 
 _lib = None
@@ -299,6 +300,9 @@ def lib():
         L.mfgpu_transfer_create_p.argtypes = [i, i, i, i, u32, vp, vp, u32, u32, vp, u32, vp, C.POINTER(vp)]
         L.mfgpu_transfer_create_p_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
         L.mfgpu_transfer_p_prolongation_1d.argtypes = [i, i, vp]
+        L.mfgpu_transfer_create_p_hn.argtypes = [i, i, i, i, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(vp)]
+        L.mfgpu_transfer_create_p_hn_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
+        L.mfgpu_transfer_p_owner_list.argtypes = [i, i, u32, vp, vp, u32, vp]
         _lib = L
     return _lib
 
@@ -1002,6 +1006,43 @@ class Transfer:
         _check(lib().mfgpu_transfer_create_p_from_meshes(coarse._h, fine._h, C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def p_hn_from_arrays(cls, dim, degree_coarse, degree_fine, coarse_cell_dofs, fine_cell_dofs, n_coarse_dofs, n_fine_dofs,
+                         coarse_dirichlet, number_type=F64, prolongation_1d=None, constraint_mask=None,
+                         coarse_constraint_weights=None):
+        """p_from_arrays on cells with hanging nodes (mfgpu_transfer_create_p_hn): constraint_mask [n_cells] is the one of
+        both descriptions (None: conforming), coarse_constraint_weights [(degree_coarse + 1)^2] the coarse description's
+        constraint_weights (None: those of FE_Q(degree_coarse))"""
+        cd = np.ascontiguousarray(coarse_cell_dofs, dtype=np.uint32)
+        fd = np.ascontiguousarray(fine_cell_dofs, dtype=np.uint32)
+        di = np.ascontiguousarray(coarse_dirichlet, dtype=np.uint32)
+        p1 = None if prolongation_1d is None else np.ascontiguousarray(prolongation_1d, dtype=np.float64)
+        cm = None if constraint_mask is None else np.ascontiguousarray(constraint_mask, dtype=np.uint32)
+        w = None if coarse_constraint_weights is None else np.ascontiguousarray(coarse_constraint_weights, dtype=np.float64)
+        ncd, nfd = (max(int(degree_coarse), 0) + 1) ** dim, (max(int(degree_fine), 0) + 1) ** dim
+        n_cells = cd.size // ncd
+        if 1 <= degree_coarse < degree_fine <= 6:  # (any other pair is the library's MFGPU_EINVAL)
+            assert cd.size == n_cells * ncd and fd.size == n_cells * nfd
+            assert p1 is None or p1.size == (degree_coarse + 1) * (degree_fine + 1)
+            assert cm is None or cm.size == n_cells
+            assert w is None or w.size == (degree_coarse + 1) ** 2
+        h = C.c_void_p()
+        _check(lib().mfgpu_transfer_create_p_hn(dim, degree_coarse, degree_fine, number_type, n_cells,
+                                                cd.ctypes.data if cd.size else None, fd.ctypes.data if fd.size else None,
+                                                n_coarse_dofs, n_fine_dofs, di.ctypes.data if di.size else None, di.size,
+                                                None if p1 is None else p1.ctypes.data,
+                                                None if cm is None else cm.ctypes.data,
+                                                None if w is None else w.ctypes.data, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def p_hn_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
+        """mfgpu_transfer_create_p_hn_from_meshes: what p_from_meshes accepts, and adaptive meshes or meshes from leaves
+        of equal cells and masks"""
+        h = C.c_void_p()
+        _check(lib().mfgpu_transfer_create_p_hn_from_meshes(coarse._h, fine._h, C.byref(h)))
+        return cls(h)
+
     def prolongate(self, dst_fine, src_coarse, stream=None):
         _check(lib().mfgpu_transfer_prolongate(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
 
@@ -1026,6 +1067,20 @@ def p_prolongation_1d(degree_coarse, degree_fine):
     host only"""
     out = np.zeros((max(int(degree_fine), 0) + 1, max(int(degree_coarse), 0) + 1), dtype=np.float64)
     _check(lib().mfgpu_transfer_p_prolongation_1d(int(degree_coarse), int(degree_fine), out.ctypes.data))
+    return out
+
+
+def p_owner_list(dim, degree_fine, fine_cell_dofs, n_fine_dofs, constraint_mask=None):
+    """the fine index list of a p-transfer as it is uploaded, [n_cells, (degree_fine + 1)^dim] with bit 31 on every entry
+    but the owner's (mfgpu_transfer_p_owner_list); host only"""
+    fd = np.ascontiguousarray(fine_cell_dofs, dtype=np.uint32)
+    nfd = (max(int(degree_fine), 0) + 1) ** dim
+    n_cells = fd.size // nfd
+    cm = None if constraint_mask is None else np.ascontiguousarray(constraint_mask, dtype=np.uint32)
+    assert fd.size == n_cells * nfd and (cm is None or cm.size == n_cells)
+    out = np.zeros((n_cells, nfd), dtype=np.uint32)
+    _check(lib().mfgpu_transfer_p_owner_list(dim, int(degree_fine), n_cells, fd.ctypes.data if fd.size else None,
+                                             None if cm is None else cm.ctypes.data, n_fine_dofs, out.ctypes.data))
     return out
 
 
@@ -1270,9 +1325,10 @@ class VCycle:
 
     @staticmethod
     def level_mesh_levels(meshes, flags=0):
-        """the `levels` of the constructor for any coarse-to-fine list of conforming stand-in meshes (cubes, balls): between
-        two consecutive meshes the h-transfer when the degrees are equal (the finer one is the global refinement), the
-        p-transfer when the degree rises (then the cells must be the same); anything else raises"""
+        """the `levels` of the constructor for any coarse-to-fine list of stand-in meshes: between two consecutive meshes
+        the h-transfer when the degrees are equal (conforming cubes or balls, the finer one the global refinement), the
+        p-transfer when the degree rises (then the cells must be the same; with hanging nodes -- adaptive meshes, meshes
+        from leaves -- Transfer.p_hn_from_meshes); anything else raises"""
         levels = []
         for l, M in enumerate(meshes):
             tr = None
@@ -1281,7 +1337,11 @@ class VCycle:
                 if pc > pf:
                     raise MfgpuError(f"VCycle.level_mesh_levels: the degree falls from {pc} to {pf} between levels "
                                      f"{l - 1} and {l}")
-                tr = Transfer.from_meshes(meshes[l - 1], M) if pc == pf else Transfer.p_from_meshes(meshes[l - 1], M)
+                masked = bool(meshes[l - 1].desc.constraint_mask) or bool(M.desc.constraint_mask)
+                if pc == pf:
+                    tr = Transfer.from_meshes(meshes[l - 1], M)
+                else:
+                    tr = (Transfer.p_hn_from_meshes if masked else Transfer.p_from_meshes)(meshes[l - 1], M)
             levels.append({"op": Operator(VCycle._flagged(M.desc, flags), M), "n_dofs": M.n_dofs, "transfer": tr})
         return levels
 

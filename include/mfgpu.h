@@ -410,6 +410,35 @@ int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int num
 /* host only: the default matrix of mfgpu_transfer_create_p, [(pf+1) * (pc+1)]; rows of fine nodes that are coarse nodes
  * (the end points; 1/2 when both degrees are even) hold exact zeros and a one                                        */
 int mfgpu_transfer_p_prolongation_1d(int degree_coarse, int degree_fine, double *p1);
+/* The p-transfer on cells with hanging nodes: an active DoFHandler with hanging nodes at two
+ * degrees.  The arguments of mfgpu_transfer_create_p -- both index lists in the description's form, hanging entries
+ * already substituted -- and two more:
+ *   constraint_mask            [n_cells], the mfgpu_desc.constraint_mask of BOTH descriptions (it is geometric, so the same
+ *                              at every degree); NULL: conforming, the object is the one mfgpu_transfer_create_p makes
+ *   coarse_constraint_weights  [(pc+1)^2] row-major, the COARSE description's constraint_weights; NULL: those of FE_Q(pc)
+ * A local position of a cell is CONSTRAINED if resolve_hanging_nodes with the cell's mask can write it (a position on a
+ * flagged face, in 3D also on a flagged edge).  The owner of a fine dof is the first cell, in cell order, that lists it at
+ * a position that is not constrained.  For the owner cell K and owned position i
+ *   (P x)[fine(K, i)] = [ P_loc C_pc(mask_K) gather_K(x with the coarse Dirichlet dofs read as 0) ]_i
+ * with C_pc = resolve_hanging_nodes<NOTRANSPOSE> at degree pc and P_loc the tensor product of prolongation_1d.  The three
+ * calls keep their meaning: prolongate stores (fine dofs no cell lists -- the hanging ones -- become 0), prolongate_add
+ * read-modify-writes (and leaves those alone), restrict_and_add adds Z P^T src with floating-point atomics.  Only
+ * enqueue, as before.
+ * MFGPU_EINVAL, nothing created: what mfgpu_transfer_create_p refuses; a mask with bits outside the 9 defined ones, or in
+ * 2D with one of the 3D bits (TYPE z, FACE z, EDGE); a fine dof that some cell lists but no cell owns (masks and index
+ * lists that do not belong together).                                                                               */
+int mfgpu_transfer_create_p_hn(int dim, int degree_coarse, int degree_fine, int number_type, uint32_t n_cells,
+                               const uint32_t *coarse_cell_dofs /* [n_cells * (pc+1)^dim] */,
+                               const uint32_t *fine_cell_dofs /* [n_cells * (pf+1)^dim] */, uint32_t n_coarse_dofs,
+                               uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                               const double *prolongation_1d /* [(pf+1) * (pc+1)], fine index major, or NULL */,
+                               const uint32_t *constraint_mask /* [n_cells] or NULL */,
+                               const double *coarse_constraint_weights /* [(pc+1)^2] or NULL */, mfgpu_transfer **out);
+/* host only, no device needed: the fine index list as the create calls upload it, bit 31 set on every entry but the
+ * owner's; constraint_mask NULL: the first cell that lists a dof owns it.  MFGPU_EINVAL as above.                     */
+int mfgpu_transfer_p_owner_list(int dim, int degree_fine, uint32_t n_cells, const uint32_t *fine_cell_dofs,
+                                const uint32_t *constraint_mask /* [n_cells] or NULL */, uint32_t n_fine_dofs,
+                                uint32_t *out /* [n_cells * (pf+1)^dim] */);
 
 /* Level operator with refinement edges (laplace_operator_gpu.h:154-186, 306-352): `desc` describes the level mesh with
  * the level's Dirichlet dofs as constrained_dofs (no hanging nodes on a level mesh, :174-176), edge_dofs are the level's
@@ -759,6 +788,10 @@ int mfgpu_transfer_create_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh
  * MFGPU_EINVAL: not the same cells (dimension, kind, cells per direction and slab of a cube, n_ref of a ball, cell
  * count) or degree_coarse >= degree_fine; MFGPU_EUNSUPPORTED: a mesh with hanging nodes (adaptive, from leaves)      */
 int mfgpu_transfer_create_p_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
+/* mfgpu_transfer_create_p_hn for two stand-in meshes: every pair the call above accepts, and adaptive meshes or meshes
+ * from leaves with the same leaves in the same order (then the masks are equal); with the coarse mesh's constraint
+ * weights and constrained dofs.  MFGPU_EINVAL: the cells differ, or degree_coarse >= degree_fine                     */
+int mfgpu_transfer_create_p_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
 /* the index arrays that call hands to mfgpu_transfer_create, on the host (no GPU needed): coarse_cell_dofs
  * [n_cells * (p+1)^dim], fine_patch_dofs [n_cells * (2p+1)^dim], n_cells = the coarse mesh's; returns n_cells     */
 int64_t mfgpu_mesh_transfer_patches(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, uint32_t *coarse_cell_dofs,
