@@ -530,6 +530,176 @@ int mfgpu_mesh_create_from_leaves(int dim, int degree, const uint32_t *leaves, u
   return 0;
 }
 
+// One step of global coarsening.  Every complete family of sibling leaves is replaced by its
+// parent; then, until nothing changes, a new parent is split again where it breaks one-irregularity: where a cell of its
+// own level next to it over a face (3D: or an edge) has a child at the shared face / edge that is itself refined, so a
+// leaf two or more levels finer than the parent touches it.  A rollback only makes the set finer, so it can only force
+// further rollbacks: the fixed point does not depend on the order.
+int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, uint32_t *out) {
+  using namespace mfgpu;
+  const char *who = "mfgpu_mesh_coarsen_leaves";
+  if ((dim != 2 && dim != 3) || !leaves || !out || n_leaves == 0) {
+    set_error(std::string(who) + ": bad argument (dim 2 or 3, arrays, at least one leaf)");
+    return MFGPU_EINVAL;
+  }
+  Tree T;
+  T.dim = dim;
+  const int kMaxLevel = 18;  // ckey's 19 bits per coordinate; dim * level < 64 for the volume sum
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    bool ok = l[0] <= (uint32_t)kMaxLevel;
+    for (int d = 0; d < 3 && ok; ++d) ok = d < dim ? l[1 + d] < (1u << l[0]) : l[1 + d] == 0;
+    if (!ok || !T.active.insert(ckey((int)l[0], l + 1)).second) {
+      set_error(std::string(who) + ": a leaf outside the root cell, deeper than level 18, or listed twice");
+      return MFGPU_EINVAL;
+    }
+    T.max_level = std::max(T.max_level, (int)l[0]);
+  }
+  if (T.max_level == 0) {
+    set_error(std::string(who) + ": the single root cell cannot be coarsened");
+    return MFGPU_EINVAL;
+  }
+  // a partition of the root: no leaf inside another, and the volumes add up
+  uint64_t volume = 0;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    volume += (uint64_t)1 << (dim * (T.max_level - (int)l[0]));
+    uint32_t c[3] = {l[1], l[2], l[3]};
+    for (int ll = (int)l[0] - 1; ll >= 0; --ll) {
+      for (int d = 0; d < dim; ++d) c[d] >>= 1;
+      if (T.is_active(ll, c)) {
+        set_error(std::string(who) + ": the leaves are not a partition (one lies inside another)");
+        return MFGPU_EINVAL;
+      }
+    }
+  }
+  if (volume != (uint64_t)1 << (dim * T.max_level)) {
+    set_error(std::string(who) + ": the leaves are not a partition (they do not cover the root cell)");
+    return MFGPU_EINVAL;
+  }
+  // the offsets to the neighbours over faces and, in 3D, edges
+  std::vector<std::array<int, 3>> offsets;
+  for (int ox = -1; ox <= 1; ++ox)
+    for (int oy = -1; oy <= 1; ++oy)
+      for (int oz = (dim == 3 ? -1 : 0); oz <= (dim == 3 ? 1 : 0); ++oz) {
+        const int nz = (ox != 0) + (oy != 0) + (oz != 0);
+        if (nz == 1 || (dim == 3 && nz == 2)) offsets.push_back({ox, oy, oz});
+      }
+  // one-irregular: no leaf touches a leaf two or more levels coarser over a face or an edge
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    for (const auto &o : offsets) {
+      const int64_t ci[3] = {(int64_t)l[1] + o[0], (int64_t)l[2] + o[1], (int64_t)l[3] + o[2]};
+      const int lv = T.covering_level((int)l[0], ci);
+      if (lv >= 0 && lv < (int)l[0] - 1) {
+        set_error(std::string(who) + ": the leaves are not one-irregular over faces and edges");
+        return MFGPU_EINVAL;
+      }
+    }
+  }
+  // the complete families
+  std::unordered_map<uint64_t, int> n_children;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    if (l[0] == 0) continue;
+    const uint32_t pc[3] = {l[1] >> 1, l[2] >> 1, l[3] >> 1};
+    ++n_children[ckey((int)l[0] - 1, pc)];
+  }
+  auto cell_of = [](uint64_t k) {
+    Cell c;
+    c.level = (int)(k >> 57);
+    c.c[0] = (uint32_t)(k & 0x7ffff);
+    c.c[1] = (uint32_t)((k >> 19) & 0x7ffff);
+    c.c[2] = (uint32_t)((k >> 38) & 0x7ffff);
+    return c;
+  };
+  std::vector<Cell> parents;
+  for (const auto &kv : n_children)
+    if (kv.second == (1 << dim)) parents.push_back(cell_of(kv.first));
+  for (const Cell &P : parents) {
+    for (int k = 0; k < (1 << dim); ++k) {
+      uint32_t c[3] = {0, 0, 0};
+      for (int d = 0; d < dim; ++d) c[d] = 2 * P.c[d] + ((k >> d) & 1);
+      T.active.erase(ckey(P.level + 1, c));
+    }
+    T.active.insert(ckey(P.level, P.c));
+  }
+  // does the coarsened parent P touch a leaf two or more levels finer?
+  auto breaks = [&](const Cell &P) {
+    for (const auto &o : offsets) {
+      int64_t nb[3] = {(int64_t)P.c[0] + o[0], (int64_t)P.c[1] + o[1], (int64_t)P.c[2] + o[2]};
+      if (T.covering_level(P.level, nb) != -1) continue;  // outside, or covered by a leaf of P's level or coarser
+      // the neighbour's children at the shared face / edge: refined themselves?
+      for (int k = 0; k < (1 << dim); ++k) {
+        int64_t ch[3] = {0, 0, 0};
+        bool at = true;
+        for (int d = 0; d < dim; ++d) {
+          const int b = (k >> d) & 1;
+          if ((o[d] == 1 && b != 0) || (o[d] == -1 && b != 1)) at = false;
+          ch[d] = 2 * nb[d] + b;
+        }
+        if (at && T.covering_level(P.level + 1, ch) == -1) return true;
+      }
+    }
+    return false;
+  };
+  for (bool changed = true; changed;) {
+    changed = false;
+    std::vector<Cell> kept;
+    for (const Cell &P : parents) {
+      if (breaks(P)) {
+        T.refine(P);  // back to its children
+        changed = true;
+      } else {
+        kept.push_back(P);
+      }
+    }
+    parents.swap(kept);
+  }
+  std::vector<uint64_t> keys(T.active.begin(), T.active.end());
+  std::sort(keys.begin(), keys.end());
+  for (size_t i = 0; i < keys.size(); ++i) {
+    const Cell c = cell_of(keys[i]);
+    out[4 * i] = (uint32_t)c.level;
+    for (int d = 0; d < 3; ++d) out[4 * i + 1 + d] = c.c[d];
+  }
+  return (int64_t)keys.size();
+}
+
+int mfgpu_mesh_coarsening_map(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, uint32_t *parent, uint32_t *child) {
+  using namespace mfgpu;
+  const char *who = "mfgpu_mesh_coarsening_map";
+  if (!coarse || !fine || !parent || !child) {
+    set_error(std::string(who) + ": null argument");
+    return MFGPU_EINVAL;
+  }
+  const Mesh &C = coarse->mesh, &F = fine->mesh;
+  if (C.dim != F.dim || C.cell_levels.size() != 4 * (size_t)C.n_cells || F.cell_levels.size() != 4 * (size_t)F.n_cells ||
+      C.n_cells == 0 || F.n_cells == 0) {
+    set_error(std::string(who) + ": needs two leaf meshes (adaptive, from leaves) of one dimension");
+    return MFGPU_EINVAL;
+  }
+  std::unordered_map<uint64_t, uint32_t> id;
+  for (uint32_t c = 0; c < C.n_cells; ++c) id[ckey((int)C.cell_levels[4 * c], &C.cell_levels[4 * c + 1])] = c;
+  for (uint32_t f = 0; f < F.n_cells; ++f) {
+    const uint32_t *l = &F.cell_levels[4 * (size_t)f];
+    auto it = id.find(ckey((int)l[0], l + 1));
+    if (it != id.end()) {
+      parent[f] = it->second;
+      child[f] = 0;
+      continue;
+    }
+    const uint32_t pc[3] = {l[1] >> 1, l[2] >> 1, l[3] >> 1};
+    if (l[0] == 0 || (it = id.find(ckey((int)l[0] - 1, pc))) == id.end()) {
+      set_error(std::string(who) + ": a fine leaf is neither a coarse leaf nor the child of one");
+      return MFGPU_EINVAL;
+    }
+    parent[f] = it->second;
+    child[f] = 1 + ((l[1] & 1u) | ((l[2] & 1u) << 1) | ((l[3] & 1u) << 2));
+  }
+  return 0;
+}
+
 int64_t mfgpu_mesh_cell_levels(const mfgpu_mesh *m, const uint32_t **ptr) {
   if (!m || !ptr) return MFGPU_EINVAL;
   *ptr = m->mesh.cell_levels.data();

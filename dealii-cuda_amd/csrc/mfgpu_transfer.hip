@@ -22,7 +22,9 @@
 // One 256-thread workgroup per coarse cell at a time (grid-stride); the three 1D contractions go through LDS.
 // Bound: HBM (one read of the fine vector + index lists); small next to the smoother's operator applies.
 // The same object and entry points also serve the transfer between two DEGREES on one mesh (p-multigrid): created by
-// mfgpu_transfer_create_p, kernels in mfgpu_transfer_p.hip (one wave per cell), dispatched here on t->degree_coarse.
+// mfgpu_transfer_create_p, kernels in mfgpu_transfer_p.hip (one wave per cell), and the transfer between two leaf meshes
+// with hanging nodes (global coarsening): mfgpu_transfer_create_h_hn, kernels in mfgpu_transfer_h.hip.  Dispatched here
+// on t->kind.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -241,14 +243,16 @@ int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src
     return MFGPU_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
+  const bool h = t->kind == TRANSFER_KIND_H;
   if (t->number_type == MFGPU_F64) {
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<double>, dim3(2048), dim3(256), 0, st, (double *)dst_fine, (size_t)t->n_fine_dofs);
-    if (!t->degree_coarse) HIP_TRY((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
+    if (h) HIP_TRY((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
   } else {
     if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst_fine, (size_t)t->n_fine_dofs);
-    if (!t->degree_coarse) HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
+    if (h) HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
   }
-  if (t->degree_coarse) HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE, st));
+  if (t->kind == TRANSFER_KIND_P) HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE, st));
+  if (t->kind == TRANSFER_KIND_H_HN) HIP_TRY(launch_h_hn_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE, st));
   return 0;
 }
 
@@ -259,8 +263,10 @@ int mfgpu_transfer_prolongate_add(mfgpu_transfer *t, void *dst_fine, const void 
     return MFGPU_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (t->degree_coarse)
+  if (t->kind == TRANSFER_KIND_P)
     HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE_ADD, st));
+  else if (t->kind == TRANSFER_KIND_H_HN)
+    HIP_TRY(launch_h_hn_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE_ADD, st));
   else if (t->number_type == MFGPU_F64)
     HIP_TRY((launch<double, false, true>(t, (double *)dst_fine, (const double *)src_coarse, st)));
   else
@@ -275,8 +281,10 @@ int mfgpu_transfer_restrict_and_add(mfgpu_transfer *t, void *dst_coarse, const v
     return MFGPU_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (t->degree_coarse)
+  if (t->kind == TRANSFER_KIND_P)
     HIP_TRY(launch_p_transfer(t, dst_coarse, src_fine, TRANSFER_RESTRICT_ADD, st));
+  else if (t->kind == TRANSFER_KIND_H_HN)
+    HIP_TRY(launch_h_hn_transfer(t, dst_coarse, src_fine, TRANSFER_RESTRICT_ADD, st));
   else if (t->number_type == MFGPU_F64)
     HIP_TRY((launch<double, true>(t, (double *)dst_coarse, (const double *)src_fine, st)));
   else

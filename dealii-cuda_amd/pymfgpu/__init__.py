@@ -130,6 +130,8 @@ SYMBOLS = [
     "mfgpu_spd_inverse_enqueue", "mfgpu_vcycle_refresh", "mfgpu_vcycle_refresh_status", "mfgpu_estimate_lambda_max_steps",
     "mfgpu_transfer_create_p", "mfgpu_transfer_create_p_from_meshes", "mfgpu_transfer_p_prolongation_1d",
     "mfgpu_transfer_create_p_hn", "mfgpu_transfer_create_p_hn_from_meshes", "mfgpu_transfer_p_owner_list",
+    "mfgpu_mesh_coarsen_leaves", "mfgpu_mesh_coarsening_map", "mfgpu_transfer_create_h_hn",
+    "mfgpu_transfer_create_h_hn_from_meshes",
 ]
 
 _lib = None
@@ -303,6 +305,12 @@ def lib():
         L.mfgpu_transfer_create_p_hn.argtypes = [i, i, i, i, u32, vp, vp, u32, u32, vp, u32, vp, vp, vp, C.POINTER(vp)]
         L.mfgpu_transfer_create_p_hn_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
         L.mfgpu_transfer_p_owner_list.argtypes = [i, i, u32, vp, vp, u32, vp]
+        L.mfgpu_mesh_coarsen_leaves.argtypes = [i, vp, u32, vp]
+        L.mfgpu_mesh_coarsen_leaves.restype = C.c_int64
+        L.mfgpu_mesh_coarsening_map.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_transfer_create_h_hn.argtypes = [i, i, i, u32, u32, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp,
+                                                 C.POINTER(vp)]
+        L.mfgpu_transfer_create_h_hn_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
         _lib = L
     return _lib
 
@@ -368,6 +376,37 @@ class Mesh:
         h = C.c_void_p()
         _check(lib().mfgpu_mesh_create_from_leaves(dim, degree, lv.ctypes.data, len(lv), number_type, C.byref(h)))
         return cls(h)
+
+    @staticmethod
+    def coarsen_leaves(dim, leaves):
+        """one step of global coarsening of the leaves (level, cx, cy, cz) (mfgpu_mesh_coarsen_leaves): complete families
+        become their parent unless that breaks one-irregularity; [n_coarse, 4]; host only"""
+        lv = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 4)
+        out = np.zeros((max(len(lv), 1), 4), dtype=np.uint32)
+        n = lib().mfgpu_mesh_coarsen_leaves(dim, lv.ctypes.data if len(lv) else None, len(lv), out.ctypes.data)
+        if n < 0:
+            _check(int(n))
+        return out[:n].copy()
+
+    @classmethod
+    def coarsening_sequence(cls, mesh, degree=None, min_cells=None):
+        """the meshes of global coarsening, coarse to fine (deal.II's create_geometric_coarsening_sequence): the leaves of
+        `mesh` coarsened step by step while a step leaves at least min_cells (default 2^dim) cells, each a
+        Mesh.from_leaves at `degree` (default: the mesh's) in the mesh's number type; the last one is `mesh` itself when
+        `degree` is its own"""
+        dim, p, nt = int(mesh.desc.dim), int(mesh.desc.degree), int(mesh.desc.number_type)
+        degree = p if degree is None else int(degree)
+        min_cells = 2 ** dim if min_cells is None else int(min_cells)
+        leaves = mesh.cell_levels()
+        if not len(leaves):
+            raise MfgpuError("Mesh.coarsening_sequence: needs a leaf mesh (Mesh.adaptive, Mesh.adaptive_mg, Mesh.from_leaves)")
+        out = [mesh if degree == p else cls.from_leaves(dim, degree, leaves, number_type=nt)]
+        while len(leaves) > 1:
+            leaves = cls.coarsen_leaves(dim, leaves)
+            if len(leaves) < min_cells:
+                break
+            out.append(cls.from_leaves(dim, degree, leaves, number_type=nt))
+        return out[::-1]
 
     def cell_levels(self):
         p = C.c_void_p()
@@ -1043,6 +1082,41 @@ class Transfer:
         _check(lib().mfgpu_transfer_create_p_hn_from_meshes(coarse._h, fine._h, C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def h_hn_from_arrays(cls, dim, degree, coarse_cell_dofs, fine_cell_dofs, parent, child, n_coarse_dofs, n_fine_dofs,
+                         coarse_dirichlet, number_type=F64, prolongation_1d=None, coarse_mask=None, fine_mask=None,
+                         constraint_weights=None):
+        """the global-coarsening h-transfer between two meshes with hanging nodes at one degree
+        (mfgpu_transfer_create_h_hn): the two descriptions' loc2glob, per fine cell its coarse cell `parent` and `child`
+        (0: the same cell, 1 + k: child k), the two descriptions' constraint masks (None: none)"""
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)  # noqa: E731
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        cd, fd, pa, ch, di = u32(coarse_cell_dofs), u32(fine_cell_dofs), u32(parent), u32(child), u32(coarse_dirichlet)
+        p1, w = f64(prolongation_1d), f64(constraint_weights)
+        cm = None if coarse_mask is None else u32(coarse_mask)
+        fm = None if fine_mask is None else u32(fine_mask)
+        nd = (max(int(degree), 0) + 1) ** dim
+        n_coarse, n_fine = cd.size // nd, fd.size // nd
+        if 1 <= degree <= 6 and dim in (2, 3):  # (anything else is the library's MFGPU_EINVAL)
+            assert cd.size == n_coarse * nd and fd.size == n_fine * nd and pa.size == n_fine and ch.size == n_fine
+            assert p1 is None or p1.size == (2 * degree + 1) * (degree + 1)
+            assert (cm is None or cm.size == n_coarse) and (fm is None or fm.size == n_fine)
+            assert w is None or w.size == (degree + 1) ** 2
+        ptr = lambda a: None if a is None or not a.size else a.ctypes.data  # noqa: E731
+        h = C.c_void_p()
+        _check(lib().mfgpu_transfer_create_h_hn(dim, degree, number_type, n_coarse, n_fine, ptr(cd), ptr(fd), ptr(pa), ptr(ch),
+                                                n_coarse_dofs, n_fine_dofs, ptr(di), di.size, ptr(p1), ptr(cm), ptr(fm),
+                                                ptr(w), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def h_hn_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
+        """mfgpu_transfer_create_h_hn_from_meshes: two leaf meshes of equal degree, the fine one's leaves those of the
+        coarse one or their children (a mesh and a member of its Mesh.coarsening_sequence)"""
+        h = C.c_void_p()
+        _check(lib().mfgpu_transfer_create_h_hn_from_meshes(coarse._h, fine._h, C.byref(h)))
+        return cls(h)
+
     def prolongate(self, dst_fine, src_coarse, stream=None):
         _check(lib().mfgpu_transfer_prolongate(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
 
@@ -1082,6 +1156,14 @@ def p_owner_list(dim, degree_fine, fine_cell_dofs, n_fine_dofs, constraint_mask=
     _check(lib().mfgpu_transfer_p_owner_list(dim, int(degree_fine), n_cells, fd.ctypes.data if fd.size else None,
                                              None if cm is None else cm.ctypes.data, n_fine_dofs, out.ctypes.data))
     return out
+
+
+def coarsening_map(coarse: "Mesh", fine: "Mesh"):
+    """(parent, child) [n_fine_cells] each of two leaf meshes (mfgpu_mesh_coarsening_map): the coarse cell of every fine
+    cell and 0 (the same cell) or 1 + k (child k of it; bit d of k: the upper half in direction d); host only"""
+    parent, child = np.zeros(fine.n_cells, dtype=np.uint32), np.zeros(fine.n_cells, dtype=np.uint32)
+    _check(lib().mfgpu_mesh_coarsening_map(coarse._h, fine._h, parent.ctypes.data, child.ctypes.data))
+    return parent, child
 
 
 def _ptr(v):
@@ -1338,7 +1420,10 @@ class VCycle:
                     raise MfgpuError(f"VCycle.level_mesh_levels: the degree falls from {pc} to {pf} between levels "
                                      f"{l - 1} and {l}")
                 masked = bool(meshes[l - 1].desc.constraint_mask) or bool(M.desc.constraint_mask)
-                if pc == pf:
+                leaf = len(meshes[l - 1].cell_levels()) > 0 or len(M.cell_levels()) > 0  # (cells_kind == -1)
+                if pc == pf and (masked or leaf):
+                    tr = Transfer.h_hn_from_meshes(meshes[l - 1], M)  # global coarsening: two leaf meshes
+                elif pc == pf:
                     tr = Transfer.from_meshes(meshes[l - 1], M)
                 else:
                     tr = (Transfer.p_hn_from_meshes if masked else Transfer.p_from_meshes)(meshes[l - 1], M)
@@ -1352,6 +1437,23 @@ class VCycle:
         nt = int(meshes[0].desc.number_type)
         return cls(cls.level_mesh_levels(meshes, flags), nt if active_type is None else active_type, meshes[-1].n_dofs,
                    keep=list(meshes), **options)
+
+    @classmethod
+    def from_global_coarsening(cls, mesh: "Mesh", degrees=None, active_type=None, flags=0, min_cells=None, **options):
+        """global-coarsening multigrid on ONE leaf mesh with hanging nodes (Mesh.adaptive, Mesh.from_leaves): from_level_meshes
+        over Mesh.coarsening_sequence(mesh) at the lowest degree followed by `mesh`'s cells at the rising `degrees` (None: the
+        mesh's degree throughout; the last one must be the mesh's).  Every level is a complete mesh: no edges, no pairs"""
+        p = int(mesh.desc.degree)
+        degrees = (p,) if degrees is None else tuple(int(d) for d in degrees)
+        if degrees[-1] != p or any(a >= b for a, b in zip(degrees, degrees[1:])):
+            raise MfgpuError(f"VCycle.from_global_coarsening: degrees {degrees} must rise and end at the mesh's degree {p}")
+        dim, nt = int(mesh.desc.dim), int(mesh.desc.number_type)
+        meshes = Mesh.coarsening_sequence(mesh, degrees[0], min_cells)
+        leaves = mesh.cell_levels()
+        meshes += [Mesh.from_leaves(dim, d, leaves, number_type=nt) for d in degrees[1:-1]]
+        if len(degrees) > 1:
+            meshes.append(mesh)
+        return cls.from_level_meshes(meshes, active_type, flags, **options)
 
     def apply(self, z, r, stream=None, check=True):
         """z = M^-1 r on active vectors (enqueued on `stream`)"""

@@ -439,6 +439,38 @@ int mfgpu_transfer_create_p_hn(int dim, int degree_coarse, int degree_fine, int 
 int mfgpu_transfer_p_owner_list(int dim, int degree_fine, uint32_t n_cells, const uint32_t *fine_cell_dofs,
                                 const uint32_t *constraint_mask /* [n_cells] or NULL */, uint32_t n_fine_dofs,
                                 uint32_t *out /* [n_cells * (pf+1)^dim] */);
+/* ---- global-coarsening multigrid: the h-transfer between two ACTIVE meshes with hanging nodes at
+ * one degree, the fine mesh's cells each a cell of the coarse mesh (child = 0) or child k of one (child = 1 + k, bit d of
+ * k: the upper half in direction d) -- two members of deal.II's create_geometric_coarsening_sequence, what
+ * MGTransferGlobalCoarsening transfers between.  Every level is a complete mesh served by an ordinary
+ * mfgpu_handle: no refinement edges, no interface matrices, no copy pairs.  Both index lists are in the description's
+ * form, hanging entries already substituted; parent [n_fine_cells] is the coarse cell's index.
+ *   prolongation_1d     [(2p+1) * (p+1)] as for mfgpu_transfer_create (rows 0..p: the lower child, rows p..2p: the upper
+ *                       one), or NULL
+ *   coarse_mask         [n_coarse_cells], the coarse description's constraint_mask, or NULL (no hanging nodes there)
+ *   fine_mask           [n_fine_cells], the fine description's, or NULL
+ *   constraint_weights  [(p+1)^2] row-major, or NULL: those of FE_Q(p)
+ * Section 19's semantics with two masks.  The owner of a fine dof is the first fine cell that lists it at a position its
+ * FINE mask does not constrain (mfgpu_transfer_p_owner_list with the fine mask).  For the owner F with parent K
+ *   (P x)[fine(F, i)] = [ E(child_F) C_p(coarse_mask_K) gather_K(x with the coarse Dirichlet dofs read as 0) ]_i
+ * E the tensor product of the halves of prolongation_1d that `child` selects, the identity for child = 0 (such a cell
+ * passes its values through bit for bit when its coarse mask is 0; it may carry a coarse mask it does not have in the
+ * fine mesh, because its neighbour was coarsened).  prolongate stores (fine dofs no cell lists become 0), prolongate_add
+ * read-modify-writes (and leaves them alone), neither with atomics; restrict_and_add is the exact transpose and adds with
+ * floating-point atomics, skipping the coarse Dirichlet dofs.  All three only enqueue.  The object is an mfgpu_transfer:
+ * memory_consumption, destroy and mfgpu_vcycle_create take it unchanged, and it mixes with the p-transfer in one V-cycle
+ * (coarsened meshes at degree 1, then 1 -> 2 -> 4 on the active mesh).
+ * MFGPU_EINVAL, nothing created: what mfgpu_transfer_create_p_hn refuses, where it applies; a parent out of range; a
+ * child > 2^dim; a fine dof that is listed but owned by nobody.                                                      */
+int mfgpu_transfer_create_h_hn(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
+                               const uint32_t *coarse_cell_dofs /* [n_coarse_cells * (p+1)^dim] */,
+                               const uint32_t *fine_cell_dofs /* [n_fine_cells * (p+1)^dim] */,
+                               const uint32_t *parent /* [n_fine_cells] */, const uint32_t *child /* [n_fine_cells] */,
+                               uint32_t n_coarse_dofs, uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet,
+                               uint32_t n_coarse_dirichlet, const double *prolongation_1d /* [(2p+1) * (p+1)] or NULL */,
+                               const uint32_t *coarse_mask /* [n_coarse_cells] or NULL */,
+                               const uint32_t *fine_mask /* [n_fine_cells] or NULL */,
+                               const double *constraint_weights /* [(p+1)^2] or NULL */, mfgpu_transfer **out);
 
 /* Level operator with refinement edges (laplace_operator_gpu.h:154-186, 306-352): `desc` describes the level mesh with
  * the level's Dirichlet dofs as constrained_dofs (no hanging nodes on a level mesh, :174-176), edge_dofs are the level's
@@ -821,6 +853,23 @@ int mfgpu_mesh_create_from_leaves(int dim, int degree, const uint32_t *leaves, u
                                   int number_type, mfgpu_mesh **out);
 /* (level, cx, cy, cz) of every cell in mesh order [n_cells*4]; empty for uniform meshes */
 int64_t mfgpu_mesh_cell_levels(const mfgpu_mesh *m, const uint32_t **ptr);
+/* ---- global coarsening (host only).  One coarsening step of a set of leaves (level, cx, cy, cz) as
+ * for mfgpu_mesh_create_from_leaves, what one step of create_geometric_coarsening_sequence does to a triangulation: every
+ * complete family of sibling leaves (all 2^dim children active) is replaced by its parent; then, until nothing changes,
+ * a new parent is split again where it breaks one-irregularity (a leaf two or more levels finer than it touches it over
+ * a face or, in 3D, an edge).  The result is one-irregular and does not depend on the order.  Returns the number of coarse
+ * leaves written to out [room for n_leaves * 4]; MFGPU_EINVAL for a set that is not one-irregular, is not a partition
+ * of the root cell, or is the single root cell.                                                                      */
+int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, uint32_t *out /* [n_leaves * 4] */);
+/* the map between two leaf meshes (adaptive, from leaves), found from their cell_levels: for every fine cell the index
+ * of its coarse cell and child = 0 (the same cell) or 1 + k (child k of it; bit d of k: the upper half in direction d).
+ * MFGPU_EINVAL: the meshes differ in dim, or some fine leaf is neither a coarse leaf nor the child of one              */
+int mfgpu_mesh_coarsening_map(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, uint32_t *parent /* [n_fine_cells] */,
+                              uint32_t *child /* [n_fine_cells] */);
+/* mfgpu_transfer_create_h_hn for two leaf meshes of equal degree, the fine one's leaves those of the coarse one or their
+ * children (mfgpu_mesh_coarsening_map), in the fine mesh's number type, with the coarse mesh's constrained dofs and
+ * constraint weights.  MFGPU_EINVAL: not two leaf meshes, the degrees or dimensions differ, no map                    */
+int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
 void mfgpu_mesh_destroy(mfgpu_mesh *m);
 /* fills *desc with pointers into the mesh (valid until mfgpu_mesh_destroy) */
 int mfgpu_mesh_desc(const mfgpu_mesh *m, mfgpu_desc *desc);
