@@ -1425,8 +1425,8 @@ class VCycle:
                     tr = Transfer.h_hn_from_meshes(meshes[l - 1], M)  # global coarsening: two leaf meshes
                 elif pc == pf:
                     tr = Transfer.from_meshes(meshes[l - 1], M)
-                else:
-                    tr = (Transfer.p_hn_from_meshes if masked else Transfer.p_from_meshes)(meshes[l - 1], M)
+                else:  # (a leaf mesh without a hanging node has no mask, and p_from_meshes refuses leaf meshes)
+                    tr = (Transfer.p_hn_from_meshes if masked or leaf else Transfer.p_from_meshes)(meshes[l - 1], M)
             levels.append({"op": Operator(VCycle._flagged(M.desc, flags), M), "n_dofs": M.n_dofs, "transfer": tr})
         return levels
 
