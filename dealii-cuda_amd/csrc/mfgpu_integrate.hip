@@ -11,6 +11,9 @@
 //          local index, ascending), constrained and unreferenced dofs 0.  No atomics: bitwise repeatable.
 //   error: cell kernel -> squared cell errors -> the two-stage fixed-order reduction of mfgpu_vec_dot.
 //   evaluate: cell kernel -> values and real-space gradients of a field at the quadrature points, cell-major.
+//   recovery indicator: nodal kernel (cell gradients as nodal coefficients, times |K|, to per-cell local buffers) ->
+//          per-dof gather over a second CSR (unconstrained positions, Dirichlet dofs included), divided by the resident
+//          denominator -> cell kernel (recovered minus cell gradient, integrated).  No atomics either.
 // Geometry at the (p+2)^dim error points is interpolated from the description's QGauss(p+1) points with the 1D Lagrange
 // basis on those points (values and derivatives): exact for mappings of degree <= p per direction (affine cells,
 // MappingQ1, i.e. all mesh stand-ins).
@@ -435,6 +438,196 @@ __global__ void __launch_bounds__(64) evaluate_cell_kernel(IntArgs a) {
   }
 }
 
+// ---- gradient-recovery indicator (include/mfgpu.h, mfgpu_integrator_recovery_indicator)
+struct IndArgs {
+  const uint32_t *loc2glob, *cmask;
+  const double *tab;     // Tab<N>
+  const double *sinv;    // [i][q] inverse of Tab<N>::SE
+  const double *jxw;     // [n_cells * N^dim]
+  const double *jinv;    // as IntArgs::jinv
+  const double *vol;     // [n_cells] |K|
+  const double *u;       // [n_dofs]
+  const double *weight;  // [n_cells * N^dim] or nullptr
+  double *local;         // dim buffers [n_cells * N^dim], component k at k * local_stride
+  double *nodal;         // dim vectors [n_dofs], component k at k * n_dofs
+  double *per_cell;      // [n_cells]
+  size_t local_stride;
+  uint32_t n_dofs;
+  int general;
+};
+
+// A = u at the cell's nodes (gathered, hanging-node interpolated); G[e * ND + q] = component e of the real-space
+// gradient at quadrature point q, by the steps of evaluate_cell_kernel
+template <int dim, int N>
+__device__ __forceinline__ void cell_gradient(const IndArgs &a, uint32_t c, unsigned mask, const double *tab, double *A,
+                                              double *G, double *T1, double *T2) {
+  constexpr int ND = cpow(N, dim);
+  using TB = Tab<N>;
+  const size_t c0 = (size_t)c * ND;
+  for (int i = threadIdx.x; i < ND; i += 64) A[i] = a.u[a.loc2glob[c0 + i]];
+  if (mask) hn_resolve<dim, N, false>(A, mask, tab + TB::W);
+  const double *S = tab + TB::SE, *D = tab + TB::GE;
+#pragma unroll
+  for (int e = 0; e < dim; ++e) tensor<dim, N, N>(A, G + e * ND, e == 0 ? D : S, e == 1 ? D : S, e == 2 ? D : S, T1, T2);
+  const double j0 = a.general ? 0.0 : a.jinv[c];
+  for (int q = threadIdx.x; q < ND; q += 64) {  // the thread owns point q: in place
+    double g[dim], r[dim];
+#pragma unroll
+    for (int e = 0; e < dim; ++e) g[e] = G[e * ND + q];
+    if (!a.general) {
+#pragma unroll
+      for (int k = 0; k < dim; ++k) r[k] = j0 * g[k];
+    } else {
+      const double *J = a.jinv + (c0 + q) * (dim * dim);  // J^-1[e][k] = d xi_e / d x_k
+#pragma unroll
+      for (int k = 0; k < dim; ++k) {
+        double s = 0;
+#pragma unroll
+        for (int e = 0; e < dim; ++e) s = fma(J[e * dim + k], g[e], s);
+        r[k] = s;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < dim; ++k) G[k * ND + q] = r[k];
+  }
+  __syncthreads();
+}
+
+// step a and the products of step b: local[k][cell][i] = |K| g_K,i of component k.  Entries at constrained positions
+// are written like the others; the gather's index list leaves them out.
+template <int dim, int N>
+__global__ void __launch_bounds__(64) indicator_nodal_kernel(IndArgs a) {
+  constexpr int ND = cpow(N, dim);
+  using TB = Tab<N>;
+  __shared__ double tab[TB::size], SINV[N * N], A[ND], G[dim * ND], TO[ND], T1[ND], T2[ND];
+  const uint32_t c = blockIdx.x;
+  const size_t c0 = (size_t)c * ND;
+  load_tab<N>(tab, a.tab);
+  for (int i = threadIdx.x; i < N * N; i += 64) SINV[i] = a.sinv[i];
+  const unsigned mask = a.cmask ? a.cmask[c] : 0u;
+  cell_gradient<dim, N>(a, c, mask, tab, A, G, T1, T2);
+  const double vol = a.vol[c];
+#pragma unroll
+  for (int k = 0; k < dim; ++k) {
+    tensor<dim, N, N>(G + k * ND, TO, SINV, SINV, SINV, T1, T2);
+    for (int i = threadIdx.x; i < ND; i += 64) a.local[k * a.local_stride + c0 + i] = vol * TO[i];
+  }
+}
+
+// step b: nodal[k][dof] = (sum of the dof's local entries of component k, ascending (cell, local index)) / den[dof];
+// 0 for a dof without entries
+__global__ void __launch_bounds__(256) indicator_gather_kernel(double *__restrict__ nodal, const double *__restrict__ local,
+                                                               const double *__restrict__ den,
+                                                               const uint32_t *__restrict__ off,
+                                                               const uint32_t *__restrict__ idx, uint32_t n_dofs,
+                                                               size_t local_stride) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_dofs) return;
+  const uint32_t b = off[i], e = off[i + 1];
+  const double *l = local + blockIdx.y * local_stride;
+  double s = 0;
+  for (uint32_t j = b; j < e; ++j) s += l[idx[j]];
+  nodal[(size_t)blockIdx.y * n_dofs + i] = e > b ? s / den[i] : 0.0;
+}
+
+// step c: per_cell[cell] = sum_q weight_q |G(x_q) - grad u_h(x_q)|^2 JxW_q
+template <int dim, int N>
+__global__ void __launch_bounds__(64) indicator_cell_kernel(IndArgs a) {
+  constexpr int ND = cpow(N, dim);
+  using TB = Tab<N>;
+  __shared__ double tab[TB::size], A[ND], G[dim * ND], B[ND], V[ND], T1[ND], T2[ND];
+  const uint32_t c = blockIdx.x;
+  const size_t c0 = (size_t)c * ND;
+  load_tab<N>(tab, a.tab);
+  const unsigned mask = a.cmask ? a.cmask[c] : 0u;
+  cell_gradient<dim, N>(a, c, mask, tab, A, G, T1, T2);
+  const double *S = tab + TB::SE;
+#pragma unroll
+  for (int k = 0; k < dim; ++k) {
+    for (int i = threadIdx.x; i < ND; i += 64) B[i] = a.nodal[(size_t)k * a.n_dofs + a.loc2glob[c0 + i]];
+    if (mask) hn_resolve<dim, N, false>(B, mask, tab + TB::W);
+    tensor<dim, N, N>(B, V, S, S, S, T1, T2);
+    for (int q = threadIdx.x; q < ND; q += 64) {  // the thread owns point q
+      const double diff = V[q] - G[k * ND + q];
+      G[k * ND + q] = diff * diff;
+    }
+  }
+  double acc = 0;
+  for (int q = threadIdx.x; q < ND; q += 64) {
+    double s = G[q];
+#pragma unroll
+    for (int k = 1; k < dim; ++k) s += G[k * ND + q];
+    const double w = a.weight ? a.weight[c0 + q] * a.jxw[c0 + q] : a.jxw[c0 + q];
+    acc += s * w;
+  }
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) a.per_cell[c] = acc;
+}
+
+template <int dim, int N>
+hipError_t launch_indicator_dn(bool nodal, const IndArgs &a, uint32_t n_cells, hipStream_t st) {
+  if (nodal) hipLaunchKernelGGL((indicator_nodal_kernel<dim, N>), dim3(n_cells), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL((indicator_cell_kernel<dim, N>), dim3(n_cells), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_indicator(int dim, int n, bool nodal, const IndArgs &a, uint32_t n_cells, hipStream_t st) {
+#define CASE(N)                                                                                                      \
+  case N:                                                                                                            \
+    return dim == 2 ? launch_indicator_dn<2, N>(nodal, a, n_cells, st) : launch_indicator_dn<3, N>(nodal, a, n_cells, st);
+  switch (n) {
+    CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7)
+    default: return hipErrorInvalidValue;
+  }
+#undef CASE
+}
+
+// inverse of the n x n row-major matrix m, Gauss-Jordan with partial pivoting in long double; false if singular
+bool invert_table(int n, const double *m, std::vector<double> &inv) {
+  std::vector<long double> a((size_t)n * 2 * n, 0.0L);
+  for (int r = 0; r < n; ++r) {
+    for (int c = 0; c < n; ++c) a[r * 2 * n + c] = m[r * n + c];
+    a[r * 2 * n + n + r] = 1.0L;
+  }
+  for (int k = 0; k < n; ++k) {
+    int piv = k;
+    for (int r = k + 1; r < n; ++r)
+      if (fabsl(a[r * 2 * n + k]) > fabsl(a[piv * 2 * n + k])) piv = r;
+    if (a[piv * 2 * n + k] == 0.0L) return false;
+    if (piv != k)
+      for (int c = 0; c < 2 * n; ++c) std::swap(a[k * 2 * n + c], a[piv * 2 * n + c]);
+    const long double d = a[k * 2 * n + k];
+    for (int c = 0; c < 2 * n; ++c) a[k * 2 * n + c] /= d;
+    for (int r = 0; r < n; ++r) {
+      if (r == k) continue;
+      const long double f = a[r * 2 * n + k];
+      if (f == 0.0L) continue;
+      for (int c = 0; c < 2 * n; ++c) a[r * 2 * n + c] -= f * a[k * 2 * n + c];
+    }
+  }
+  inv.assign((size_t)n * n, 0.0);
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c < n; ++c) inv[r * n + c] = (double)a[r * 2 * n + n + c];
+  return true;
+}
+
+// is local position i of a cell with this constraint mask on a constrained face or (3D) edge?  (mfgpu_cell.h hn_flag2 /
+// hn_flag3: the union of the pencils hn_resolve rewrites)
+bool constrained_position(int dim, int n, unsigned mask, int i) {
+  if (!mask) return false;
+  const int p = n - 1, ix[3] = {i % n, (i / n) % n, dim == 3 ? i / (n * n) : 0};
+  bool at[3];
+  for (int d = 0; d < 3; ++d) at[d] = ix[d] == ((mask & (1u << d)) ? 0 : p);
+  for (int d = 0; d < dim; ++d)
+    if ((mask & (1u << (3 + d))) && at[d]) return true;
+  if (dim == 3) {
+    const unsigned EDGE[3] = {1u << 7, 1u << 8, 1u << 6};  // along x, y, z
+    for (int e = 0; e < 3; ++e)
+      if ((mask & EDGE[e]) && at[(e + 1) % 3] && at[(e + 2) % 3]) return true;
+  }
+  return false;
+}
+
 enum Which { RHS, L2, POINTS, EVAL };
 
 template <int dim, int N>
@@ -515,6 +708,10 @@ struct mfgpu_integrator {
   // mfgpu_integrator_update_coefficients and the gradients of mfgpu_integrator_evaluate read (JxW: d_jxw)
   bool updatable = false;
   FoldGeometry geo;
+  // mfgpu_integrator_recovery_indicator (updatable integrators): the inverse 1D table, |K|, the CSR over unconstrained
+  // positions and the denominator from creation; the local buffers and nodal vectors from the first call
+  DeviceArray<uint32_t> d_ind_off, d_ind_idx;
+  DeviceArray<double> d_sinv, d_vol, d_den, d_ind_local, d_ind_nodal;
 };
 
 void mfgpu_integrator_destroy(mfgpu_integrator *it) { delete it; }
@@ -587,6 +784,34 @@ static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
   if ((rc = fold_coefficient<double>(it->d_metric, d.coefficient, d.quadrature_points, in))) return rc;
   if (d.mass_coefficient && (rc = fold_mass<double>(it->d_mass, d.mass_coefficient, in))) return rc;
   if (it->updatable) it->geo = std::move(geo);
+  if (it->updatable) {
+    std::vector<double> se, sinv;  // [q][i] = phi_i(x_q) and its inverse
+    for (int q = 0; q < n; ++q)
+      for (int i = 0; i < n; ++i) se.push_back(sv[i * n + q]);
+    if (!invert_table(n, se.data(), sinv)) {
+      set_error("mfgpu_integrator: shape_values is singular");
+      return MFGPU_EINVAL;
+    }
+    std::vector<double> vol(nc, 0.0), den(d.n_dofs, 0.0);
+    for (size_t c = 0; c < nc; ++c)
+      for (size_t q = 0; q < nd; ++q) vol[c] += ((const double *)d.JxW)[c * nd + q];
+    std::vector<uint32_t> ioff(d.n_dofs + 1, 0);
+    auto listed = [&](size_t j) { return !hn || !constrained_position(dim, n, d.constraint_mask[j / nd], (int)(j % nd)); };
+    for (size_t j = 0; j < nc * nd; ++j)
+      if (listed(j)) ++ioff[d.loc2glob[j] + 1];
+    for (uint32_t i = 0; i < d.n_dofs; ++i) ioff[i + 1] += ioff[i];
+    std::vector<uint32_t> iidx(ioff[d.n_dofs]), ipos(ioff.begin(), ioff.end() - 1);
+    for (size_t j = 0; j < nc * nd; ++j)
+      if (listed(j)) {
+        iidx[ipos[d.loc2glob[j]]++] = (uint32_t)j;
+        den[d.loc2glob[j]] += vol[j / nd];
+      }
+    if ((rc = it->d_sinv.upload(sinv.data(), sinv.size()))) return rc;
+    if ((rc = it->d_vol.upload(vol.data(), vol.size()))) return rc;
+    if ((rc = it->d_den.upload(den.data(), den.size()))) return rc;
+    if ((rc = it->d_ind_off.upload(ioff.data(), ioff.size()))) return rc;
+    if ((rc = it->d_ind_idx.upload(iidx.data(), iidx.size()))) return rc;
+  }
   return 0;
 }
 
@@ -744,5 +969,46 @@ int mfgpu_integrator_evaluate(mfgpu_integrator *it, const void *u, void *values_
   a.values = (double *)values_qp;
   a.grads = (double *)gradients_qp;
   HIP_TRY(launch(it->dim, it->n, EVAL, a, (hipStream_t)stream));
+  return 0;
+}
+
+int mfgpu_integrator_recovery_indicator(mfgpu_integrator *it, const void *u, const void *weight_qp, void *per_cell,
+                                        void *stream) {
+  if (!it || !u || !per_cell) {
+    set_error("null argument");
+    return MFGPU_EINVAL;
+  }
+  if (!it->updatable) {
+    set_error("mfgpu_integrator_recovery_indicator: gradients need inv_jac on the device; create the integrator with "
+              "MFGPU_UPDATABLE_COEFFICIENTS");
+    return MFGPU_EINVAL;
+  }
+  const size_t local_stride = (size_t)it->n_cells * (size_t)ipow(it->n, it->dim);
+  int rc;
+  if (!it->d_ind_local.get() && (rc = it->d_ind_local.alloc(local_stride * it->dim))) return rc;
+  if (!it->d_ind_nodal.get() && (rc = it->d_ind_nodal.alloc((size_t)it->n_dofs * it->dim))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  IndArgs a{};
+  a.loc2glob = it->d_l2g.get();
+  a.cmask = it->d_cmask.get();
+  a.tab = it->d_tab.get();
+  a.sinv = it->d_sinv.get();
+  a.jxw = it->d_jxw.get();
+  a.jinv = it->geo.jinv.as<const double>();
+  a.vol = it->d_vol.get();
+  a.u = (const double *)u;
+  a.weight = (const double *)weight_qp;
+  a.local = it->d_ind_local.get();
+  a.nodal = it->d_ind_nodal.get();
+  a.per_cell = (double *)per_cell;
+  a.local_stride = local_stride;
+  a.n_dofs = it->n_dofs;
+  a.general = it->general ? 1 : 0;
+  HIP_TRY(launch_indicator(it->dim, it->n, true, a, it->n_cells, st));
+  hipLaunchKernelGGL(indicator_gather_kernel, dim3((it->n_dofs + 255) / 256, it->dim), dim3(256), 0, st, a.nodal,
+                     (const double *)a.local, (const double *)it->d_den.get(), it->d_ind_off.get(), it->d_ind_idx.get(),
+                     it->n_dofs, local_stride);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_indicator(it->dim, it->n, false, a, it->n_cells, st));
   return 0;
 }

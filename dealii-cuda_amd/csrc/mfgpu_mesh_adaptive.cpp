@@ -530,19 +530,37 @@ int mfgpu_mesh_create_from_leaves(int dim, int degree, const uint32_t *leaves, u
   return 0;
 }
 
-// One step of global coarsening (DESIGN.md section 20).  Every complete family of sibling leaves is replaced by its
-// parent; then, until nothing changes, a new parent is split again where it breaks one-irregularity: where a cell of its
-// own level next to it over a face (3D: or an edge) has a child at the shared face / edge that is itself refined, so a
-// leaf two or more levels finer than the parent touches it.  A rollback only makes the set finer, so it can only force
-// further rollbacks: the fixed point does not depend on the order.
-int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, uint32_t *out) {
-  using namespace mfgpu;
-  const char *who = "mfgpu_mesh_coarsen_leaves";
-  if ((dim != 2 && dim != 3) || !leaves || !out || n_leaves == 0) {
-    set_error(std::string(who) + ": bad argument (dim 2 or 3, arrays, at least one leaf)");
-    return MFGPU_EINVAL;
+// the offsets to the neighbours of a cell over faces and, in 3D, edges; with `vertices` over vertices too
+static std::vector<std::array<int, 3>> neighbour_offsets(int dim, bool vertices) {
+  std::vector<std::array<int, 3>> offsets;
+  for (int ox = -1; ox <= 1; ++ox)
+    for (int oy = -1; oy <= 1; ++oy)
+      for (int oz = (dim == 3 ? -1 : 0); oz <= (dim == 3 ? 1 : 0); ++oz) {
+        const int nz = (ox != 0) + (oy != 0) + (oz != 0);
+        if (nz != 0 && (nz < dim || vertices)) offsets.push_back({ox, oy, oz});
+      }
+  return offsets;
+}
+
+// one-irregular: no leaf touches a leaf two or more levels coarser over one of the offsets
+static bool one_irregular(const mfgpu::Tree &T, const uint32_t *leaves, uint32_t n_leaves,
+                          const std::vector<std::array<int, 3>> &offsets) {
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    for (const auto &o : offsets) {
+      const int64_t ci[3] = {(int64_t)l[1] + o[0], (int64_t)l[2] + o[1], (int64_t)l[3] + o[2]};
+      const int lv = T.covering_level((int)l[0], ci);
+      if (lv >= 0 && lv < (int)l[0] - 1) return false;
+    }
   }
-  Tree T;
+  return true;
+}
+
+// The checks mfgpu_mesh_coarsen_leaves and mfgpu_mesh_refine_leaves share: the leaves (level, cx, cy, cz) lie in the root
+// cell, none deeper than level 18 or listed twice, they partition the root cell, and they are one-irregular over faces and,
+// in 3D, edges.  Fills T with them.
+static int load_leaves(const char *who, int dim, const uint32_t *leaves, uint32_t n_leaves, mfgpu::Tree &T) {
+  using namespace mfgpu;
   T.dim = dim;
   const int kMaxLevel = 18;  // ckey's 19 bits per coordinate; dim * level < 64 for the volume sum
   for (uint32_t i = 0; i < n_leaves; ++i) {
@@ -554,10 +572,6 @@ int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_le
       return MFGPU_EINVAL;
     }
     T.max_level = std::max(T.max_level, (int)l[0]);
-  }
-  if (T.max_level == 0) {
-    set_error(std::string(who) + ": the single root cell cannot be coarsened");
-    return MFGPU_EINVAL;
   }
   // a partition of the root: no leaf inside another, and the volumes add up
   uint64_t volume = 0;
@@ -577,25 +591,31 @@ int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_le
     set_error(std::string(who) + ": the leaves are not a partition (they do not cover the root cell)");
     return MFGPU_EINVAL;
   }
-  // the offsets to the neighbours over faces and, in 3D, edges
-  std::vector<std::array<int, 3>> offsets;
-  for (int ox = -1; ox <= 1; ++ox)
-    for (int oy = -1; oy <= 1; ++oy)
-      for (int oz = (dim == 3 ? -1 : 0); oz <= (dim == 3 ? 1 : 0); ++oz) {
-        const int nz = (ox != 0) + (oy != 0) + (oz != 0);
-        if (nz == 1 || (dim == 3 && nz == 2)) offsets.push_back({ox, oy, oz});
-      }
-  // one-irregular: no leaf touches a leaf two or more levels coarser over a face or an edge
-  for (uint32_t i = 0; i < n_leaves; ++i) {
-    const uint32_t *l = leaves + 4 * (size_t)i;
-    for (const auto &o : offsets) {
-      const int64_t ci[3] = {(int64_t)l[1] + o[0], (int64_t)l[2] + o[1], (int64_t)l[3] + o[2]};
-      const int lv = T.covering_level((int)l[0], ci);
-      if (lv >= 0 && lv < (int)l[0] - 1) {
-        set_error(std::string(who) + ": the leaves are not one-irregular over faces and edges");
-        return MFGPU_EINVAL;
-      }
-    }
+  if (!one_irregular(T, leaves, n_leaves, neighbour_offsets(dim, false))) {
+    set_error(std::string(who) + ": the leaves are not one-irregular over faces and edges");
+    return MFGPU_EINVAL;
+  }
+  return 0;
+}
+
+// One step of global coarsening (DESIGN.md section 20).  Every complete family of sibling leaves is replaced by its
+// parent; then, until nothing changes, a new parent is split again where it breaks one-irregularity: where a cell of its
+// own level next to it over a face (3D: or an edge) has a child at the shared face / edge that is itself refined, so a
+// leaf two or more levels finer than the parent touches it.  A rollback only makes the set finer, so it can only force
+// further rollbacks: the fixed point does not depend on the order.
+int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, uint32_t *out) {
+  using namespace mfgpu;
+  const char *who = "mfgpu_mesh_coarsen_leaves";
+  if ((dim != 2 && dim != 3) || !leaves || !out || n_leaves == 0) {
+    set_error(std::string(who) + ": bad argument (dim 2 or 3, arrays, at least one leaf)");
+    return MFGPU_EINVAL;
+  }
+  Tree T;
+  if (const int rc = load_leaves(who, dim, leaves, n_leaves, T)) return rc;
+  const std::vector<std::array<int, 3>> offsets = neighbour_offsets(dim, false);
+  if (T.max_level == 0) {
+    set_error(std::string(who) + ": the single root cell cannot be coarsened");
+    return MFGPU_EINVAL;
   }
   // the complete families
   std::unordered_map<uint64_t, int> n_children;
@@ -664,6 +684,64 @@ int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_le
     for (int d = 0; d < 3; ++d) out[4 * i + 1 + d] = c.c[d];
   }
   return (int64_t)keys.size();
+}
+
+// One step of refinement: the flagged leaves and, to stay one-irregular, every leaf that a split
+// leaf of higher level touches (Tree::refine_flagged: over faces and 3D edges, with balance_vertices over vertices too)
+// are replaced by their children.  The closure only ever reaches leaves coarser than the one that forces them, and the
+// input is one-irregular in the relation of the closure (with balance_vertices that is checked here: over vertices too),
+// so no child splits: whatever is no longer a leaf afterwards was an input leaf.
+int64_t mfgpu_mesh_refine_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, const uint8_t *flags,
+                                 uint32_t balance_vertices, uint32_t *out, uint64_t out_capacity) {
+  using namespace mfgpu;
+  const char *who = "mfgpu_mesh_refine_leaves";
+  if ((dim != 2 && dim != 3) || !leaves || !flags || !out || n_leaves == 0) {
+    set_error(std::string(who) + ": bad argument (dim 2 or 3, arrays, at least one leaf)");
+    return MFGPU_EINVAL;
+  }
+  Tree T;
+  if (const int rc = load_leaves(who, dim, leaves, n_leaves, T)) return rc;
+  T.balance_vertices = balance_vertices != 0;
+  // the closure starts at split leaves only: an input that is not balanced over vertices would stay unbalanced where
+  // nothing splits, and could force a child to split where something does
+  if (T.balance_vertices && !one_irregular(T, leaves, n_leaves, neighbour_offsets(dim, true))) {
+    set_error(std::string(who) + ": balance_vertices needs leaves that are one-irregular over vertices too");
+    return MFGPU_EINVAL;
+  }
+  std::vector<Cell> flagged;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    if (!flags[i]) continue;
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    if (l[0] >= 18) {
+      set_error(std::string(who) + ": a child of a flagged leaf would be deeper than level 18");
+      return MFGPU_EINVAL;
+    }
+    flagged.push_back(Cell{(int)l[0], {l[1], l[2], l[3]}});
+  }
+  T.refine_flagged(flagged);
+  uint64_t n_out = 0;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    n_out += T.is_active((int)l[0], l + 1) ? 1 : (1u << dim);
+  }
+  if (n_out > out_capacity) {
+    set_error(std::string(who) + ": out_capacity " + std::to_string(out_capacity) + " is too small, the refined set has " +
+              std::to_string(n_out) + " leaves");
+    return MFGPU_EINVAL;
+  }
+  uint32_t *o = out;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    if (T.is_active((int)l[0], l + 1)) {
+      for (int j = 0; j < 4; ++j) *o++ = l[j];
+      continue;
+    }
+    for (uint32_t k = 0; k < (1u << dim); ++k) {
+      *o++ = l[0] + 1;
+      for (int d = 0; d < 3; ++d) *o++ = d < dim ? 2 * l[1 + d] + ((k >> d) & 1u) : 0u;
+    }
+  }
+  return (int64_t)n_out;
 }
 
 int mfgpu_mesh_coarsening_map(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, uint32_t *parent, uint32_t *child) {

@@ -132,6 +132,7 @@ SYMBOLS = [
     "mfgpu_transfer_create_p_hn", "mfgpu_transfer_create_p_hn_from_meshes", "mfgpu_transfer_p_owner_list",
     "mfgpu_mesh_coarsen_leaves", "mfgpu_mesh_coarsening_map", "mfgpu_transfer_create_h_hn",
     "mfgpu_transfer_create_h_hn_from_meshes",
+    "mfgpu_integrator_recovery_indicator", "mfgpu_mesh_refine_leaves",
 ]
 
 _lib = None
@@ -311,6 +312,9 @@ def lib():
         L.mfgpu_transfer_create_h_hn.argtypes = [i, i, i, u32, u32, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp,
                                                  C.POINTER(vp)]
         L.mfgpu_transfer_create_h_hn_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
+        L.mfgpu_integrator_recovery_indicator.argtypes = [vp, vp, vp, vp, vp]
+        L.mfgpu_mesh_refine_leaves.argtypes = [i, vp, u32, vp, u32, vp, C.c_uint64]
+        L.mfgpu_mesh_refine_leaves.restype = C.c_int64
         _lib = L
     return _lib
 
@@ -387,6 +391,37 @@ class Mesh:
         if n < 0:
             _check(int(n))
         return out[:n].copy()
+
+    @staticmethod
+    def refine_leaves(dim, leaves, flags, balance_vertices=False):
+        """one refinement step of the leaves (level, cx, cy, cz) (mfgpu_mesh_refine_leaves): the flagged leaves and
+        whatever one-irregularity forces become their children, in the parent's place; [n_fine, 4]; host only.  With
+        balance_vertices the leaves must be one-irregular over vertices too (Mesh.adaptive_mg, results of this call
+        with balance_vertices): the call balances what it splits, it does not repair an unbalanced input"""
+        lv = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 4)
+        fl = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8).reshape(-1)
+        if len(fl) != len(lv):
+            raise MfgpuError("Mesh.refine_leaves: one flag per leaf")
+        cap = max(len(lv), 1) * 2 ** dim  # no leaf splits twice
+        out = np.zeros((cap, 4), dtype=np.uint32)
+        n = lib().mfgpu_mesh_refine_leaves(dim, lv.ctypes.data if len(lv) else None, len(lv),
+                                           fl.ctypes.data if len(fl) else None, int(bool(balance_vertices)),
+                                           out.ctypes.data, cap)
+        if n < 0:
+            _check(int(n))
+        return out[:n].copy()
+
+    def refined(self, flags, degree=None, balance_vertices=False, number_type=None):
+        """a new leaf mesh: this adaptive or from-leaves mesh with the flagged cells (one flag per cell, in cell order)
+        refined by Mesh.refine_leaves, at `degree` and `number_type` (default: this mesh's).  Transfer.h_hn_from_meshes
+        (self, result) and coarsening_map(self, result) apply to the pair when the degrees are equal."""
+        leaves = self.cell_levels()
+        if not len(leaves):
+            raise MfgpuError("Mesh.refined: needs a leaf mesh (Mesh.adaptive, Mesh.adaptive_mg, Mesh.from_leaves)")
+        dim = int(self.desc.dim)
+        return Mesh.from_leaves(dim, int(self.desc.degree) if degree is None else int(degree),
+                                Mesh.refine_leaves(dim, leaves, flags, balance_vertices),
+                                number_type=int(self.desc.number_type) if number_type is None else number_type)
 
     @classmethod
     def coarsening_sequence(cls, mesh, degree=None, min_cells=None):
@@ -910,6 +945,15 @@ class Integrator:
         `gradients` [n_cells * (p+1)^dim * dim] (device arrays; gradients need UPDATABLE_COEFFICIENTS)"""
         _check(lib().mfgpu_integrator_evaluate(self._h, _ptr(u), _optr(values), _optr(gradients), stream))
 
+    def recovery_indicator(self, u, per_cell=None, weight=None, stream=None):
+        """eta_K^2 [n_cells] of the gradient-recovery indicator (mfgpu_integrator_recovery_indicator) into the device
+        array `per_cell` (default: a new DeviceVector, which is returned); weight: [n_cells * (p+1)^dim] at the
+        quadrature points or None for 1.  Needs UPDATABLE_COEFFICIENTS.  Asynchronous."""
+        if per_cell is None:
+            per_cell = DeviceVector(self.n_cells)
+        _check(lib().mfgpu_integrator_recovery_indicator(self._h, _ptr(u), _optr(weight), _ptr(per_cell), stream))
+        return per_cell
+
     def error_points(self):
         """the error points of every cell on the host, [n_cells, (p+2)^dim, dim]"""
         v = DeviceVector(self.n_cells * self.n_error_points * self.dim)
@@ -1164,6 +1208,18 @@ def coarsening_map(coarse: "Mesh", fine: "Mesh"):
     parent, child = np.zeros(fine.n_cells, dtype=np.uint32), np.zeros(fine.n_cells, dtype=np.uint32)
     _check(lib().mfgpu_mesh_coarsening_map(coarse._h, fine._h, parent.ctypes.data, child.ctypes.data))
     return parent, child
+
+
+def mark_fixed_number(indicators, fraction):
+    """flags [n] (uint8) of the ceil(fraction * n) largest indicators, ties broken by the lower cell index
+    (GridRefinement::refine_and_coarsen_fixed_number without coarsening); host numpy"""
+    eta = np.asarray(indicators, dtype=np.float64).reshape(-1)
+    if not 0.0 <= fraction <= 1.0:
+        raise MfgpuError("mark_fixed_number: fraction must lie in [0, 1]")
+    k = min(len(eta), int(np.ceil(fraction * len(eta))))
+    flags = np.zeros(len(eta), dtype=np.uint8)
+    flags[np.argsort(-eta, kind="stable")[:k]] = 1
+    return flags
 
 
 def _ptr(v):

@@ -792,6 +792,30 @@ int mfgpu_integrator_update_coefficients(mfgpu_integrator *it, const void *coeff
  * wave per cell, no atomics: two calls give bitwise-equal results.  Asynchronous.  With this and the BLAS-1 calls a
  * coefficient a(u) is formed on the device and handed to the update calls (host/nonlinear.cc).                       */
 int mfgpu_integrator_evaluate(mfgpu_integrator *it, const void *u, void *values_qp, void *gradients_qp, void *stream);
+/* Cell-based gradient-recovery error indicator (Zienkiewicz-Zhu style): per_cell [n_cells] =
+ * eta_K^2 of the field u [n_dofs].  Device doubles.  weight_qp: [n_cells * (p+1)^dim] at the quadrature points, or NULL
+ * for 1 (pass the coefficient for the energy norm).  With N = p+1, ND = N^dim:
+ *  a. Cell gradient at the nodes.  u is gathered through loc2glob with hanging-node interpolation and its real-space
+ *     gradient grad u_h is formed at the cell's ND quadrature points, both exactly as mfgpu_integrator_evaluate does.
+ *     Per component, g_K [ND] are the nodal coefficients of the Q_p polynomial that takes those ND values at the
+ *     quadrature points: g_K = (T x T (x T)) values, T [i][q] the inverse of the square 1D table [q][i] = phi_i(x_q)
+ *     (= shape_values transposed), x fastest.
+ *  b. Nodal average.  |K| = sum_q JxW_q.  A local position is constrained when it lies on a constrained face or, in 3D,
+ *     a constrained edge of the cell -- the pencils the hanging-node resolution rewrites: with the mask bits of
+ *     hanging_nodes.cuh:38-50, face d (bit 3+d) at index 0 of direction d if type bit d is set, else p; the edge along
+ *     e (bits 7, 8, 6 for e = x, y, z) at those indices of both other directions.  Every position i that is not
+ *     constrained adds |K| g_K,i (per component) to the numerator and |K| to the denominator of the dof
+ *     loc2glob[K][i], Dirichlet dofs included, summed per dof in ascending (cell, local index) order.
+ *     G_dof = numerator / denominator; a dof without contribution (a hanging dof) gets 0 and is never read.
+ *  c. eta_K^2 = sum_q weight_q |G(x_q) - grad u_h(x_q)|^2 JxW_q, with G read through loc2glob with hanging-node
+ *     interpolation, component by component, and evaluated at the quadrature points with phi_i(x_q).
+ * Needs inv_jac on the device: MFGPU_EINVAL on an integrator created without MFGPU_UPDATABLE_COEFFICIENTS, and on NULL
+ * u or per_cell.  The index list and the denominator of step b are built at creation; the double scratch (dim local
+ * buffers [n_cells * ND], dim nodal vectors [n_dofs]) is allocated by the first call and kept, so call once before
+ * capturing the call in a graph.  Three launches (a, b, c), one wave per cell in a and c, no atomics: two calls give
+ * bitwise-equal results.  Asynchronous: enqueues on `stream` and reads nothing back.                                 */
+int mfgpu_integrator_recovery_indicator(mfgpu_integrator *it, const void *u, const void *weight_qp, void *per_cell,
+                                        void *stream);
 void mfgpu_integrator_destroy(mfgpu_integrator *it);
 
 /* ---- deal.II stand-in for the setup side (host only) --------------------------------------
@@ -870,6 +894,23 @@ int mfgpu_mesh_coarsening_map(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, 
  * children (mfgpu_mesh_coarsening_map), in the fine mesh's number type, with the coarse mesh's constrained dofs and
  * constraint weights.  MFGPU_EINVAL: not two leaf meshes, the degrees or dimensions differ, no map                    */
 int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
+/* ---- adaptive refinement (host only).  One refinement step of a set of leaves: every leaf i with
+ * flags[i] != 0 is replaced by its 2^dim children (child k: bit d of k = the upper half in direction d, as in
+ * mfgpu_mesh_coarsening_map); then, until nothing changes, every leaf that is touched by a leaf two or more levels finer
+ * is split too -- touched over a face or, in 3D, an edge (the relation of mfgpu_mesh_coarsen_leaves), with
+ * balance_vertices != 0 also over a vertex (the rule of mfgpu_mesh_create_adaptive_mg).  Splitting only makes the set
+ * finer, so the fixed point does not depend on the order.  The input must be one-irregular in the same relation -- over
+ * faces and edges, with balance_vertices over vertices too (mfgpu_mesh_create_adaptive_mg meshes and results of this
+ * call with balance_vertices are) -- and is refused otherwise: the call balances what it splits, it does not repair an
+ * unbalanced input.  The input being one-irregular in that relation, only input leaves ever split:
+ * every output leaf is an input leaf or a child of one, and mfgpu_mesh_coarsening_map and
+ * mfgpu_transfer_create_h_hn_from_meshes apply to the pair.  Output order: the input order, the children of a split
+ * leaf in its place in child order.  Returns the number of leaves written to out [out_capacity * 4]; MFGPU_EINVAL when
+ * out_capacity is too small (the message names the needed count), when the input is not a partition of the root cell or
+ * not one-irregular over faces and edges (with balance_vertices: and vertices), or when a child would be deeper than
+ * level 18.                                                                                                          */
+int64_t mfgpu_mesh_refine_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, const uint8_t *flags,
+                                 uint32_t balance_vertices, uint32_t *out, uint64_t out_capacity /* leaves */);
 void mfgpu_mesh_destroy(mfgpu_mesh *m);
 /* fills *desc with pointers into the mesh (valid until mfgpu_mesh_destroy) */
 int mfgpu_mesh_desc(const mfgpu_mesh *m, mfgpu_desc *desc);
