@@ -27,6 +27,7 @@
 
 #include "mfgpu_cell.h"
 #include "mfgpu_stream.h"
+#include "mfgpu_transfer_build.h"
 
 using namespace mfgpu;
 
@@ -609,23 +610,6 @@ bool invert_table(int n, const double *m, std::vector<double> &inv) {
   for (int r = 0; r < n; ++r)
     for (int c = 0; c < n; ++c) inv[r * n + c] = (double)a[r * 2 * n + n + c];
   return true;
-}
-
-// is local position i of a cell with this constraint mask on a constrained face or (3D) edge?  (mfgpu_cell.h hn_flag2 /
-// hn_flag3: the union of the pencils hn_resolve rewrites)
-bool constrained_position(int dim, int n, unsigned mask, int i) {
-  if (!mask) return false;
-  const int p = n - 1, ix[3] = {i % n, (i / n) % n, dim == 3 ? i / (n * n) : 0};
-  bool at[3];
-  for (int d = 0; d < 3; ++d) at[d] = ix[d] == ((mask & (1u << d)) ? 0 : p);
-  for (int d = 0; d < dim; ++d)
-    if ((mask & (1u << (3 + d))) && at[d]) return true;
-  if (dim == 3) {
-    const unsigned EDGE[3] = {1u << 7, 1u << 8, 1u << 6};  // along x, y, z
-    for (int e = 0; e < 3; ++e)
-      if ((mask & EDGE[e]) && at[(e + 1) % 3] && at[(e + 2) % 3]) return true;
-  }
-  return false;
 }
 
 enum Which { RHS, L2, POINTS, EVAL };

@@ -50,7 +50,6 @@ int build_ball(Mesh &M, int n_ref);
 // free_gpu.h:246 level_dof_indices); fine must be the global refinement of coarse
 int mesh_transfer_patches(const Mesh &coarse, const Mesh &fine, std::vector<uint32_t> &coarse_cell_dofs,
                           std::vector<uint32_t> &fine_patch_dofs);
-void default_prolongation_1d(int p, std::vector<double> &P1);
 int build_from_tree_leaves(Mesh &M, int dim, std::vector<std::array<uint32_t, 4>> leaves);
 
 }  // namespace mfgpu

@@ -1,22 +1,17 @@
-// The transfer object behind mfgpu_transfer_* (mfgpu_transfer.hip: between two refinement levels at one degree;
-// mfgpu_transfer_p.hip: between two degrees on one mesh; mfgpu_transfer_h.hip: between two leaf meshes with hanging
-// nodes at one degree).  All kinds share the index layout -- per cell its coarse dofs (bit 31: Dirichlet) and its fine
-// dofs (bit 31: another cell owns the dof, or the position is a constrained one of a cell with hanging nodes) -- and the
-// three entry points, which dispatch on `kind`.
+// The transfer object behind mfgpu_transfer_* and what its three kernel files share on the host: the modes of the one
+// entry path and the dispatch on them (mfgpu_transfer.hip: creators, entry points and the kernel between two refinement
+// levels at one degree; mfgpu_transfer_p.hip: between two degrees on one mesh; mfgpu_transfer_h.hip: between two leaf
+// meshes with hanging nodes at one degree).  The device arrays are a TransferImage as uploaded: the index format and the
+// owner rule are mfgpu_transfer_build.h's.
 #ifndef MFGPU_TRANSFER_H
 #define MFGPU_TRANSFER_H
 
 #include <hip/hip_runtime.h>
 
-#include "mfgpu_device.h"
+#include <type_traits>
 
-namespace mfgpu {
-enum TransferKind {
-  TRANSFER_KIND_H = 0,     // mfgpu_transfer_create: coarse cells and the patches of their children
-  TRANSFER_KIND_P = 1,     // mfgpu_transfer_create_p(_hn): degree_coarse -> degree on the same cells
-  TRANSFER_KIND_H_HN = 2,  // mfgpu_transfer_create_h_hn: fine leaves, each the same cell as or a child of a coarse leaf
-};
-}
+#include "mfgpu_device.h"
+#include "mfgpu_transfer_build.h"
 
 struct mfgpu_transfer {
   int kind = mfgpu::TRANSFER_KIND_H;
@@ -27,34 +22,63 @@ struct mfgpu_transfer {
   // h_hn: [coarse cells][(p+1)^dim], [fine cells][(p+1)^dim]
   mfgpu::DeviceArray<uint32_t> d_coarse, d_fine;
   mfgpu::DeviceArray<void> d_p1;  // h, h_hn: P1[(2p+1) * (p+1)]; p: P1[(pf+1) * (pc+1)]; fine index major
-  // p-transfer on cells with hanging nodes (mfgpu_transfer_create_p_hn with a mask): the cells' constraint masks and the
-  // weight matrix W[(pc+1)^2] of the COARSE degree in number_type; the fine side's constrained positions are plain
-  // bit-31 entries of d_fine.  h_hn: d_weights is W[(p+1)^2] and d_mask holds one word per FINE cell, the parent's
-  // coarse mask in bits 0..8 and `child` in bits 16..19
+  // hanging_nodes (p with a mask, h_hn): TransferImage::words and the weight matrix W of the COARSE degree in number_type
   bool hanging_nodes = false;
   mfgpu::DeviceArray<uint32_t> d_mask;
   mfgpu::DeviceArray<void> d_weights;
-  // h_hn only: the fine cells' count and the index of each one's coarse cell
-  uint32_t n_fine_cells = 0;
-  mfgpu::DeviceArray<uint32_t> d_parent;
-  bool covers_all = true;                         // every fine dof is listed by some cell
+  uint32_t n_fine_cells = 0;               // the fine lists' count (h, p: n_coarse_cells)
+  mfgpu::DeviceArray<uint32_t> d_parent;   // h_hn only: the index of each fine cell's coarse cell
+  bool covers_all = true;  // every fine dof is listed by some cell
   size_t device_bytes = 0;
 };
 
 namespace mfgpu {
 
-enum TransferMode { TRANSFER_PROLONGATE = 0, TRANSFER_PROLONGATE_ADD = 1, TRANSFER_RESTRICT_ADD = 2 };
-// the p-transfer's kernel for t->number_type (mfgpu_transfer_p.hip); enqueues only
-hipError_t launch_p_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st);
-// the same for the h-transfer between two leaf meshes (mfgpu_transfer_h.hip)
-hipError_t launch_h_hn_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st);
+constexpr int ipow_c(int a, int e) { return e == 0 ? 1 : a * ipow_c(a, e - 1); }
 
-// (mfgpu_transfer_p.hip) the 9 bits of a constraint mask; in 2D only TYPE x, y and FACE x, y
-bool valid_mask(int dim, uint32_t m);
-// (mfgpu_transfer_p.hip) the fine index list as it is uploaded, bit 31 on every entry but the owner's; `covered` = the
-// number of fine dofs with an owner; MFGPU_EINVAL for a bad mask, a dof out of range, a listed dof nobody owns
-int p_owner_list(const char *who, int dim, int degree_fine, uint32_t n_cells, const uint32_t *fine_cell_dofs,
-                 const uint32_t *mask, uint32_t n_fine_dofs, uint32_t *out, size_t &covered);
+enum TransferMode { TRANSFER_PROLONGATE = 0, TRANSFER_PROLONGATE_ADD = 1, TRANSFER_RESTRICT_ADD = 2 };
+
+// f(RESTRICT, ADD) with the mode's two kernel template arguments as std::integral_constants
+template <typename F>
+hipError_t dispatch_mode(TransferMode mode, F f) {
+  switch (mode) {
+    case TRANSFER_PROLONGATE: return f(std::false_type(), std::false_type());
+    case TRANSFER_PROLONGATE_ADD: return f(std::false_type(), std::true_type());
+    case TRANSFER_RESTRICT_ADD: return f(std::true_type(), std::false_type());
+  }
+  return hipErrorInvalidValue;
+}
+// f(dim, degree) as std::integral_constants for dim 2, 3 and degree MIN_DEGREE..6
+template <int MIN_DEGREE, typename F>
+hipError_t dispatch_dim_degree(int dim, int degree, F f) {
+#define MFGPU_TR_CASE(D, P)                                                                      \
+  case D * 10 + P:                                                                               \
+    if constexpr (P >= MIN_DEGREE) return f(std::integral_constant<int, D>(), std::integral_constant<int, P>()); \
+    break;
+  switch (dim * 10 + degree) {
+    MFGPU_TR_CASE(2, 1) MFGPU_TR_CASE(2, 2) MFGPU_TR_CASE(2, 3) MFGPU_TR_CASE(2, 4) MFGPU_TR_CASE(2, 5) MFGPU_TR_CASE(2, 6)
+    MFGPU_TR_CASE(3, 1) MFGPU_TR_CASE(3, 2) MFGPU_TR_CASE(3, 3) MFGPU_TR_CASE(3, 4) MFGPU_TR_CASE(3, 5) MFGPU_TR_CASE(3, 6)
+  }
+#undef MFGPU_TR_CASE
+  return hipErrorInvalidValue;
+}
+
+// f(dim, degree, RESTRICT, ADD): the template arguments of t's kernel for a mode
+template <int MIN_DEGREE, typename F>
+hipError_t dispatch_kernel(const mfgpu_transfer *t, TransferMode mode, F f) {
+  return dispatch_mode(mode, [&](auto restrict_, auto add) {
+    return dispatch_dim_degree<MIN_DEGREE>(t->dim, t->degree, [&](auto dim, auto degree) {
+      return f(dim, degree, decltype(restrict_)(), decltype(add)());
+    });
+  });
+}
+
+// The wave-per-cell kernels of t for number type T (HN: on cells with hanging nodes); each enqueues only.  Defined and
+// instantiated for double and float in mfgpu_transfer_p.hip and mfgpu_transfer_h.hip.
+template <typename T, bool HN>
+hipError_t launch_p_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st);
+template <typename T>
+hipError_t launch_h_hn_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st);
 
 }  // namespace mfgpu
 

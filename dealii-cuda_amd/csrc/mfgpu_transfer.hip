@@ -21,14 +21,13 @@
 //    and a transfer that does not cover the fine level simply leaves the other entries alone (no zero pass).
 // One 256-thread workgroup per coarse cell at a time (grid-stride); the three 1D contractions go through LDS.
 // Bound: HBM (one read of the fine vector + index lists); small next to the smoother's operator applies.
-// The same object and entry points also serve the transfer between two DEGREES on one mesh (p-multigrid): created by
-// mfgpu_transfer_create_p, kernels in mfgpu_transfer_p.hip (one wave per cell), and the transfer between two leaf meshes
-// with hanging nodes (global coarsening): mfgpu_transfer_create_h_hn, kernels in mfgpu_transfer_h.hip.  Dispatched here
-// on t->kind.
+// The same object and entry points also serve the transfer between two DEGREES on one mesh (p-multigrid; kernels in
+// mfgpu_transfer_p.hip, one wave per cell) and the transfer between two leaf meshes with hanging nodes (global
+// coarsening; kernels in mfgpu_transfer_h.hip).  All creators are here: each describes what it was given as a
+// TransferInput, build_transfer_image (mfgpu_transfer_build.cpp, plain C++) checks it and makes the host image, and
+// upload_transfer turns the image into the object.  All entry points go through launch_transfer.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -40,8 +39,6 @@
 namespace mfgpu {
 
 namespace {
-
-constexpr int ipow_c(int a, int e) { return e == 0 ? 1 : a * ipow_c(a, e - 1); }
 
 // sizes of the intermediate arrays: after contracting directions 0..k-1 the array is nf^k x nc^(dim-k)
 template <int dim, int p, typename T, bool RESTRICT, bool ADD>
@@ -103,23 +100,16 @@ transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *
   }
 }
 
-template <typename T, bool RESTRICT, bool ADD = false>
-hipError_t launch(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t st) {
+template <typename T>
+hipError_t launch_level_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {
   const uint32_t n = t->n_coarse_cells;
   if (n == 0) return hipSuccess;
   const unsigned grid = n < 8192u ? n : 8192u;
-#define TR_CASE(D, PP)                                                                                           \
-  case D * 10 + PP:                                                                                              \
-    hipLaunchKernelGGL((transfer_kernel<D, PP, T, RESTRICT, ADD>), dim3(grid), dim3(256), 0, st, dst, src,           \
-                       t->d_coarse.get(), t->d_fine.get(), t->d_p1.as<const T>(), n);                            \
-    break;
-  switch (t->dim * 10 + t->degree) {
-    TR_CASE(2, 1) TR_CASE(2, 2) TR_CASE(2, 3) TR_CASE(2, 4) TR_CASE(2, 5) TR_CASE(2, 6)
-    TR_CASE(3, 1) TR_CASE(3, 2) TR_CASE(3, 3) TR_CASE(3, 4) TR_CASE(3, 5) TR_CASE(3, 6)
-    default: return hipErrorInvalidValue;
-  }
-#undef TR_CASE
-  return hipGetLastError();
+  return dispatch_kernel<1>(t, mode, [&](auto D, auto P, auto R, auto A) {
+    hipLaunchKernelGGL((transfer_kernel<D(), P(), T, R(), A()>), dim3(grid), dim3(256), 0, st, (T *)dst, (const T *)src,
+                       t->d_coarse.get(), t->d_fine.get(), t->d_p1.as<const T>(), n);
+    return hipGetLastError();
+  });
 }
 
 template <typename T>
@@ -128,24 +118,80 @@ __global__ void zero_kernel(T *v, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) v[i] = T(0);
 }
 
-}  // namespace
-
-// FE_Q(p) on Gauss-Lobatto nodes: P1[X * (p+1) + x] = phi_x(xi_X), xi_X the 2p+1 child nodes on the parent's [0,1]
-void default_prolongation_1d(int p, std::vector<double> &P1) {
-  std::vector<double> nodes, val, der;
-  gll_01(p, nodes);
-  const int nc = p + 1, nf = 2 * p + 1;
-  P1.assign((size_t)nf * nc, 0.0);
-  for (int X = 0; X < nf; ++X) {
-    const double xi = X <= p ? 0.5 * nodes[X] : 0.5 + 0.5 * nodes[X - p];
-    lagrange_eval(nodes, xi, val, der);
-    for (int x = 0; x < nc; ++x) P1[(size_t)X * nc + x] = val[x];
-  }
-  // exact zeros / ones where a child node coincides with a parent node
-  for (double &v : P1)
-    if (std::fabs(v) < 1e-15) v = 0.0;
-    else if (std::fabs(v - 1.0) < 1e-15) v = 1.0;
+// the image as device arrays: P1 and W in number_type, every array that is present, device_bytes their sum
+int upload_transfer(const TransferInput &in, const TransferImage &img, mfgpu_transfer **out) {
+  std::unique_ptr<mfgpu_transfer> t(new mfgpu_transfer());
+  t->kind = in.kind;
+  t->dim = in.dim;
+  t->degree = in.degree;
+  t->degree_coarse = in.kind == TRANSFER_KIND_P ? in.degree_coarse : 0;
+  t->number_type = in.number_type;
+  t->n_coarse_cells = in.n_coarse_cells;
+  t->n_fine_cells = in.n_fine_cells;
+  t->n_coarse_dofs = in.n_coarse_dofs;
+  t->n_fine_dofs = in.n_fine_dofs;
+  t->hanging_nodes = img.hanging_nodes;
+  t->covers_all = img.covered == in.n_fine_dofs;
+  auto upload_numbers = [&](DeviceArray<void> &d, const std::vector<double> &v) {
+    if (in.number_type == MFGPU_F64) return d.upload(v.data(), v.size() * sizeof(double));
+    const std::vector<float> f(v.begin(), v.end());
+    return d.upload(f.data(), f.size() * sizeof(float));
+  };
+  int rc;
+  if ((rc = t->d_coarse.upload(img.coarse.data(), img.coarse.size())) || (rc = t->d_fine.upload(img.fine.data(), img.fine.size())) ||
+      (rc = t->d_parent.upload(img.parent.data(), img.parent.size())) || (rc = t->d_mask.upload(img.words.data(), img.words.size())) ||
+      (rc = upload_numbers(t->d_p1, img.P1)) || (rc = upload_numbers(t->d_weights, img.W)))
+    return rc;
+  t->device_bytes = t->d_coarse.bytes() + t->d_fine.bytes() + t->d_parent.bytes() + t->d_mask.bytes() + t->d_p1.bytes() +
+                    t->d_weights.bytes();
+  *out = t.release();
+  return 0;
 }
+
+int create_transfer(const TransferInput &in, mfgpu_transfer **out) {
+  if (!out) {
+    set_error(std::string(in.who) + ": bad argument (null out)");
+    return MFGPU_EINVAL;
+  }
+  TransferImage img;
+  if (const int rc = build_transfer_image(in, img)) return rc;
+  return upload_transfer(in, img, out);
+}
+
+hipError_t launch_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {
+  const bool f64 = t->number_type == MFGPU_F64;
+  switch (t->kind) {
+    case TRANSFER_KIND_H:
+      return f64 ? launch_level_transfer<double>(t, dst, src, mode, st) : launch_level_transfer<float>(t, dst, src, mode, st);
+    case TRANSFER_KIND_P:
+      if (t->hanging_nodes)
+        return f64 ? launch_p_transfer<double, true>(t, dst, src, mode, st) : launch_p_transfer<float, true>(t, dst, src, mode, st);
+      return f64 ? launch_p_transfer<double, false>(t, dst, src, mode, st) : launch_p_transfer<float, false>(t, dst, src, mode, st);
+    case TRANSFER_KIND_H_HN:
+      return f64 ? launch_h_hn_transfer<double>(t, dst, src, mode, st) : launch_h_hn_transfer<float>(t, dst, src, mode, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+// the three entry points; `who` is the C-ABI function.  A prolongation that does not cover the fine side zeroes dst first
+// (a kernel on the caller's stream, so that a captured graph holds kernel nodes only)
+int apply_transfer(const char *who, const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, void *stream) {
+  if (!t || !dst || !src) {
+    set_error(std::string(who) + ": null argument");
+    return MFGPU_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == TRANSFER_PROLONGATE && !t->covers_all) {
+    if (t->number_type == MFGPU_F64)
+      hipLaunchKernelGGL(zero_kernel<double>, dim3(2048), dim3(256), 0, st, (double *)dst, (size_t)t->n_fine_dofs);
+    else
+      hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst, (size_t)t->n_fine_dofs);
+  }
+  HIP_TRY(launch_transfer(t, dst, src, mode, st));
+  return 0;
+}
+
+}  // namespace
 
 void transfer_sizes(const mfgpu_transfer *t, uint32_t *n_coarse_dofs, uint32_t *n_fine_dofs, int *number_type) {
   *n_coarse_dofs = t->n_coarse_dofs;
@@ -161,65 +207,21 @@ int mfgpu_transfer_create(int dim, int degree, int number_type, uint32_t n_coars
                           const uint32_t *fine_patch_dofs, uint32_t n_coarse_dofs, uint32_t n_fine_dofs,
                           const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet, const double *prolongation_1d,
                           mfgpu_transfer **out) {
-  using namespace mfgpu;
-  if (!out || (dim != 2 && dim != 3) || degree < 1 || degree > 6 || (n_coarse_cells && (!coarse_cell_dofs || !fine_patch_dofs)) ||
-      (n_coarse_dirichlet && !coarse_dirichlet) || !valid_number_type(number_type) ||
-      n_coarse_dofs >= (1u << 31) || n_fine_dofs >= (1u << 31)) {
-    set_error("mfgpu_transfer_create: bad argument");
-    return MFGPU_EINVAL;
-  }
-  const int nc = degree + 1, nf = 2 * degree + 1;
-  const size_t NC = (size_t)ipow(nc, dim), NF = (size_t)ipow(nf, dim);
-  std::vector<uint8_t> dir(n_coarse_dofs, 0), seen(n_fine_dofs, 0);
-  for (uint32_t i = 0; i < n_coarse_dirichlet; ++i) {
-    if (coarse_dirichlet[i] >= n_coarse_dofs) {
-      set_error("mfgpu_transfer_create: Dirichlet dof out of range");
-      return MFGPU_EINVAL;
-    }
-    dir[coarse_dirichlet[i]] = 1;
-  }
-  std::vector<uint32_t> cd((size_t)n_coarse_cells * NC), fd((size_t)n_coarse_cells * NF);
-  for (size_t i = 0; i < cd.size(); ++i) {
-    const uint32_t g = coarse_cell_dofs[i];
-    if (g >= n_coarse_dofs) {
-      set_error("mfgpu_transfer_create: coarse dof out of range");
-      return MFGPU_EINVAL;
-    }
-    cd[i] = g | (dir[g] ? 0x80000000u : 0u);
-  }
-  size_t covered = 0;
-  for (size_t i = 0; i < fd.size(); ++i) {
-    const uint32_t g = fine_patch_dofs[i];
-    if (g >= n_fine_dofs) {
-      set_error("mfgpu_transfer_create: fine dof out of range");
-      return MFGPU_EINVAL;
-    }
-    fd[i] = g | (seen[g] ? 0x80000000u : 0u);  // the first patch that lists a fine dof owns it
-    if (!seen[g]) ++covered;
-    seen[g] = 1;
-  }
-  std::vector<double> P1;
-  if (prolongation_1d)
-    P1.assign(prolongation_1d, prolongation_1d + (size_t)nf * nc);
-  else
-    default_prolongation_1d(degree, P1);
-  std::unique_ptr<mfgpu_transfer> t(new mfgpu_transfer());
-  t->dim = dim;
-  t->degree = degree;
-  t->number_type = number_type;
-  t->n_coarse_cells = n_coarse_cells;
-  t->n_coarse_dofs = n_coarse_dofs;
-  t->n_fine_dofs = n_fine_dofs;
-  t->covers_all = covered == n_fine_dofs;
-  std::vector<float> P1f(P1.begin(), P1.end());
-  const void *p1src = number_type == MFGPU_F64 ? (const void *)P1.data() : (const void *)P1f.data();
-  int rc;
-  if ((rc = t->d_coarse.upload(cd.data(), cd.size())) || (rc = t->d_fine.upload(fd.data(), fd.size())) ||
-      (rc = t->d_p1.upload(p1src, P1.size() * esize(number_type))))
-    return rc;
-  t->device_bytes = t->d_coarse.bytes() + t->d_fine.bytes() + t->d_p1.bytes();
-  *out = t.release();
-  return 0;
+  mfgpu::TransferInput in;
+  in.who = "mfgpu_transfer_create";
+  in.kind = mfgpu::TRANSFER_KIND_H;
+  in.dim = dim;
+  in.degree = degree;
+  in.number_type = number_type;
+  in.n_coarse_cells = in.n_fine_cells = n_coarse_cells;
+  in.coarse_cell_dofs = coarse_cell_dofs;
+  in.fine_cell_dofs = fine_patch_dofs;
+  in.n_coarse_dofs = n_coarse_dofs;
+  in.n_fine_dofs = n_fine_dofs;
+  in.coarse_dirichlet = coarse_dirichlet;
+  in.n_coarse_dirichlet = n_coarse_dirichlet;
+  in.prolongation_1d = prolongation_1d;
+  return mfgpu::create_transfer(in, out);
 }
 
 int mfgpu_transfer_create_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
@@ -236,60 +238,147 @@ int mfgpu_transfer_create_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh
                                (uint32_t)coarse->mesh.constrained.size(), nullptr, out);
 }
 
-int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src_coarse, void *stream) {
+int mfgpu_transfer_create_p(int dim, int degree_coarse, int degree_fine, int number_type, uint32_t n_cells,
+                            const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, uint32_t n_coarse_dofs,
+                            uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                            const double *prolongation_1d, mfgpu_transfer **out) {
+  return mfgpu_transfer_create_p_hn(dim, degree_coarse, degree_fine, number_type, n_cells, coarse_cell_dofs, fine_cell_dofs,
+                                    n_coarse_dofs, n_fine_dofs, coarse_dirichlet, n_coarse_dirichlet, prolongation_1d, nullptr,
+                                    nullptr, out);
+}
+
+int mfgpu_transfer_create_p_hn(int dim, int degree_coarse, int degree_fine, int number_type, uint32_t n_cells,
+                               const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, uint32_t n_coarse_dofs,
+                               uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                               const double *prolongation_1d, const uint32_t *constraint_mask,
+                               const double *coarse_constraint_weights, mfgpu_transfer **out) {
+  mfgpu::TransferInput in;
+  in.who = "mfgpu_transfer_create_p_hn";
+  in.kind = mfgpu::TRANSFER_KIND_P;
+  in.dim = dim;
+  in.degree_coarse = degree_coarse;
+  in.degree = degree_fine;
+  in.number_type = number_type;
+  in.n_coarse_cells = in.n_fine_cells = n_cells;
+  in.coarse_cell_dofs = coarse_cell_dofs;
+  in.fine_cell_dofs = fine_cell_dofs;
+  in.n_coarse_dofs = n_coarse_dofs;
+  in.n_fine_dofs = n_fine_dofs;
+  in.coarse_dirichlet = coarse_dirichlet;
+  in.n_coarse_dirichlet = n_coarse_dirichlet;
+  in.prolongation_1d = prolongation_1d;
+  in.coarse_mask = in.fine_mask = constraint_mask;  // (NULL: the conforming object, the HN = false kernels)
+  in.constraint_weights = coarse_constraint_weights;
+  return mfgpu::create_transfer(in, out);
+}
+
+int mfgpu_transfer_create_p_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
   using namespace mfgpu;
-  if (!t || !dst_fine || !src_coarse) {
-    set_error("mfgpu_transfer_prolongate: null argument");
+  if (!coarse || !fine || !out) {
+    set_error("mfgpu_transfer_create_p_from_meshes: null argument");
     return MFGPU_EINVAL;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const bool h = t->kind == TRANSFER_KIND_H;
-  if (t->number_type == MFGPU_F64) {
-    if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<double>, dim3(2048), dim3(256), 0, st, (double *)dst_fine, (size_t)t->n_fine_dofs);
-    if (h) HIP_TRY((launch<double, false>(t, (double *)dst_fine, (const double *)src_coarse, st)));
-  } else {
-    if (!t->covers_all) hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst_fine, (size_t)t->n_fine_dofs);
-    if (h) HIP_TRY((launch<float, false>(t, (float *)dst_fine, (const float *)src_coarse, st)));
+  const Mesh &C = coarse->mesh, &F = fine->mesh;
+  if (C.cells_kind < 0 || F.cells_kind < 0 || !C.constraint_mask.empty() || !F.constraint_mask.empty()) {
+    set_error("mfgpu_transfer_create_p_from_meshes: meshes with hanging nodes (adaptive, from leaves) are not supported");
+    return MFGPU_EUNSUPPORTED;
   }
-  if (t->kind == TRANSFER_KIND_P) HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE, st));
-  if (t->kind == TRANSFER_KIND_H_HN) HIP_TRY(launch_h_hn_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE, st));
-  return 0;
+  bool same = C.dim == F.dim && C.cells_kind == F.cells_kind && C.n_cells == F.n_cells;
+  if (same && C.cells_kind == 0)
+    for (int d = 0; d < 3; ++d) same = same && C.nper[d] == F.nper[d];
+  same = same && C.slab[0] == F.slab[0] && C.slab[1] == F.slab[1] && C.n_ref == F.n_ref;
+  if (!same) {
+    set_error("mfgpu_transfer_create_p_from_meshes: the two meshes are not the same cells (dimension, kind, cells per "
+              "direction and slab or n_ref, cell count)");
+    return MFGPU_EINVAL;
+  }
+  return mfgpu_transfer_create_p(C.dim, C.degree, F.degree, F.number_type, C.n_cells, C.loc2glob.data(), F.loc2glob.data(),
+                                 C.n_dofs, F.n_dofs, C.constrained.data(), (uint32_t)C.constrained.size(), nullptr, out);
+}
+
+int mfgpu_transfer_create_p_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
+  using namespace mfgpu;
+  if (!coarse || !fine || !out) {
+    set_error("mfgpu_transfer_create_p_hn_from_meshes: null argument");
+    return MFGPU_EINVAL;
+  }
+  const Mesh &C = coarse->mesh, &F = fine->mesh;
+  if (C.cells_kind >= 0 && F.cells_kind >= 0 && C.constraint_mask.empty() && F.constraint_mask.empty())
+    return mfgpu_transfer_create_p_from_meshes(coarse, fine, out);
+  // adaptive meshes and meshes from leaves: the same leaves in the same order; the masks are geometric, so equal too
+  if (C.cells_kind != -1 || F.cells_kind != -1 || C.dim != F.dim || C.n_cells != F.n_cells || C.cell_levels.empty() ||
+      C.cell_levels != F.cell_levels || C.constraint_mask != F.constraint_mask) {
+    set_error("mfgpu_transfer_create_p_hn_from_meshes: the two meshes are not the same cells (dimension, cell count, the "
+              "leaves and their order, constraint masks)");
+    return MFGPU_EINVAL;
+  }
+  return mfgpu_transfer_create_p_hn(C.dim, C.degree, F.degree, F.number_type, C.n_cells, C.loc2glob.data(), F.loc2glob.data(),
+                                    C.n_dofs, F.n_dofs, C.constrained.data(), (uint32_t)C.constrained.size(), nullptr,
+                                    C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(), C.weights.data(), out);
+}
+
+int mfgpu_transfer_create_h_hn(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
+                               const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, const uint32_t *parent,
+                               const uint32_t *child, uint32_t n_coarse_dofs, uint32_t n_fine_dofs,
+                               const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet, const double *prolongation_1d,
+                               const uint32_t *coarse_mask, const uint32_t *fine_mask, const double *constraint_weights,
+                               mfgpu_transfer **out) {
+  mfgpu::TransferInput in;
+  in.who = "mfgpu_transfer_create_h_hn";
+  in.kind = mfgpu::TRANSFER_KIND_H_HN;
+  in.dim = dim;
+  in.degree = degree;
+  in.number_type = number_type;
+  in.n_coarse_cells = n_coarse_cells;
+  in.n_fine_cells = n_fine_cells;
+  in.coarse_cell_dofs = coarse_cell_dofs;
+  in.fine_cell_dofs = fine_cell_dofs;
+  in.parent = parent;
+  in.child = child;
+  in.n_coarse_dofs = n_coarse_dofs;
+  in.n_fine_dofs = n_fine_dofs;
+  in.coarse_dirichlet = coarse_dirichlet;
+  in.n_coarse_dirichlet = n_coarse_dirichlet;
+  in.prolongation_1d = prolongation_1d;
+  in.coarse_mask = coarse_mask;
+  in.fine_mask = fine_mask;
+  in.constraint_weights = constraint_weights;
+  return mfgpu::create_transfer(in, out);
+}
+
+int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
+  using namespace mfgpu;
+  if (!coarse || !fine || !out) {
+    set_error("mfgpu_transfer_create_h_hn_from_meshes: null argument");
+    return MFGPU_EINVAL;
+  }
+  const Mesh &C = coarse->mesh, &F = fine->mesh;
+  if (C.cells_kind != -1 || F.cells_kind != -1 || C.cell_levels.empty() || F.cell_levels.empty() || C.dim != F.dim ||
+      C.degree != F.degree) {
+    set_error("mfgpu_transfer_create_h_hn_from_meshes: needs two leaf meshes (adaptive, from leaves) of one dimension and "
+              "one degree");
+    return MFGPU_EINVAL;
+  }
+  std::vector<uint32_t> parent(F.n_cells), child(F.n_cells);
+  int rc = mfgpu_mesh_coarsening_map(coarse, fine, parent.data(), child.data());
+  if (rc) return rc;
+  return mfgpu_transfer_create_h_hn(C.dim, C.degree, F.number_type, C.n_cells, F.n_cells, C.loc2glob.data(), F.loc2glob.data(),
+                                    parent.data(), child.data(), C.n_dofs, F.n_dofs, C.constrained.data(),
+                                    (uint32_t)C.constrained.size(), nullptr,
+                                    C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(),
+                                    F.constraint_mask.empty() ? nullptr : F.constraint_mask.data(), C.weights.data(), out);
+}
+
+int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src_coarse, void *stream) {
+  return mfgpu::apply_transfer("mfgpu_transfer_prolongate", t, dst_fine, src_coarse, mfgpu::TRANSFER_PROLONGATE, stream);
 }
 
 int mfgpu_transfer_prolongate_add(mfgpu_transfer *t, void *dst_fine, const void *src_coarse, void *stream) {
-  using namespace mfgpu;
-  if (!t || !dst_fine || !src_coarse) {
-    set_error("mfgpu_transfer_prolongate_add: null argument");
-    return MFGPU_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (t->kind == TRANSFER_KIND_P)
-    HIP_TRY(launch_p_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE_ADD, st));
-  else if (t->kind == TRANSFER_KIND_H_HN)
-    HIP_TRY(launch_h_hn_transfer(t, dst_fine, src_coarse, TRANSFER_PROLONGATE_ADD, st));
-  else if (t->number_type == MFGPU_F64)
-    HIP_TRY((launch<double, false, true>(t, (double *)dst_fine, (const double *)src_coarse, st)));
-  else
-    HIP_TRY((launch<float, false, true>(t, (float *)dst_fine, (const float *)src_coarse, st)));
-  return 0;
+  return mfgpu::apply_transfer("mfgpu_transfer_prolongate_add", t, dst_fine, src_coarse, mfgpu::TRANSFER_PROLONGATE_ADD, stream);
 }
 
 int mfgpu_transfer_restrict_and_add(mfgpu_transfer *t, void *dst_coarse, const void *src_fine, void *stream) {
-  using namespace mfgpu;
-  if (!t || !dst_coarse || !src_fine) {
-    set_error("mfgpu_transfer_restrict_and_add: null argument");
-    return MFGPU_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (t->kind == TRANSFER_KIND_P)
-    HIP_TRY(launch_p_transfer(t, dst_coarse, src_fine, TRANSFER_RESTRICT_ADD, st));
-  else if (t->kind == TRANSFER_KIND_H_HN)
-    HIP_TRY(launch_h_hn_transfer(t, dst_coarse, src_fine, TRANSFER_RESTRICT_ADD, st));
-  else if (t->number_type == MFGPU_F64)
-    HIP_TRY((launch<double, true>(t, (double *)dst_coarse, (const double *)src_fine, st)));
-  else
-    HIP_TRY((launch<float, true>(t, (float *)dst_coarse, (const float *)src_fine, st)));
-  return 0;
+  return mfgpu::apply_transfer("mfgpu_transfer_restrict_and_add", t, dst_coarse, src_fine, mfgpu::TRANSFER_RESTRICT_ADD, stream);
 }
 
 size_t mfgpu_transfer_memory_consumption(const mfgpu_transfer *t) { return t ? t->device_bytes : 0; }

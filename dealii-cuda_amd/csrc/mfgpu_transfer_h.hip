@@ -3,7 +3,7 @@
 // child k of one (child = 1 + k, bit d of k: the upper half in direction d).  What deal.II's MGTransferGlobalCoarsening
 // does between two members of create_geometric_coarsening_sequence.  The object is an mfgpu_transfer (mfgpu_transfer.h,
 // kind H_HN); the semantics are section 19's with two masks:
-//   owner of a fine dof   the first fine cell that lists it at a position its FINE mask does not constrain (p_owner_list)
+//   owner of a fine dof   the first fine cell that lists it at a position its FINE mask does not constrain (the owner rule)
 //   prolongate            for the owner F with parent K:  dst[fine(F, i)] = [ E(child_F) C_p(coarse_mask_K) gather_K(src) ]_i,
 //                         coarse Dirichlet dofs read as 0; plain store (prolongate_add: plain read-modify-write)
 //   restrict_and_add      the exact transpose: owned entries, E^T, C_p^T (z, y, x), floating-point atomics that skip the
@@ -29,25 +29,15 @@
 // 500 + 4 + 500 B, and 1/8 of the coarse index memory.  So the list is indexed THROUGH PARENT.  The extra dependent load
 // (parent -> coarse index -> value) is hidden by requesting the parent word TWO cells ahead: when the lists of the next
 // cell are requested its parent has been in a register for a whole cell.
+// The creator is in mfgpu_transfer.hip; what the kernel shares with the p kernel in mfgpu_transfer_wave.h.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "mfgpu_device.h"
-#include "mfgpu_mesh.h"
 #include "mfgpu_transfer.h"
-#include "mfgpu_transfer_hn.h"
+#include "mfgpu_transfer_wave.h"
 
 namespace mfgpu {
 
 namespace {
-
-constexpr int ipow_c(int a, int e) { return e == 0 ? 1 : a * ipow_c(a, e - 1); }
-constexpr int kWaves = 4;            // fine cells per workgroup pass
-constexpr unsigned kMaxGrid = 2048;  // workgroups: 8 per CU on 256 CUs; more cells than 4 * kMaxGrid take further passes
 
 template <int dim, int p, typename T, bool RESTRICT, bool ADD>
 __global__ void __launch_bounds__(64 * kWaves)
@@ -65,7 +55,6 @@ h_hn_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint3
   // Both index lists of a cell sit in registers (entry lane + 64 j in slot j; past the end: bit 31, "skip") and are
   // requested one cell ahead, the parent index and the child / mask word two cells ahead (file header)
   constexpr int KF = (N + 63) / 64;
-  constexpr uint32_t kSkip = 0x80000000u;
   const uint64_t stride = (uint64_t)gridDim.x * kWaves;
   uint64_t cell = (uint64_t)blockIdx.x * kWaves + wave;
   uint32_t word = cell < n_cells ? words[cell] : 0u;
@@ -75,8 +64,8 @@ h_hn_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint3
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
       const int t = lane + 64 * j;
-      gc[j] = (cell < n_cells && t < N) ? coarse[par * N + t] : kSkip;
-      gf[j] = (cell < n_cells && t < N) ? fine[cell * N + t] : kSkip;
+      gc[j] = (cell < n_cells && t < N) ? coarse[par * N + t] : kTransferSkip;
+      gf[j] = (cell < n_cells && t < N) ? fine[cell * N + t] : kTransferSkip;
     }
   }
   uint32_t next_par = cell + stride < n_cells ? parent[cell + stride] : 0u;
@@ -97,12 +86,12 @@ h_hn_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint3
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
       const int t = lane + 64 * j;
-      next_gc[j] = (next < n_cells && t < N) ? coarse[(uint64_t)next_par * N + t] : kSkip;
-      next_gf[j] = (next < n_cells && t < N) ? fine[next * N + t] : kSkip;
+      next_gc[j] = (next < n_cells && t < N) ? coarse[(uint64_t)next_par * N + t] : kTransferSkip;
+      next_gf[j] = (next < n_cells && t < N) ? fine[next * N + t] : kTransferSkip;
     }
     // one wave owns one cell: the word is the same in all lanes, say so (scalar branches and a scalar matrix offset)
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
-    const uint32_t m = w & 0x1ffu, child = w >> 16;
+    const uint32_t m = transfer_word_mask(w), child = transfer_word_child(w);
     wave_sync();
     if (!RESTRICT && m) hn_resolve_wave<dim, false, KF>(in, W, n, m, lane);  // C_p on the gathered coarse values
     if (child) {  // (uniform) child = 0: the same cell, E is the identity
@@ -139,160 +128,28 @@ h_hn_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint3
         const uint32_t g = gc[j];
         if (t < N && !(g >> 31)) atomicAdd(dst + g, in[t]);  // several cells share the coarse dof; Dirichlet dofs are skipped
       }
-      gc[j] = next_gc[j];
-      gf[j] = next_gf[j];
     }
+    wave_hand_over(gc, gf, next_gc, next_gf);
     word = next_word;
     next_par = after_par;
     next_word = after_word;
   }
 }
 
-template <typename T, bool RESTRICT, bool ADD>
-hipError_t launch_h(const mfgpu_transfer *t, T *dst, const T *src, hipStream_t st) {
-  const uint32_t n = t->n_fine_cells;
-  if (n == 0) return hipSuccess;
-  const unsigned groups = (n + kWaves - 1) / kWaves;
-  const unsigned grid = groups < kMaxGrid ? groups : kMaxGrid;
-#define TRH_CASE(D, PP)                                                                                               \
-  case D * 10 + PP:                                                                                                   \
-    hipLaunchKernelGGL((h_hn_transfer_kernel<D, PP, T, RESTRICT, ADD>), dim3(grid), dim3(64 * kWaves), 0, st, dst, src,  \
-                       t->d_coarse.get(), t->d_fine.get(), t->d_parent.get(), t->d_mask.get(), t->d_p1.as<const T>(), \
-                       t->d_weights.as<const T>(), n);                                                                \
-    break;
-  switch (t->dim * 10 + t->degree) {
-    TRH_CASE(2, 1) TRH_CASE(2, 2) TRH_CASE(2, 3) TRH_CASE(2, 4) TRH_CASE(2, 5) TRH_CASE(2, 6)
-    TRH_CASE(3, 1) TRH_CASE(3, 2) TRH_CASE(3, 3) TRH_CASE(3, 4) TRH_CASE(3, 5) TRH_CASE(3, 6)
-    default: return hipErrorInvalidValue;
-  }
-#undef TRH_CASE
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_mode(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {
-  switch (mode) {
-    case TRANSFER_PROLONGATE: return launch_h<T, false, false>(t, (T *)dst, (const T *)src, st);
-    case TRANSFER_PROLONGATE_ADD: return launch_h<T, false, true>(t, (T *)dst, (const T *)src, st);
-    case TRANSFER_RESTRICT_ADD: return launch_h<T, true, false>(t, (T *)dst, (const T *)src, st);
-  }
-  return hipErrorInvalidValue;
-}
-
 }  // namespace
 
+template <typename T>
 hipError_t launch_h_hn_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {
-  return t->number_type == MFGPU_F64 ? launch_mode<double>(t, dst, src, mode, st) : launch_mode<float>(t, dst, src, mode, st);
+  const uint32_t n = t->n_fine_cells;
+  if (n == 0) return hipSuccess;
+  return dispatch_kernel<1>(t, mode, [&](auto D, auto P, auto R, auto A) {
+    hipLaunchKernelGGL((h_hn_transfer_kernel<D(), P(), T, R(), A()>), dim3(wave_grid(n)), dim3(64 * kWaves), 0, st, (T *)dst,
+                       (const T *)src, t->d_coarse.get(), t->d_fine.get(), t->d_parent.get(), t->d_mask.get(),
+                       t->d_p1.as<const T>(), t->d_weights.as<const T>(), n);
+    return hipGetLastError();
+  });
 }
+template hipError_t launch_h_hn_transfer<double>(const mfgpu_transfer *, void *, const void *, TransferMode, hipStream_t);
+template hipError_t launch_h_hn_transfer<float>(const mfgpu_transfer *, void *, const void *, TransferMode, hipStream_t);
 
 }  // namespace mfgpu
-
-extern "C" {
-
-int mfgpu_transfer_create_h_hn(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
-                               const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, const uint32_t *parent,
-                               const uint32_t *child, uint32_t n_coarse_dofs, uint32_t n_fine_dofs,
-                               const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet, const double *prolongation_1d,
-                               const uint32_t *coarse_mask, const uint32_t *fine_mask, const double *constraint_weights,
-                               mfgpu_transfer **out) {
-  using namespace mfgpu;
-  const char *who = "mfgpu_transfer_create_h_hn";
-  if (!out || (dim != 2 && dim != 3) || degree < 1 || degree > 6 || (n_coarse_cells && !coarse_cell_dofs) ||
-      (n_fine_cells && (!fine_cell_dofs || !parent || !child)) || (n_coarse_dirichlet && !coarse_dirichlet) ||
-      !valid_number_type(number_type) || n_coarse_dofs >= (1u << 31) || n_fine_dofs >= (1u << 31)) {
-    set_error(std::string(who) + ": bad argument (1 <= degree <= 6, dim 2 or 3, dof counts < 2^31, arrays)");
-    return MFGPU_EINVAL;
-  }
-  const int n = degree + 1;
-  const size_t N = (size_t)ipow(n, dim);
-  std::vector<uint8_t> dir(n_coarse_dofs, 0);
-  for (uint32_t i = 0; i < n_coarse_dirichlet; ++i) {
-    if (coarse_dirichlet[i] >= n_coarse_dofs) {
-      set_error(std::string(who) + ": Dirichlet dof out of range");
-      return MFGPU_EINVAL;
-    }
-    dir[coarse_dirichlet[i]] = 1;
-  }
-  std::vector<uint32_t> cd((size_t)n_coarse_cells * N), fd((size_t)n_fine_cells * N), words(n_fine_cells);
-  for (size_t i = 0; i < cd.size(); ++i) {
-    const uint32_t g = coarse_cell_dofs[i];
-    if (g >= n_coarse_dofs) {
-      set_error(std::string(who) + ": coarse dof out of range");
-      return MFGPU_EINVAL;
-    }
-    cd[i] = g | (dir[g] ? 0x80000000u : 0u);
-  }
-  for (uint32_t c = 0; c < n_coarse_cells; ++c)
-    if (coarse_mask && !valid_mask(dim, coarse_mask[c])) {
-      set_error(std::string(who) + ": a coarse constraint mask has bits outside the defined ones (9 in 3D; TYPE x, y and "
-                "FACE x, y in 2D)");
-      return MFGPU_EINVAL;
-    }
-  for (uint32_t f = 0; f < n_fine_cells; ++f) {
-    if (parent[f] >= n_coarse_cells || child[f] > (1u << dim)) {
-      set_error(std::string(who) + ": parent out of range or child > 2^dim");
-      return MFGPU_EINVAL;
-    }
-    words[f] = (coarse_mask ? coarse_mask[parent[f]] : 0u) | (child[f] << 16);
-  }
-  size_t covered = 0;
-  int rc;
-  if ((rc = p_owner_list(who, dim, degree, n_fine_cells, fine_cell_dofs, fine_mask, n_fine_dofs, fd.data(), covered)))
-    return rc;
-  std::vector<double> P1, W;
-  if (prolongation_1d)
-    P1.assign(prolongation_1d, prolongation_1d + (size_t)(2 * degree + 1) * n);
-  else
-    default_prolongation_1d(degree, P1);
-  if (constraint_weights)
-    W.assign(constraint_weights, constraint_weights + (size_t)n * n);
-  else
-    fe_q_constraint_weights(degree, W);
-  std::unique_ptr<mfgpu_transfer> t(new mfgpu_transfer());
-  t->kind = TRANSFER_KIND_H_HN;
-  t->dim = dim;
-  t->degree = degree;
-  t->number_type = number_type;
-  t->n_coarse_cells = n_coarse_cells;
-  t->n_fine_cells = n_fine_cells;
-  t->n_coarse_dofs = n_coarse_dofs;
-  t->n_fine_dofs = n_fine_dofs;
-  t->covers_all = covered == n_fine_dofs;
-  t->hanging_nodes = true;
-  std::vector<float> P1f(P1.begin(), P1.end()), Wf(W.begin(), W.end());
-  const bool f64 = number_type == MFGPU_F64;
-  if ((rc = t->d_coarse.upload(cd.data(), cd.size())) || (rc = t->d_fine.upload(fd.data(), fd.size())) ||
-      (rc = t->d_parent.upload(parent, n_fine_cells)) || (rc = t->d_mask.upload(words.data(), words.size())) ||
-      (rc = t->d_p1.upload(f64 ? (const void *)P1.data() : (const void *)P1f.data(), P1.size() * esize(number_type))) ||
-      (rc = t->d_weights.upload(f64 ? (const void *)W.data() : (const void *)Wf.data(), W.size() * esize(number_type))))
-    return rc;
-  t->device_bytes = t->d_coarse.bytes() + t->d_fine.bytes() + t->d_parent.bytes() + t->d_mask.bytes() + t->d_p1.bytes() +
-                    t->d_weights.bytes();
-  *out = t.release();
-  return 0;
-}
-
-int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
-  using namespace mfgpu;
-  if (!coarse || !fine || !out) {
-    set_error("mfgpu_transfer_create_h_hn_from_meshes: null argument");
-    return MFGPU_EINVAL;
-  }
-  const Mesh &C = coarse->mesh, &F = fine->mesh;
-  if (C.cells_kind != -1 || F.cells_kind != -1 || C.cell_levels.empty() || F.cell_levels.empty() || C.dim != F.dim ||
-      C.degree != F.degree) {
-    set_error("mfgpu_transfer_create_h_hn_from_meshes: needs two leaf meshes (adaptive, from leaves) of one dimension and "
-              "one degree");
-    return MFGPU_EINVAL;
-  }
-  std::vector<uint32_t> parent(F.n_cells), child(F.n_cells);
-  int rc = mfgpu_mesh_coarsening_map(coarse, fine, parent.data(), child.data());
-  if (rc) return rc;
-  return mfgpu_transfer_create_h_hn(C.dim, C.degree, F.number_type, C.n_cells, F.n_cells, C.loc2glob.data(), F.loc2glob.data(),
-                                    parent.data(), child.data(), C.n_dofs, F.n_dofs, C.constrained.data(),
-                                    (uint32_t)C.constrained.size(), nullptr,
-                                    C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(),
-                                    F.constraint_mask.empty() ? nullptr : F.constraint_mask.data(), C.weights.data(), out);
-}
-
-}  // extern "C"

@@ -1034,60 +1034,54 @@ class Level:
 
 
 class Transfer:
-    """MGTransferMatrixFreeGpu between two globally refined levels (mfgpu_transfer_*), or between two degrees on one mesh
-    (p_from_arrays / p_from_meshes: p-multigrid); the calls are the same for both."""
+    """A multigrid transfer (mfgpu_transfer_*) of one of three kinds: between two globally refined levels at one degree
+    (from_arrays / from_meshes, MGTransferMatrixFreeGpu), between two degrees on one mesh (p_from_arrays / p_hn_from_arrays
+    / p_from_meshes / p_hn_from_meshes: p-multigrid, with or without hanging nodes), and between two leaf meshes with
+    hanging nodes at one degree (h_hn_from_arrays / h_hn_from_meshes: global coarsening); the calls are the same for all."""
 
     def __init__(self, handle):
         self._h = handle
 
+    @staticmethod
+    def _arg(a, dtype):
+        """(contiguous array or None, its address or None): None and an empty array are the library's null pointer"""
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        return a, a.ctypes.data if a.size else None
+
     @classmethod
-    def from_arrays(cls, dim, degree, coarse_cell_dofs, fine_patch_dofs, n_coarse_dofs, n_fine_dofs, coarse_dirichlet,
-                    number_type=F64, prolongation_1d=None):
-        cd = np.ascontiguousarray(coarse_cell_dofs, dtype=np.uint32)
-        fd = np.ascontiguousarray(fine_patch_dofs, dtype=np.uint32)
-        di = np.ascontiguousarray(coarse_dirichlet, dtype=np.uint32)
-        p1 = None if prolongation_1d is None else np.ascontiguousarray(prolongation_1d, dtype=np.float64)
-        n_cells = cd.size // ((degree + 1) ** dim)
-        assert fd.size == n_cells * (2 * degree + 1) ** dim
+    def _create(cls, creator, *args):
         h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create(dim, degree, number_type, n_cells, cd.ctypes.data, fd.ctypes.data, n_coarse_dofs,
-                                           n_fine_dofs, di.ctypes.data if di.size else None, di.size,
-                                           None if p1 is None else p1.ctypes.data, C.byref(h)))
+        _check(getattr(lib(), creator)(*args, C.byref(h)))
         return cls(h)
 
     @classmethod
+    def from_arrays(cls, dim, degree, coarse_cell_dofs, fine_patch_dofs, n_coarse_dofs, n_fine_dofs, coarse_dirichlet,
+                    number_type=F64, prolongation_1d=None):
+        (cd, cdp), (fd, fdp) = cls._arg(coarse_cell_dofs, np.uint32), cls._arg(fine_patch_dofs, np.uint32)
+        (di, dip), (_, p1p) = cls._arg(coarse_dirichlet, np.uint32), cls._arg(prolongation_1d, np.float64)
+        n_cells = cd.size // ((degree + 1) ** dim)
+        assert fd.size == n_cells * (2 * degree + 1) ** dim
+        return cls._create("mfgpu_transfer_create", dim, degree, number_type, n_cells, cdp, fdp, n_coarse_dofs, n_fine_dofs,
+                           dip, di.size, p1p)
+
+    @classmethod
     def from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_from_meshes(coarse._h, fine._h, C.byref(h)))
-        return cls(h)
+        return cls._create("mfgpu_transfer_create_from_meshes", coarse._h, fine._h)
 
     @classmethod
     def p_from_arrays(cls, dim, degree_coarse, degree_fine, coarse_cell_dofs, fine_cell_dofs, n_coarse_dofs, n_fine_dofs,
                       coarse_dirichlet, number_type=F64, prolongation_1d=None):
         """the p-multigrid transfer between FE_Q(degree_coarse) and FE_Q(degree_fine) on the same cells
         (mfgpu_transfer_create_p): the two descriptions' loc2glob, same cell order"""
-        cd = np.ascontiguousarray(coarse_cell_dofs, dtype=np.uint32)
-        fd = np.ascontiguousarray(fine_cell_dofs, dtype=np.uint32)
-        di = np.ascontiguousarray(coarse_dirichlet, dtype=np.uint32)
-        p1 = None if prolongation_1d is None else np.ascontiguousarray(prolongation_1d, dtype=np.float64)
-        ncd, nfd = (max(int(degree_coarse), 0) + 1) ** dim, (max(int(degree_fine), 0) + 1) ** dim
-        n_cells = cd.size // ncd
-        if 1 <= degree_coarse < degree_fine <= 6:  # (any other pair is the library's MFGPU_EINVAL)
-            assert cd.size == n_cells * ncd and fd.size == n_cells * nfd
-            assert p1 is None or p1.size == (degree_coarse + 1) * (degree_fine + 1)
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_p(dim, degree_coarse, degree_fine, number_type, n_cells,
-                                             cd.ctypes.data if cd.size else None, fd.ctypes.data if fd.size else None,
-                                             n_coarse_dofs, n_fine_dofs, di.ctypes.data if di.size else None, di.size,
-                                             None if p1 is None else p1.ctypes.data, C.byref(h)))
-        return cls(h)
+        return cls.p_hn_from_arrays(dim, degree_coarse, degree_fine, coarse_cell_dofs, fine_cell_dofs, n_coarse_dofs,
+                                    n_fine_dofs, coarse_dirichlet, number_type, prolongation_1d)
 
     @classmethod
     def p_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
         """mfgpu_transfer_create_p_from_meshes: two stand-in meshes of the same cells, the degree rises"""
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_p_from_meshes(coarse._h, fine._h, C.byref(h)))
-        return cls(h)
+        return cls._create("mfgpu_transfer_create_p_from_meshes", coarse._h, fine._h)
 
     @classmethod
     def p_hn_from_arrays(cls, dim, degree_coarse, degree_fine, coarse_cell_dofs, fine_cell_dofs, n_coarse_dofs, n_fine_dofs,
@@ -1096,12 +1090,9 @@ class Transfer:
         """p_from_arrays on cells with hanging nodes (mfgpu_transfer_create_p_hn): constraint_mask [n_cells] is the one of
         both descriptions (None: conforming), coarse_constraint_weights [(degree_coarse + 1)^2] the coarse description's
         constraint_weights (None: those of FE_Q(degree_coarse))"""
-        cd = np.ascontiguousarray(coarse_cell_dofs, dtype=np.uint32)
-        fd = np.ascontiguousarray(fine_cell_dofs, dtype=np.uint32)
-        di = np.ascontiguousarray(coarse_dirichlet, dtype=np.uint32)
-        p1 = None if prolongation_1d is None else np.ascontiguousarray(prolongation_1d, dtype=np.float64)
-        cm = None if constraint_mask is None else np.ascontiguousarray(constraint_mask, dtype=np.uint32)
-        w = None if coarse_constraint_weights is None else np.ascontiguousarray(coarse_constraint_weights, dtype=np.float64)
+        (cd, cdp), (fd, fdp) = cls._arg(coarse_cell_dofs, np.uint32), cls._arg(fine_cell_dofs, np.uint32)
+        (di, dip), (p1, p1p) = cls._arg(coarse_dirichlet, np.uint32), cls._arg(prolongation_1d, np.float64)
+        (cm, cmp_), (w, wp) = cls._arg(constraint_mask, np.uint32), cls._arg(coarse_constraint_weights, np.float64)
         ncd, nfd = (max(int(degree_coarse), 0) + 1) ** dim, (max(int(degree_fine), 0) + 1) ** dim
         n_cells = cd.size // ncd
         if 1 <= degree_coarse < degree_fine <= 6:  # (any other pair is the library's MFGPU_EINVAL)
@@ -1109,22 +1100,14 @@ class Transfer:
             assert p1 is None or p1.size == (degree_coarse + 1) * (degree_fine + 1)
             assert cm is None or cm.size == n_cells
             assert w is None or w.size == (degree_coarse + 1) ** 2
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_p_hn(dim, degree_coarse, degree_fine, number_type, n_cells,
-                                                cd.ctypes.data if cd.size else None, fd.ctypes.data if fd.size else None,
-                                                n_coarse_dofs, n_fine_dofs, di.ctypes.data if di.size else None, di.size,
-                                                None if p1 is None else p1.ctypes.data,
-                                                None if cm is None else cm.ctypes.data,
-                                                None if w is None else w.ctypes.data, C.byref(h)))
-        return cls(h)
+        return cls._create("mfgpu_transfer_create_p_hn", dim, degree_coarse, degree_fine, number_type, n_cells, cdp, fdp,
+                           n_coarse_dofs, n_fine_dofs, dip, di.size, p1p, cmp_, wp)
 
     @classmethod
     def p_hn_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
         """mfgpu_transfer_create_p_hn_from_meshes: what p_from_meshes accepts, and adaptive meshes or meshes from leaves
         of equal cells and masks"""
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_p_hn_from_meshes(coarse._h, fine._h, C.byref(h)))
-        return cls(h)
+        return cls._create("mfgpu_transfer_create_p_hn_from_meshes", coarse._h, fine._h)
 
     @classmethod
     def h_hn_from_arrays(cls, dim, degree, coarse_cell_dofs, fine_cell_dofs, parent, child, n_coarse_dofs, n_fine_dofs,
@@ -1133,12 +1116,11 @@ class Transfer:
         """the global-coarsening h-transfer between two meshes with hanging nodes at one degree
         (mfgpu_transfer_create_h_hn): the two descriptions' loc2glob, per fine cell its coarse cell `parent` and `child`
         (0: the same cell, 1 + k: child k), the two descriptions' constraint masks (None: none)"""
-        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)  # noqa: E731
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-        cd, fd, pa, ch, di = u32(coarse_cell_dofs), u32(fine_cell_dofs), u32(parent), u32(child), u32(coarse_dirichlet)
-        p1, w = f64(prolongation_1d), f64(constraint_weights)
-        cm = None if coarse_mask is None else u32(coarse_mask)
-        fm = None if fine_mask is None else u32(fine_mask)
+        (cd, cdp), (fd, fdp) = cls._arg(coarse_cell_dofs, np.uint32), cls._arg(fine_cell_dofs, np.uint32)
+        (pa, pap), (ch, chp) = cls._arg(parent, np.uint32), cls._arg(child, np.uint32)
+        (di, dip), (p1, p1p) = cls._arg(coarse_dirichlet, np.uint32), cls._arg(prolongation_1d, np.float64)
+        (cm, cmp_), (fm, fmp) = cls._arg(coarse_mask, np.uint32), cls._arg(fine_mask, np.uint32)
+        w, wp = cls._arg(constraint_weights, np.float64)
         nd = (max(int(degree), 0) + 1) ** dim
         n_coarse, n_fine = cd.size // nd, fd.size // nd
         if 1 <= degree <= 6 and dim in (2, 3):  # (anything else is the library's MFGPU_EINVAL)
@@ -1146,20 +1128,14 @@ class Transfer:
             assert p1 is None or p1.size == (2 * degree + 1) * (degree + 1)
             assert (cm is None or cm.size == n_coarse) and (fm is None or fm.size == n_fine)
             assert w is None or w.size == (degree + 1) ** 2
-        ptr = lambda a: None if a is None or not a.size else a.ctypes.data  # noqa: E731
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_h_hn(dim, degree, number_type, n_coarse, n_fine, ptr(cd), ptr(fd), ptr(pa), ptr(ch),
-                                                n_coarse_dofs, n_fine_dofs, ptr(di), di.size, ptr(p1), ptr(cm), ptr(fm),
-                                                ptr(w), C.byref(h)))
-        return cls(h)
+        return cls._create("mfgpu_transfer_create_h_hn", dim, degree, number_type, n_coarse, n_fine, cdp, fdp, pap, chp,
+                           n_coarse_dofs, n_fine_dofs, dip, di.size, p1p, cmp_, fmp, wp)
 
     @classmethod
     def h_hn_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
         """mfgpu_transfer_create_h_hn_from_meshes: two leaf meshes of equal degree, the fine one's leaves those of the
         coarse one or their children (a mesh and a member of its Mesh.coarsening_sequence)"""
-        h = C.c_void_p()
-        _check(lib().mfgpu_transfer_create_h_hn_from_meshes(coarse._h, fine._h, C.byref(h)))
-        return cls(h)
+        return cls._create("mfgpu_transfer_create_h_hn_from_meshes", coarse._h, fine._h)
 
     def prolongate(self, dst_fine, src_coarse, stream=None):
         _check(lib().mfgpu_transfer_prolongate(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
