@@ -556,6 +556,67 @@ static bool one_irregular(const mfgpu::Tree &T, const uint32_t *leaves, uint32_t
   return true;
 }
 
+// the cell of a ckey
+static mfgpu::Cell cell_of(uint64_t k) {
+  mfgpu::Cell c;
+  c.level = (int)(k >> 57);
+  c.c[0] = (uint32_t)(k & 0x7ffff);
+  c.c[1] = (uint32_t)((k >> 19) & 0x7ffff);
+  c.c[2] = (uint32_t)((k >> 38) & 0x7ffff);
+  return c;
+}
+
+// does the leaf P of T touch a leaf two or more levels finer over one of the offsets?  (The rollback of
+// mfgpu_mesh_coarsen_leaves and mfgpu_mesh_adapt_leaves: a new parent that does is split again.)
+static bool touched_by_two_finer(const mfgpu::Tree &T, int dim, const mfgpu::Cell &P,
+                                 const std::vector<std::array<int, 3>> &offsets) {
+  for (const auto &o : offsets) {
+    int64_t nb[3] = {(int64_t)P.c[0] + o[0], (int64_t)P.c[1] + o[1], (int64_t)P.c[2] + o[2]};
+    if (T.covering_level(P.level, nb) != -1) continue;  // outside, or covered by a leaf of P's level or coarser
+    // the neighbour's children at the shared face / edge / vertex: refined themselves?
+    for (int k = 0; k < (1 << dim); ++k) {
+      int64_t ch[3] = {0, 0, 0};
+      bool at = true;
+      for (int d = 0; d < dim; ++d) {
+        const int b = (k >> d) & 1;
+        if ((o[d] == 1 && b != 0) || (o[d] == -1 && b != 1)) at = false;
+        ch[d] = 2 * nb[d] + b;
+      }
+      if (at && T.covering_level(P.level + 1, ch) == -1) return true;
+    }
+  }
+  return false;
+}
+
+// replaces the families of `parents` in T by their parents; then, until nothing changes, splits every parent again that
+// a leaf two or more levels finer touches.  A rollback only makes the set finer, so it can only force further rollbacks:
+// the fixed point does not depend on the order.  `parents` keeps the survivors
+static void coarsen_families(mfgpu::Tree &T, int dim, std::vector<mfgpu::Cell> &parents,
+                             const std::vector<std::array<int, 3>> &offsets) {
+  using namespace mfgpu;
+  for (const Cell &P : parents) {
+    for (int k = 0; k < (1 << dim); ++k) {
+      uint32_t c[3] = {0, 0, 0};
+      for (int d = 0; d < dim; ++d) c[d] = 2 * P.c[d] + ((k >> d) & 1);
+      T.active.erase(ckey(P.level + 1, c));
+    }
+    T.active.insert(ckey(P.level, P.c));
+  }
+  for (bool changed = true; changed;) {
+    changed = false;
+    std::vector<Cell> kept;
+    for (const Cell &P : parents) {
+      if (touched_by_two_finer(T, dim, P, offsets)) {
+        T.refine(P);  // back to its children
+        changed = true;
+      } else {
+        kept.push_back(P);
+      }
+    }
+    parents.swap(kept);
+  }
+}
+
 // The checks mfgpu_mesh_coarsen_leaves and mfgpu_mesh_refine_leaves share: the leaves (level, cx, cy, cz) lie in the root
 // cell, none deeper than level 18 or listed twice, they partition the root cell, and they are one-irregular over faces and,
 // in 3D, edges.  Fills T with them.
@@ -625,57 +686,10 @@ int64_t mfgpu_mesh_coarsen_leaves(int dim, const uint32_t *leaves, uint32_t n_le
     const uint32_t pc[3] = {l[1] >> 1, l[2] >> 1, l[3] >> 1};
     ++n_children[ckey((int)l[0] - 1, pc)];
   }
-  auto cell_of = [](uint64_t k) {
-    Cell c;
-    c.level = (int)(k >> 57);
-    c.c[0] = (uint32_t)(k & 0x7ffff);
-    c.c[1] = (uint32_t)((k >> 19) & 0x7ffff);
-    c.c[2] = (uint32_t)((k >> 38) & 0x7ffff);
-    return c;
-  };
   std::vector<Cell> parents;
   for (const auto &kv : n_children)
     if (kv.second == (1 << dim)) parents.push_back(cell_of(kv.first));
-  for (const Cell &P : parents) {
-    for (int k = 0; k < (1 << dim); ++k) {
-      uint32_t c[3] = {0, 0, 0};
-      for (int d = 0; d < dim; ++d) c[d] = 2 * P.c[d] + ((k >> d) & 1);
-      T.active.erase(ckey(P.level + 1, c));
-    }
-    T.active.insert(ckey(P.level, P.c));
-  }
-  // does the coarsened parent P touch a leaf two or more levels finer?
-  auto breaks = [&](const Cell &P) {
-    for (const auto &o : offsets) {
-      int64_t nb[3] = {(int64_t)P.c[0] + o[0], (int64_t)P.c[1] + o[1], (int64_t)P.c[2] + o[2]};
-      if (T.covering_level(P.level, nb) != -1) continue;  // outside, or covered by a leaf of P's level or coarser
-      // the neighbour's children at the shared face / edge: refined themselves?
-      for (int k = 0; k < (1 << dim); ++k) {
-        int64_t ch[3] = {0, 0, 0};
-        bool at = true;
-        for (int d = 0; d < dim; ++d) {
-          const int b = (k >> d) & 1;
-          if ((o[d] == 1 && b != 0) || (o[d] == -1 && b != 1)) at = false;
-          ch[d] = 2 * nb[d] + b;
-        }
-        if (at && T.covering_level(P.level + 1, ch) == -1) return true;
-      }
-    }
-    return false;
-  };
-  for (bool changed = true; changed;) {
-    changed = false;
-    std::vector<Cell> kept;
-    for (const Cell &P : parents) {
-      if (breaks(P)) {
-        T.refine(P);  // back to its children
-        changed = true;
-      } else {
-        kept.push_back(P);
-      }
-    }
-    parents.swap(kept);
-  }
+  coarsen_families(T, dim, parents, offsets);
   std::vector<uint64_t> keys(T.active.begin(), T.active.end());
   std::sort(keys.begin(), keys.end());
   for (size_t i = 0; i < keys.size(); ++i) {
@@ -742,6 +756,104 @@ int64_t mfgpu_mesh_refine_leaves(int dim, const uint32_t *leaves, uint32_t n_lea
     }
   }
   return (int64_t)n_out;
+}
+
+// Refinement and coarsening in one step.  R is what mfgpu_mesh_refine_leaves makes of the refine
+// flags.  A family is a candidate when its 2^dim children are input leaves, all with a coarsen flag, none with a refine
+// flag, and all still leaves of R (refinement wins).  The candidates become their parents; then mfgpu_mesh_coarsen_leaves'
+// rollback runs in the relation of the closure, until no surviving parent is touched by a leaf two or more levels finer.
+// A rollback only makes the set finer, so the fixed point does not depend on the order.  `new` is the result, `mid` the
+// input with exactly the surviving families replaced: a surviving parent P of level l is touched by no leaf deeper than
+// l + 1 in `new`, and an input leaf of level l + 2 next to it is in `new` itself, split, or coarsened with its own
+// surviving family, which `mid` holds too -- so `mid` is one-irregular as well.
+int64_t mfgpu_mesh_adapt_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, const uint8_t *refine_flags,
+                                const uint8_t *coarsen_flags, uint32_t balance_vertices, uint32_t *out_new,
+                                uint64_t new_capacity, uint32_t *out_mid, uint32_t *n_mid) {
+  using namespace mfgpu;
+  const char *who = "mfgpu_mesh_adapt_leaves";
+  if ((dim != 2 && dim != 3) || !leaves || !refine_flags || !coarsen_flags || !out_new || !out_mid || !n_mid ||
+      n_leaves == 0) {
+    set_error(std::string(who) + ": bad argument (dim 2 or 3, arrays, at least one leaf)");
+    return MFGPU_EINVAL;
+  }
+  Tree T;
+  if (const int rc = load_leaves(who, dim, leaves, n_leaves, T)) return rc;
+  T.balance_vertices = balance_vertices != 0;
+  const std::vector<std::array<int, 3>> offsets = neighbour_offsets(dim, T.balance_vertices);
+  if (T.balance_vertices && !one_irregular(T, leaves, n_leaves, offsets)) {
+    set_error(std::string(who) + ": balance_vertices needs leaves that are one-irregular over vertices too");
+    return MFGPU_EINVAL;
+  }
+  std::vector<Cell> flagged;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    if (!refine_flags[i]) continue;
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    if (l[0] >= 18) {
+      set_error(std::string(who) + ": a child of a flagged leaf would be deeper than level 18");
+      return MFGPU_EINVAL;
+    }
+    flagged.push_back(Cell{(int)l[0], {l[1], l[2], l[3]}});
+  }
+  T.refine_flagged(flagged);  // T holds R
+  // the candidate families, by their parents
+  auto parent_key = [](const uint32_t *l) {
+    const uint32_t pc[3] = {l[1] >> 1, l[2] >> 1, l[3] >> 1};
+    return ckey((int)l[0] - 1, pc);
+  };
+  std::unordered_map<uint64_t, int> n_willing;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    if (l[0] == 0 || !coarsen_flags[i] || refine_flags[i] || !T.is_active((int)l[0], l + 1)) continue;
+    ++n_willing[parent_key(l)];
+  }
+  std::vector<Cell> parents;
+  for (const auto &kv : n_willing)
+    if (kv.second == (1 << dim)) parents.push_back(cell_of(kv.first));
+  coarsen_families(T, dim, parents, offsets);  // the rollback of mfgpu_mesh_coarsen_leaves, over the offsets of this call
+  std::unordered_set<uint64_t> survivors;
+  for (const Cell &P : parents) survivors.insert(ckey(P.level, P.c));
+  // 0: the leaf stays or splits; 1: child 0 of a surviving family; 2: another child of one
+  auto role = [&](const uint32_t *l) {
+    if (l[0] == 0 || !survivors.count(parent_key(l))) return 0;
+    return ((l[1] | l[2] | l[3]) & 1u) ? 2 : 1;
+  };
+  uint64_t n_new = 0;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    const int r = role(l);
+    n_new += r ? (r == 1 ? 1 : 0) : T.is_active((int)l[0], l + 1) ? 1 : (1u << dim);
+  }
+  if (n_new > new_capacity) {
+    set_error(std::string(who) + ": new_capacity " + std::to_string(new_capacity) + " is too small, the adapted set has " +
+              std::to_string(n_new) + " leaves");
+    return MFGPU_EINVAL;
+  }
+  uint32_t *o = out_new, *m = out_mid;
+  for (uint32_t i = 0; i < n_leaves; ++i) {
+    const uint32_t *l = leaves + 4 * (size_t)i;
+    const int r = role(l);
+    if (r == 2) continue;
+    if (r == 1) {
+      for (uint32_t *dst : {o, m}) {
+        dst[0] = l[0] - 1;
+        for (int d = 0; d < 3; ++d) dst[1 + d] = l[1 + d] >> 1;
+      }
+      o += 4;
+      m += 4;
+      continue;
+    }
+    for (int j = 0; j < 4; ++j) *m++ = l[j];
+    if (T.is_active((int)l[0], l + 1)) {
+      for (int j = 0; j < 4; ++j) *o++ = l[j];
+      continue;
+    }
+    for (uint32_t k = 0; k < (1u << dim); ++k) {
+      *o++ = l[0] + 1;
+      for (int d = 0; d < 3; ++d) *o++ = d < dim ? 2 * l[1 + d] + ((k >> d) & 1u) : 0u;
+    }
+  }
+  *n_mid = (uint32_t)((m - out_mid) / 4);
+  return (int64_t)n_new;
 }
 
 int mfgpu_mesh_coarsening_map(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, uint32_t *parent, uint32_t *child) {

@@ -29,6 +29,12 @@ struct mfgpu_transfer {
   uint32_t n_fine_cells = 0;               // the fine lists' count (h, p: n_coarse_cells)
   mfgpu::DeviceArray<uint32_t> d_parent;   // h_hn only: the index of each fine cell's coarse cell
   bool covers_all = true;  // every fine dof is listed by some cell
+  // the interpolation image (h_hn from an _interp creator only; TransferImage::interp_*): the coarse list with owner
+  // marking, the fine cells of each coarse cell, the fine masks, J1[(p+1)^2] in number_type
+  bool interpolation = false;
+  bool interp_covers_all = true;  // interpolate stores every coarse dof
+  mfgpu::DeviceArray<uint32_t> d_interp_coarse, d_interp_kids, d_interp_fine_mask;
+  mfgpu::DeviceArray<void> d_j1;
   size_t device_bytes = 0;
 };
 
@@ -79,6 +85,9 @@ template <typename T, bool HN>
 hipError_t launch_p_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st);
 template <typename T>
 hipError_t launch_h_hn_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st);
+// mfgpu_transfer_interpolate of an h_hn object with the interpolation image (mfgpu_transfer_h.hip)
+template <typename T>
+hipError_t launch_h_hn_interpolate(const mfgpu_transfer *t, void *dst, const void *src, hipStream_t st);
 
 }  // namespace mfgpu
 

@@ -25,7 +25,8 @@
 // mfgpu_transfer_p.hip, one wave per cell) and the transfer between two leaf meshes with hanging nodes (global
 // coarsening; kernels in mfgpu_transfer_h.hip).  All creators are here: each describes what it was given as a
 // TransferInput, build_transfer_image (mfgpu_transfer_build.cpp, plain C++) checks it and makes the host image, and
-// upload_transfer turns the image into the object.  All entry points go through launch_transfer.
+// upload_transfer turns the image into the object.  The three entry points go through launch_transfer; the fourth,
+// mfgpu_transfer_interpolate, exists for leaf-mesh objects made with the interpolation image (interpolate_transfer).
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -132,6 +133,8 @@ int upload_transfer(const TransferInput &in, const TransferImage &img, mfgpu_tra
   t->n_fine_dofs = in.n_fine_dofs;
   t->hanging_nodes = img.hanging_nodes;
   t->covers_all = img.covered == in.n_fine_dofs;
+  t->interpolation = in.interpolation;
+  t->interp_covers_all = img.interp_covered == in.n_coarse_dofs;
   auto upload_numbers = [&](DeviceArray<void> &d, const std::vector<double> &v) {
     if (in.number_type == MFGPU_F64) return d.upload(v.data(), v.size() * sizeof(double));
     const std::vector<float> f(v.begin(), v.end());
@@ -144,6 +147,14 @@ int upload_transfer(const TransferInput &in, const TransferImage &img, mfgpu_tra
     return rc;
   t->device_bytes = t->d_coarse.bytes() + t->d_fine.bytes() + t->d_parent.bytes() + t->d_mask.bytes() + t->d_p1.bytes() +
                     t->d_weights.bytes();
+  if (in.interpolation) {  // the interpolation image; an object without it uploads and counts nothing more
+    if ((rc = t->d_interp_coarse.upload(img.interp_coarse.data(), img.interp_coarse.size())) ||
+        (rc = t->d_interp_kids.upload(img.interp_kids.data(), img.interp_kids.size())) ||
+        (rc = t->d_interp_fine_mask.upload(img.interp_fine_mask.data(), img.interp_fine_mask.size())) ||
+        (rc = upload_numbers(t->d_j1, img.J1)))
+      return rc;
+    t->device_bytes += t->d_interp_coarse.bytes() + t->d_interp_kids.bytes() + t->d_interp_fine_mask.bytes() + t->d_j1.bytes();
+  }
   *out = t.release();
   return 0;
 }
@@ -188,6 +199,20 @@ int apply_transfer(const char *who, const mfgpu_transfer *t, void *dst, const vo
       hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst, (size_t)t->n_fine_dofs);
   }
   HIP_TRY(launch_transfer(t, dst, src, mode, st));
+  return 0;
+}
+
+// mfgpu_transfer_interpolate of an object with the image.  Coarse Dirichlet dofs and dofs that no coarse cell owns are
+// stored by nobody: dst is zeroed first, by a kernel on the caller's stream as in apply_transfer
+int interpolate_transfer(const mfgpu_transfer *t, void *dst, const void *src, hipStream_t st) {
+  const bool f64 = t->number_type == MFGPU_F64;
+  if (!t->interp_covers_all) {
+    if (f64)
+      hipLaunchKernelGGL(zero_kernel<double>, dim3(2048), dim3(256), 0, st, (double *)dst, (size_t)t->n_coarse_dofs);
+    else
+      hipLaunchKernelGGL(zero_kernel<float>, dim3(2048), dim3(256), 0, st, (float *)dst, (size_t)t->n_coarse_dofs);
+  }
+  HIP_TRY(f64 ? launch_h_hn_interpolate<double>(t, dst, src, st) : launch_h_hn_interpolate<float>(t, dst, src, st));
   return 0;
 }
 
@@ -317,14 +342,15 @@ int mfgpu_transfer_create_p_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu
                                     C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(), C.weights.data(), out);
 }
 
-int mfgpu_transfer_create_h_hn(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
-                               const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, const uint32_t *parent,
-                               const uint32_t *child, uint32_t n_coarse_dofs, uint32_t n_fine_dofs,
-                               const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet, const double *prolongation_1d,
-                               const uint32_t *coarse_mask, const uint32_t *fine_mask, const double *constraint_weights,
-                               mfgpu_transfer **out) {
+// the two creators of the kind H_HN object; `interpolation`: with the interpolation image
+static int create_h_hn(const char *who, bool interpolation, int dim, int degree, int number_type, uint32_t n_coarse_cells,
+                       uint32_t n_fine_cells, const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs,
+                       const uint32_t *parent, const uint32_t *child, uint32_t n_coarse_dofs, uint32_t n_fine_dofs,
+                       const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet, const double *prolongation_1d,
+                       const uint32_t *coarse_mask, const uint32_t *fine_mask, const double *constraint_weights,
+                       const double *interpolation_1d, mfgpu_transfer **out) {
   mfgpu::TransferInput in;
-  in.who = "mfgpu_transfer_create_h_hn";
+  in.who = who;
   in.kind = mfgpu::TRANSFER_KIND_H_HN;
   in.dim = dim;
   in.degree = degree;
@@ -343,30 +369,78 @@ int mfgpu_transfer_create_h_hn(int dim, int degree, int number_type, uint32_t n_
   in.coarse_mask = coarse_mask;
   in.fine_mask = fine_mask;
   in.constraint_weights = constraint_weights;
+  in.interpolation = interpolation;
+  in.interpolation_1d = interpolation_1d;
   return mfgpu::create_transfer(in, out);
 }
 
-int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
+int mfgpu_transfer_create_h_hn(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
+                               const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs, const uint32_t *parent,
+                               const uint32_t *child, uint32_t n_coarse_dofs, uint32_t n_fine_dofs,
+                               const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet, const double *prolongation_1d,
+                               const uint32_t *coarse_mask, const uint32_t *fine_mask, const double *constraint_weights,
+                               mfgpu_transfer **out) {
+  return create_h_hn("mfgpu_transfer_create_h_hn", false, dim, degree, number_type, n_coarse_cells, n_fine_cells,
+                     coarse_cell_dofs, fine_cell_dofs, parent, child, n_coarse_dofs, n_fine_dofs, coarse_dirichlet,
+                     n_coarse_dirichlet, prolongation_1d, coarse_mask, fine_mask, constraint_weights, nullptr, out);
+}
+
+int mfgpu_transfer_create_h_hn_interp(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
+                                      const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs,
+                                      const uint32_t *parent, const uint32_t *child, uint32_t n_coarse_dofs,
+                                      uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                                      const double *prolongation_1d, const uint32_t *coarse_mask, const uint32_t *fine_mask,
+                                      const double *constraint_weights, const double *interpolation_1d,
+                                      mfgpu_transfer **out) {
+  return create_h_hn("mfgpu_transfer_create_h_hn_interp", true, dim, degree, number_type, n_coarse_cells, n_fine_cells,
+                     coarse_cell_dofs, fine_cell_dofs, parent, child, n_coarse_dofs, n_fine_dofs, coarse_dirichlet,
+                     n_coarse_dirichlet, prolongation_1d, coarse_mask, fine_mask, constraint_weights, interpolation_1d, out);
+}
+
+static int create_h_hn_from_meshes(const char *who, bool interpolation, const mfgpu_mesh *coarse, const mfgpu_mesh *fine,
+                                   mfgpu_transfer **out) {
   using namespace mfgpu;
   if (!coarse || !fine || !out) {
-    set_error("mfgpu_transfer_create_h_hn_from_meshes: null argument");
+    set_error(std::string(who) + ": null argument");
     return MFGPU_EINVAL;
   }
   const Mesh &C = coarse->mesh, &F = fine->mesh;
   if (C.cells_kind != -1 || F.cells_kind != -1 || C.cell_levels.empty() || F.cell_levels.empty() || C.dim != F.dim ||
       C.degree != F.degree) {
-    set_error("mfgpu_transfer_create_h_hn_from_meshes: needs two leaf meshes (adaptive, from leaves) of one dimension and "
-              "one degree");
+    set_error(std::string(who) + ": needs two leaf meshes (adaptive, from leaves) of one dimension and one degree");
     return MFGPU_EINVAL;
   }
   std::vector<uint32_t> parent(F.n_cells), child(F.n_cells);
   int rc = mfgpu_mesh_coarsening_map(coarse, fine, parent.data(), child.data());
   if (rc) return rc;
-  return mfgpu_transfer_create_h_hn(C.dim, C.degree, F.number_type, C.n_cells, F.n_cells, C.loc2glob.data(), F.loc2glob.data(),
-                                    parent.data(), child.data(), C.n_dofs, F.n_dofs, C.constrained.data(),
-                                    (uint32_t)C.constrained.size(), nullptr,
-                                    C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(),
-                                    F.constraint_mask.empty() ? nullptr : F.constraint_mask.data(), C.weights.data(), out);
+  return create_h_hn(interpolation ? "mfgpu_transfer_create_h_hn_interp" : "mfgpu_transfer_create_h_hn", interpolation, C.dim,
+                     C.degree, F.number_type, C.n_cells, F.n_cells, C.loc2glob.data(), F.loc2glob.data(), parent.data(),
+                     child.data(), C.n_dofs, F.n_dofs, C.constrained.data(), (uint32_t)C.constrained.size(), nullptr,
+                     C.constraint_mask.empty() ? nullptr : C.constraint_mask.data(),
+                     F.constraint_mask.empty() ? nullptr : F.constraint_mask.data(), C.weights.data(), nullptr, out);
+}
+
+int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
+  return create_h_hn_from_meshes("mfgpu_transfer_create_h_hn_from_meshes", false, coarse, fine, out);
+}
+
+int mfgpu_transfer_create_h_hn_interp_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out) {
+  return create_h_hn_from_meshes("mfgpu_transfer_create_h_hn_interp_from_meshes", true, coarse, fine, out);
+}
+
+int mfgpu_transfer_interpolate(mfgpu_transfer *t, void *dst_coarse, const void *src_fine, void *stream) {
+  using namespace mfgpu;
+  const char *who = "mfgpu_transfer_interpolate";
+  if (!t || !dst_coarse || !src_fine) {
+    set_error(std::string(who) + ": null argument");
+    return MFGPU_EINVAL;
+  }
+  if (t->kind != TRANSFER_KIND_H_HN || !t->interpolation) {
+    set_error(std::string(who) + ": the object has no interpolation image (make it with mfgpu_transfer_create_h_hn_interp or "
+                                 "mfgpu_transfer_create_h_hn_interp_from_meshes)");
+    return MFGPU_EINVAL;
+  }
+  return interpolate_transfer(t, dst_coarse, src_fine, (hipStream_t)stream);
 }
 
 int mfgpu_transfer_prolongate(mfgpu_transfer *t, void *dst_fine, const void *src_coarse, void *stream) {

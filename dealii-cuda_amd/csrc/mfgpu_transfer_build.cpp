@@ -100,6 +100,63 @@ void p_prolongation_1d(int pc, int pf, std::vector<double> &P1) {
   }
 }
 
+void default_interpolation_1d(int p, std::vector<double> &J1) {
+  std::vector<double> nodes, val, der;
+  gll_01(p, nodes);
+  const int n = p + 1;
+  J1.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    const double xi = i <= p / 2 ? 2.0 * nodes[i] : 2.0 * nodes[i] - 1.0;  // the nodes are symmetric: i <= p/2 <=> xi_i <= 1/2
+    lagrange_eval(nodes, xi, val, der);
+    for (int j = 0; j < n; ++j) J1[(size_t)i * n + j] = val[j];
+  }
+  // exact zeros / ones where a coarse node is a node of the child (every node at p = 1, 2)
+  for (double &v : J1)
+    if (std::fabs(v) < 1e-15) v = 0.0;
+    else if (std::fabs(v - 1.0) < 1e-15) v = 1.0;
+}
+
+namespace {
+
+// the interpolation image of a kind H_HN pair (mfgpu_transfer_build.h), after the rest of the image was checked
+int build_interpolation_image(const TransferInput &in, TransferImage &img) {
+  const int dim = in.dim, n = in.degree + 1;
+  const uint32_t nk = 1u << dim;
+  img.interp_kids.assign((size_t)in.n_coarse_cells * nk, 0u);
+  std::vector<uint32_t> seen(in.n_coarse_cells, 0u);  // bit k: child k was met; bit 2^dim: the cell itself
+  for (uint32_t f = 0; f < in.n_fine_cells; ++f) {
+    const uint32_t c = in.parent[f], ch = in.child[f], bit = ch ? 1u << (ch - 1) : 1u << nk;
+    if ((seen[c] & bit) || (ch ? seen[c] >> nk : seen[c]) != 0u)
+      return refuse(in.who, "a coarse cell is listed as the parent of the same child twice, or both as an unchanged cell "
+                            "and as a refined one");
+    seen[c] |= bit;
+    img.interp_kids[(size_t)c * nk + (ch ? ch - 1 : 0)] = ch ? f : f | kTransferSkip;
+  }
+  for (uint32_t c = 0; c < in.n_coarse_cells; ++c)
+    if (seen[c] != (1u << nk) && seen[c] != (1u << nk) - 1u)
+      return refuse(in.who, "a coarse cell is neither one fine cell (child = 0) nor all its 2^dim children: there is "
+                            "nothing to interpolate from");
+  img.interp_fine_mask.assign(in.n_fine_cells, 0u);
+  if (in.fine_mask) img.interp_fine_mask.assign(in.fine_mask, in.fine_mask + in.n_fine_cells);
+  img.interp_coarse.resize((size_t)in.n_coarse_cells * img.coarse_per_cell);
+  size_t owned;
+  if (const int rc = owner_list(in.who, dim, n, in.n_coarse_cells, in.coarse_cell_dofs, in.coarse_mask, in.n_coarse_dofs,
+                                img.interp_coarse.data(), owned))
+    return rc;
+  img.interp_covered = 0;
+  for (size_t i = 0; i < img.interp_coarse.size(); ++i) {
+    img.interp_coarse[i] |= img.coarse[i] & kTransferSkip;  // the Dirichlet dofs of the coarse side
+    if (!(img.interp_coarse[i] >> 31)) ++img.interp_covered;
+  }
+  if (in.interpolation_1d)
+    img.J1.assign(in.interpolation_1d, in.interpolation_1d + (size_t)n * n);
+  else
+    default_interpolation_1d(in.degree, img.J1);
+  return 0;
+}
+
+}  // namespace
+
 int build_transfer_image(const TransferInput &in, TransferImage &img) {
   const bool p_kind = in.kind == TRANSFER_KIND_P, h_hn = in.kind == TRANSFER_KIND_H_HN;
   const int dim = in.dim;
@@ -110,6 +167,8 @@ int build_transfer_image(const TransferInput &in, TransferImage &img) {
       in.n_fine_dofs >= (1u << 31))
     return refuse(in.who, "bad argument (dim 2 or 3, 1 <= degree <= 6, a p-transfer 1 <= degree_coarse < degree_fine <= 6, "
                           "number type, dof counts < 2^31, arrays)");
+  if (in.interpolation && !h_hn)
+    return refuse(in.who, "the interpolation image exists for the transfer between two leaf meshes only");
   // entries per direction of a cell's coarse list, of its fine list, and rows of P1
   const int pc = p_kind ? in.degree_coarse : in.degree;
   const int nc = pc + 1, nf = in.kind == TRANSFER_KIND_H ? 2 * in.degree + 1 : in.degree + 1;
@@ -159,7 +218,7 @@ int build_transfer_image(const TransferInput &in, TransferImage &img) {
     img.W.assign(in.constraint_weights, in.constraint_weights + (size_t)nc * nc);
   else if (img.hanging_nodes)
     fe_q_constraint_weights(pc, img.W);
-  return 0;
+  return in.interpolation ? build_interpolation_image(in, img) : 0;
 }
 
 }  // namespace mfgpu

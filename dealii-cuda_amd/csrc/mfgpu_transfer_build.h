@@ -8,6 +8,13 @@
 //   words        kind P with masks: per cell its constraint mask.  Kind H_HN: per FINE cell the parent's coarse mask in
 //                bits 0..8 and `child` in bits 16..19 (transfer_word)
 //   parent       kind H_HN: per fine cell the index of its coarse cell
+// Kind H_HN with TransferInput::interpolation also carries the interpolation image (mfgpu_transfer_interpolate):
+//   interp_coarse     per coarse cell its dofs; bit 31: another coarse cell owns the dof (the owner rule with the coarse
+//                     lists and the COARSE mask), or it is a Dirichlet dof of the coarse side (never written)
+//   interp_kids       per coarse cell 2^dim fine cell indices, entry k its child k; an unchanged cell: entry 0 the fine
+//                     cell that it is, with bit 31 as the marker, the other entries 0
+//   interp_fine_mask  per fine cell its own (fine) constraint mask
+//   J1                [(p+1) * (p+1)], row i: the child's basis at the coarse node i (default_interpolation_1d)
 // Owner rule: the owner of a fine dof is the first cell, in cell order, that lists it at a position its mask does not
 // constrain (no mask: the first that lists it).  Every fine dof is stored by its owner alone and enters a restriction
 // through its owner alone.
@@ -46,6 +53,8 @@ struct TransferInput {
   const uint32_t *coarse_mask = nullptr, *fine_mask = nullptr;
   const double *constraint_weights = nullptr;  // of the coarse degree; null: FE_Q's
   const uint32_t *parent = nullptr, *child = nullptr;  // kind H_HN
+  bool interpolation = false;                // kind H_HN: build the interpolation image too
+  const double *interpolation_1d = nullptr;  // null: default_interpolation_1d
 };
 
 struct TransferImage {
@@ -54,6 +63,10 @@ struct TransferImage {
   std::vector<double> P1, W;  // W: empty unless hanging_nodes
   bool hanging_nodes = false;  // the kernels resolve hanging nodes on the coarse side (words and W are present)
   size_t covered = 0;          // the number of fine dofs with an owner
+  // the interpolation image; empty unless TransferInput::interpolation
+  std::vector<uint32_t> interp_coarse, interp_kids, interp_fine_mask;
+  std::vector<double> J1;
+  size_t interp_covered = 0;  // the number of coarse dofs that interpolate stores
 };
 
 // Validates `in` and fills `img`.  0, or MFGPU_EINVAL with a message that begins with in.who.
@@ -73,6 +86,9 @@ int owner_list(const char *who, int dim, int n, uint32_t n_cells, const uint32_t
 void default_prolongation_1d(int p, std::vector<double> &P1);
 // P1[X * (pc+1) + x] = phi_x(xi_X): the FE_Q(pc) Lagrange basis on its Gauss-Lobatto nodes at the FE_Q(pf) nodes
 void p_prolongation_1d(int pc, int pf, std::vector<double> &P1);
+// J1[i * (p+1) + j] = phi_j(2 xi_i - b(i)), b(i) = 0 if xi_i <= 1/2 else 1: the basis of the child that holds the coarse
+// node xi_i, at that node.  Rows 0..p/2 belong to the lower child, the others to the upper one
+void default_interpolation_1d(int p, std::vector<double> &J1);
 
 }  // namespace mfgpu
 

@@ -30,6 +30,8 @@
 // (parent -> coarse index -> value) is hidden by requesting the parent word TWO cells ahead: when the lists of the next
 // cell are requested its parent has been in a register for a whole cell.
 // The creator is in mfgpu_transfer.hip; what the kernel shares with the p kernel in mfgpu_transfer_wave.h.
+// The second kernel of this file, h_hn_interpolate_kernel, is the interpolation of the same object from the fine to the
+// coarse mesh (one wave per COARSE cell); its mapping and byte model stand in front of it.
 #include <hip/hip_runtime.h>
 
 #include "mfgpu_transfer.h"
@@ -136,7 +138,152 @@ h_hn_transfer_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint3
   }
 }
 
+// mfgpu_transfer_interpolate: the fine function's nodal interpolant on the coarse mesh, per
+// include/mfgpu.h.  One wave per COARSE cell on the skeleton above.  An unchanged cell gathers its one fine cell, resolves
+// the FINE mask and stores.  A refined cell loops over its 2^dim children (the trip count is wave-uniform): each child is
+// gathered, resolved where it has a mask, and contracted per direction with the rows of J1 that lie in its half only
+// (rows 0..p/2 the lower, the others the upper half), at the positions that lie in its sub-block in the directions done
+// so far; the sub-blocks of the children partition the N positions, so every lane keeps the results of its entries
+// (lane + 64 j) in registers over the loop and the cell is stored once, by the owner, with plain stores.
+// Requested ahead: the coarse owner list and the first fine cell's index one coarse cell ahead, the fine list and the
+// fine mask one FINE cell ahead (the next child, or the next coarse cell's first fine cell).
+// Byte model per coarse cell (N = n^dim, T = 8 or 4 bytes, c = 1 for an unchanged and 2^dim for a refined cell):
+//   4 N coarse indices (owner marking), 4 * 2^dim fine cell indices, c * (4 N fine indices + 4 (mask) + N T source
+//   entries), and the owned part of N T entries stored.
+// At p = 4 in 3D for a refined cell: 500 + 32 + 8 * (504 + 1000) B read, at most 1000 B written; the fine side dominates
+// as it does for restrict_and_add of the same pair, which reads the same fine lists and entries.
+template <int dim, int n>
+__device__ __forceinline__ bool in_child_block(int t, int k, int upto) {
+  constexpr int H = (n - 1) / 2 + 1;  // rows of the lower half
+  bool ok = true;
+#pragma unroll
+  for (int d = 0; d < dim; ++d) {
+    const int c = (t / (d == 0 ? 1 : d == 1 ? n : n * n)) % n;
+    if (d <= upto) ok = ok && (((k >> d) & 1) ? c >= H : c < H);
+  }
+  return ok;
+}
+
+template <int dim, int p, typename T>
+__global__ void __launch_bounds__(64 * kWaves)
+h_hn_interpolate_kernel(T *__restrict__ dst, const T *__restrict__ src, const uint32_t *__restrict__ coarse_owned,
+                        const uint32_t *__restrict__ fine, const uint32_t *__restrict__ kids,
+                        const uint32_t *__restrict__ fine_mask, const T *__restrict__ j1, const T *__restrict__ hn_weights,
+                        uint32_t n_cells) {
+  constexpr int n = p + 1, N = ipow_c(n, dim), NK = 1 << dim;
+  __shared__ T buf[kWaves][2][N], J[2 * n * n];  // J1[n * n], then W[n * n]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int t = threadIdx.x; t < n * n; t += 64 * kWaves) {
+    J[t] = j1[t];
+    J[n * n + t] = hn_weights[t];
+  }
+  const T *W = J + n * n;
+  __syncthreads();
+  constexpr int KF = (N + 63) / 64;
+  constexpr uint32_t kIndex = ~kTransferSkip;
+  const uint64_t stride = (uint64_t)gridDim.x * kWaves;
+  uint64_t cell = (uint64_t)blockIdx.x * kWaves + wave;
+  uint32_t first = cell < n_cells ? kids[cell * NK] : 0u;  // fine cell 0 of the cell; bit 31: it is the cell itself
+  uint32_t fm = cell < n_cells ? fine_mask[first & kIndex] : 0u;
+  uint32_t gc[KF], gf[KF];
+#pragma unroll
+  for (int j = 0; j < KF; ++j) {
+    const int t = lane + 64 * j;
+    gc[j] = (cell < n_cells && t < N) ? coarse_owned[cell * N + t] : kTransferSkip;
+    gf[j] = (cell < n_cells && t < N) ? fine[(uint64_t)(first & kIndex) * N + t] & kIndex : 0u;
+  }
+  for (; cell < n_cells; cell += stride) {
+    const uint64_t next = cell + stride;
+    const uint32_t next_first = next < n_cells ? kids[next * NK] : 0u;
+    uint32_t next_gc[KF];
+#pragma unroll
+    for (int j = 0; j < KF; ++j) {
+      const int t = lane + 64 * j;
+      next_gc[j] = (next < n_cells && t < N) ? coarse_owned[next * N + t] : kTransferSkip;
+    }
+    // one wave owns one cell: say so (a scalar trip count, scalar branches)
+    const bool same = (uint32_t)__builtin_amdgcn_readfirstlane((int)first) >> 31;
+    const int n_kids = same ? 1 : NK;
+    T r[KF];
+#pragma unroll
+    for (int j = 0; j < KF; ++j) r[j] = T(0);
+    for (int k = 0; k < n_kids; ++k) {
+      T *in = buf[wave][0], *out = buf[wave][1];
+      wave_sync();  // the previous fine cell's last reads of its arrays come first
+#pragma unroll
+      for (int j = 0; j < KF; ++j) {
+        const int t = lane + 64 * j;
+        if (t < N) in[t] = src[gf[j]];  // every entry as it stands, whoever owns it
+      }
+      const bool more = k + 1 < n_kids, valid = more || next < n_cells;
+      const uint32_t nf = (more ? kids[cell * NK + k + 1] : next_first) & kIndex;
+      const uint32_t next_fm = valid ? fine_mask[nf] : 0u;
+      uint32_t next_gf[KF];
+#pragma unroll
+      for (int j = 0; j < KF; ++j) {
+        const int t = lane + 64 * j;
+        next_gf[j] = (valid && t < N) ? fine[(uint64_t)nf * N + t] & kIndex : 0u;
+      }
+      const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)fm);
+      wave_sync();
+      if (m) hn_resolve_wave<dim, false, KF>(in, W, n, m, lane);  // C_p of the FINE mask on the gathered values
+      if (!same) {
+#pragma unroll
+        for (int d = 0; d < dim; ++d) {
+          const int lo = d == 0 ? 1 : d == 1 ? n : n * n;
+#pragma unroll
+          for (int j = 0; j < KF; ++j) {
+            const int t = lane + 64 * j;
+            if (t < N && in_child_block<dim, n>(t, k, d)) {
+              const int o = (t / lo) % n;
+              const T *v = in + (t - o * lo), *row = J + o * n;
+              T s = T(0);
+#pragma unroll
+              for (int i = 0; i < n; ++i) s += row[i] * v[i * lo];
+              out[t] = s;
+            }
+          }
+          wave_sync();
+          T *tmp = in;
+          in = out;
+          out = tmp;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KF; ++j) {
+        const int t = lane + 64 * j;
+        if (t < N && (same || in_child_block<dim, n>(t, k, dim - 1))) r[j] = in[t];
+      }
+#pragma unroll
+      for (int j = 0; j < KF; ++j) gf[j] = next_gf[j];
+      fm = next_fm;
+    }
+#pragma unroll
+    for (int j = 0; j < KF; ++j) {
+      const int t = lane + 64 * j;
+      const uint32_t g = gc[j];
+      if (t < N && !(g >> 31)) dst[g] = r[j];  // one owner per coarse dof: no atomics
+      gc[j] = next_gc[j];
+    }
+    first = next_first;
+  }
+}
+
 }  // namespace
+
+template <typename T>
+hipError_t launch_h_hn_interpolate(const mfgpu_transfer *t, void *dst, const void *src, hipStream_t st) {
+  const uint32_t n = t->n_coarse_cells;
+  if (n == 0) return hipSuccess;
+  return dispatch_dim_degree<1>(t->dim, t->degree, [&](auto D, auto P) {
+    hipLaunchKernelGGL((h_hn_interpolate_kernel<D(), P(), T>), dim3(wave_grid(n)), dim3(64 * kWaves), 0, st, (T *)dst,
+                       (const T *)src, t->d_interp_coarse.get(), t->d_fine.get(), t->d_interp_kids.get(),
+                       t->d_interp_fine_mask.get(), t->d_j1.as<const T>(), t->d_weights.as<const T>(), n);
+    return hipGetLastError();
+  });
+}
+template hipError_t launch_h_hn_interpolate<double>(const mfgpu_transfer *, void *, const void *, hipStream_t);
+template hipError_t launch_h_hn_interpolate<float>(const mfgpu_transfer *, void *, const void *, hipStream_t);
 
 template <typename T>
 hipError_t launch_h_hn_transfer(const mfgpu_transfer *t, void *dst, const void *src, TransferMode mode, hipStream_t st) {

@@ -133,6 +133,8 @@ SYMBOLS = [
     "mfgpu_mesh_coarsen_leaves", "mfgpu_mesh_coarsening_map", "mfgpu_transfer_create_h_hn",
     "mfgpu_transfer_create_h_hn_from_meshes",
     "mfgpu_integrator_recovery_indicator", "mfgpu_mesh_refine_leaves",
+    "mfgpu_mesh_adapt_leaves", "mfgpu_transfer_create_h_hn_interp", "mfgpu_transfer_create_h_hn_interp_from_meshes",
+    "mfgpu_transfer_interpolate",
 ]
 
 _lib = None
@@ -315,6 +317,12 @@ def lib():
         L.mfgpu_integrator_recovery_indicator.argtypes = [vp, vp, vp, vp, vp]
         L.mfgpu_mesh_refine_leaves.argtypes = [i, vp, u32, vp, u32, vp, C.c_uint64]
         L.mfgpu_mesh_refine_leaves.restype = C.c_int64
+        L.mfgpu_mesh_adapt_leaves.argtypes = [i, vp, u32, vp, vp, u32, vp, C.c_uint64, vp, C.POINTER(u32)]
+        L.mfgpu_mesh_adapt_leaves.restype = C.c_int64
+        L.mfgpu_transfer_create_h_hn_interp.argtypes = [i, i, i, u32, u32, vp, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, vp,
+                                                        vp, C.POINTER(vp)]
+        L.mfgpu_transfer_create_h_hn_interp_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
+        L.mfgpu_transfer_interpolate.argtypes = [vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -422,6 +430,41 @@ class Mesh:
         return Mesh.from_leaves(dim, int(self.desc.degree) if degree is None else int(degree),
                                 Mesh.refine_leaves(dim, leaves, flags, balance_vertices),
                                 number_type=int(self.desc.number_type) if number_type is None else number_type)
+
+    @staticmethod
+    def adapt_leaves(dim, leaves, refine, coarsen, balance_vertices=False):
+        """one step of refinement and coarsening of the leaves (level, cx, cy, cz) (mfgpu_mesh_adapt_leaves): (new, mid),
+        [n_new, 4] and [n_mid, 4].  Refinement wins; a family of siblings that all carry a coarsen flag becomes its parent
+        unless that breaks one-irregularity; `mid` is the input with exactly those families replaced, the common
+        coarsening of the input and `new`; host only"""
+        lv = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 4)
+        rf = np.ascontiguousarray(np.asarray(refine) != 0, dtype=np.uint8).reshape(-1)
+        cf = np.ascontiguousarray(np.asarray(coarsen) != 0, dtype=np.uint8).reshape(-1)
+        if len(rf) != len(lv) or len(cf) != len(lv):
+            raise MfgpuError("Mesh.adapt_leaves: one refine flag and one coarsen flag per leaf")
+        cap = max(len(lv), 1) * 2 ** dim  # no leaf splits twice
+        new, mid = np.zeros((cap, 4), dtype=np.uint32), np.zeros((max(len(lv), 1), 4), dtype=np.uint32)
+        n_mid = C.c_uint32(0)
+        n = lib().mfgpu_mesh_adapt_leaves(dim, lv.ctypes.data if len(lv) else None, len(lv),
+                                          rf.ctypes.data if len(rf) else None, cf.ctypes.data if len(cf) else None,
+                                          int(bool(balance_vertices)), new.ctypes.data, cap, mid.ctypes.data,
+                                          C.byref(n_mid))
+        if n < 0:
+            _check(int(n))
+        return new[:n].copy(), mid[:n_mid.value].copy()
+
+    def adapted(self, refine, coarsen, degree=None, balance_vertices=False, number_type=None):
+        """(new_mesh, mid_mesh): this adaptive or from-leaves mesh adapted by Mesh.adapt_leaves (one flag of each kind per
+        cell, in cell order), at `degree` and `number_type` (default: this mesh's).  The h_hn creators and coarsening_map
+        apply to (mid_mesh, self) and (mid_mesh, new_mesh) when the degrees are equal (carry_over)."""
+        leaves = self.cell_levels()
+        if not len(leaves):
+            raise MfgpuError("Mesh.adapted: needs a leaf mesh (Mesh.adaptive, Mesh.adaptive_mg, Mesh.from_leaves)")
+        dim = int(self.desc.dim)
+        p = int(self.desc.degree) if degree is None else int(degree)
+        nt = int(self.desc.number_type) if number_type is None else number_type
+        new, mid = Mesh.adapt_leaves(dim, leaves, refine, coarsen, balance_vertices)
+        return Mesh.from_leaves(dim, p, new, number_type=nt), Mesh.from_leaves(dim, p, mid, number_type=nt)
 
     @classmethod
     def coarsening_sequence(cls, mesh, degree=None, min_cells=None):
@@ -1037,7 +1080,8 @@ class Transfer:
     """A multigrid transfer (mfgpu_transfer_*) of one of three kinds: between two globally refined levels at one degree
     (from_arrays / from_meshes, MGTransferMatrixFreeGpu), between two degrees on one mesh (p_from_arrays / p_hn_from_arrays
     / p_from_meshes / p_hn_from_meshes: p-multigrid, with or without hanging nodes), and between two leaf meshes with
-    hanging nodes at one degree (h_hn_from_arrays / h_hn_from_meshes: global coarsening); the calls are the same for all."""
+    hanging nodes at one degree (h_hn_from_arrays / h_hn_from_meshes: global coarsening); the calls are the same for all.
+    The last kind made by h_hn_interp_from_arrays / h_hn_interp_from_meshes also interpolates from fine to coarse."""
 
     def __init__(self, handle):
         self._h = handle
@@ -1137,6 +1181,38 @@ class Transfer:
         coarse one or their children (a mesh and a member of its Mesh.coarsening_sequence)"""
         return cls._create("mfgpu_transfer_create_h_hn_from_meshes", coarse._h, fine._h)
 
+    @classmethod
+    def h_hn_interp_from_arrays(cls, dim, degree, coarse_cell_dofs, fine_cell_dofs, parent, child, n_coarse_dofs,
+                                n_fine_dofs, coarse_dirichlet, number_type=F64, prolongation_1d=None, coarse_mask=None,
+                                fine_mask=None, constraint_weights=None, interpolation_1d=None):
+        """h_hn_from_arrays plus the interpolation image (mfgpu_transfer_create_h_hn_interp): the same object, and
+        interpolate works on it; interpolation_1d [(degree + 1)^2] replaces the default J1"""
+        (cd, cdp), (fd, fdp) = cls._arg(coarse_cell_dofs, np.uint32), cls._arg(fine_cell_dofs, np.uint32)
+        (pa, pap), (ch, chp) = cls._arg(parent, np.uint32), cls._arg(child, np.uint32)
+        (di, dip), (p1, p1p) = cls._arg(coarse_dirichlet, np.uint32), cls._arg(prolongation_1d, np.float64)
+        (cm, cmp_), (fm, fmp) = cls._arg(coarse_mask, np.uint32), cls._arg(fine_mask, np.uint32)
+        (w, wp), (j1, j1p) = cls._arg(constraint_weights, np.float64), cls._arg(interpolation_1d, np.float64)
+        nd = (max(int(degree), 0) + 1) ** dim
+        n_coarse, n_fine = cd.size // nd, fd.size // nd
+        if 1 <= degree <= 6 and dim in (2, 3):  # (anything else is the library's MFGPU_EINVAL)
+            assert cd.size == n_coarse * nd and fd.size == n_fine * nd and pa.size == n_fine and ch.size == n_fine
+            assert p1 is None or p1.size == (2 * degree + 1) * (degree + 1)
+            assert (cm is None or cm.size == n_coarse) and (fm is None or fm.size == n_fine)
+            assert w is None or w.size == (degree + 1) ** 2
+            assert j1 is None or j1.size == (degree + 1) ** 2
+        return cls._create("mfgpu_transfer_create_h_hn_interp", dim, degree, number_type, n_coarse, n_fine, cdp, fdp, pap,
+                           chp, n_coarse_dofs, n_fine_dofs, dip, di.size, p1p, cmp_, fmp, wp, j1p)
+
+    @classmethod
+    def h_hn_interp_from_meshes(cls, coarse: "Mesh", fine: "Mesh"):
+        """h_hn_from_meshes plus the interpolation image (mfgpu_transfer_create_h_hn_interp_from_meshes)"""
+        return cls._create("mfgpu_transfer_create_h_hn_interp_from_meshes", coarse._h, fine._h)
+
+    def interpolate(self, dst_coarse, src_fine, stream=None):
+        """dst_coarse = the nodal interpolant of src_fine on the coarse mesh (mfgpu_transfer_interpolate); coarse
+        Dirichlet dofs and dofs no coarse cell owns become 0.  Needs an object from an h_hn_interp creator"""
+        _check(lib().mfgpu_transfer_interpolate(self._h, _ptr(dst_coarse), _ptr(src_fine), stream))
+
     def prolongate(self, dst_fine, src_coarse, stream=None):
         _check(lib().mfgpu_transfer_prolongate(self._h, _ptr(dst_fine), _ptr(src_coarse), stream))
 
@@ -1196,6 +1272,45 @@ def mark_fixed_number(indicators, fraction):
     flags = np.zeros(len(eta), dtype=np.uint8)
     flags[np.argsort(-eta, kind="stable")[:k]] = 1
     return flags
+
+
+def mark_refine_coarsen(indicators, refine_fraction, coarsen_fraction):
+    """(refine, coarsen) flags [n] (uint8) each: the ceil(refine_fraction * n) largest and the floor(coarsen_fraction * n)
+    smallest indicators, ties to the lower cell index; a cell that is marked for refinement is never marked for
+    coarsening, so the two sets do not overlap (GridRefinement::refine_and_coarsen_fixed_number); host numpy"""
+    eta = np.asarray(indicators, dtype=np.float64).reshape(-1)
+    if not (0.0 <= refine_fraction <= 1.0 and 0.0 <= coarsen_fraction <= 1.0):
+        raise MfgpuError("mark_refine_coarsen: the fractions must lie in [0, 1]")
+    n = len(eta)
+    refine = mark_fixed_number(eta, refine_fraction)
+    coarsen = np.zeros(n, dtype=np.uint8)
+    order = np.argsort(eta, kind="stable")
+    order = order[refine[order] == 0]
+    coarsen[order[:min(len(order), int(np.floor(coarsen_fraction * n)))]] = 1
+    return refine, coarsen
+
+
+def carry_over(old: "Mesh", mid: "Mesh", new: "Mesh", x_old, homogeneous=True, stream=None):
+    """x_new, a DeviceVector on `new`: x_old (device, on `old`) interpolated to `mid` and prolongated to `new`, the three
+    meshes those of Mesh.adapted at one degree.  Exact where the mesh did not change or was refined, the nodal interpolant
+    where it was coarsened.  homogeneous: the dofs of `mid` on the boundary are carried as 0 (the homogeneous part of a
+    solution; the lift is set again on the new mesh); otherwise every value is carried"""
+    nt = int(new.desc.number_type)
+    if homogeneous:
+        down, up = Transfer.h_hn_interp_from_meshes(mid, old), Transfer.h_hn_from_meshes(mid, new)
+    else:
+        def make(creator, fine):
+            dim, p = int(mid.desc.dim), int(mid.desc.degree)
+            ma, fa = mid.arrays(), fine.arrays()
+            parent, child = coarsening_map(mid, fine)
+            return creator(dim, p, ma["loc2glob"], fa["loc2glob"], parent, child, mid.n_dofs, fine.n_dofs, [], nt,
+                           coarse_mask=ma["constraint_mask"], fine_mask=fa["constraint_mask"])
+        down, up = make(Transfer.h_hn_interp_from_arrays, old), make(Transfer.h_hn_from_arrays, new)
+    x_mid, x_new = DeviceVector(mid.n_dofs, nt), DeviceVector(new.n_dofs, nt)
+    down.interpolate(x_mid, x_old, stream)
+    up.prolongate(x_new, x_mid, stream)
+    synchronize()  # the two transfers and x_mid end here
+    return x_new
 
 
 def _ptr(v):

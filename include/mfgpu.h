@@ -911,6 +911,64 @@ int mfgpu_transfer_create_h_hn_from_meshes(const mfgpu_mesh *coarse, const mfgpu
  * level 18.                                                                                                          */
 int64_t mfgpu_mesh_refine_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, const uint8_t *flags,
                                  uint32_t balance_vertices, uint32_t *out, uint64_t out_capacity /* leaves */);
+/* ---- refinement and coarsening in one step (host only), what
+ * Triangulation::execute_coarsening_and_refinement does with both kinds of flags.
+ *  1. R is what mfgpu_mesh_refine_leaves(leaves, refine_flags, balance_vertices) yields: the same closure, the same
+ *     checks and refusals.
+ *  2. A family (a parent Q with its 2^dim children) is a candidate when all its children are input leaves, all of them
+ *     have coarsen_flags != 0, none has a refine flag, and all are still leaves of R (the closure split none).
+ *  3. Every candidate family in R is replaced by its parent.
+ *  4. Until nothing changes, a new parent is split again when a leaf two or more levels finer touches it, in the
+ *     relation of the closure (faces, 3D edges, with balance_vertices vertices): mfgpu_mesh_coarsen_leaves' rollback.  A
+ *     rollback only makes the set finer, so the fixed point does not depend on the order.
+ * The result is `new`; `mid` is the input with exactly the surviving families replaced by their parents, the common
+ * coarsening of old and new.  What holds:
+ *  - refinement wins over coarsening;
+ *  - new and mid are one-irregular in the relation of the call;
+ *  - every old leaf is a leaf of mid or the child of one, and so is every new leaf: mfgpu_mesh_coarsening_map and the
+ *    h_hn creators apply to both pairs (mid, old) and (mid, new);
+ *  - no flags: new == mid == old; refine flags only: new == mfgpu_mesh_refine_leaves(...), mid == old; all coarsen flags,
+ *    no refine flags, no balance_vertices: new == mid == mfgpu_mesh_coarsen_leaves(old) as sets.
+ * Order: the input's; the children of a split leaf in its place in child order; a surviving parent where its child 0
+ * stood, its other children dropped.  Returns the number of leaves written to out_new [new_capacity * 4] and sets *n_mid
+ * to the number written to out_mid [n_leaves * 4].  MFGPU_EINVAL, nothing written: what mfgpu_mesh_refine_leaves
+ * refuses, and a new_capacity that is too small (the message names the needed count).                                */
+int64_t mfgpu_mesh_adapt_leaves(int dim, const uint32_t *leaves, uint32_t n_leaves, const uint8_t *refine_flags,
+                                const uint8_t *coarsen_flags, uint32_t balance_vertices, uint32_t *out_new,
+                                uint64_t new_capacity /* leaves */, uint32_t *out_mid /* [n_leaves * 4] */,
+                                uint32_t *n_mid);
+/* ---- interpolation on the h_hn transfer: the fine function's nodal interpolant on the coarser
+ * mesh, what MGTwoLevelTransfer::interpolate and SolutionTransfer give.  The two creators take the arguments of
+ * mfgpu_transfer_create_h_hn (mfgpu_transfer_create_h_hn_from_meshes) and make the same object -- prolongate,
+ * prolongate_add and restrict_and_add agree bit for bit with it -- plus an interpolation image: per coarse cell the
+ * indices of its fine cells, the fine masks per fine cell, a coarse list with owner marking, and interpolation_1d.
+ * mfgpu_transfer_interpolate returns MFGPU_EINVAL for any object made without the image; objects from the other creators
+ * do not grow.
+ *   The owner of a coarse dof is the first coarse cell that lists it at a position its COARSE mask does not constrain
+ * (mfgpu_transfer_p_owner_list with the coarse lists and mask).  For the owner K and the local position
+ * i = (i_0, ..., i_{dim-1}), xi the Gauss-Lobatto nodes of FE_Q(p) on [0, 1]:
+ *  - K is also a fine cell F (child = 0):  v_i = [ C_p(fine_mask_F) gather_F(src) ]_i.  The gather reads every entry of
+ *    F's list as it stands in src.
+ *  - otherwise b_d = 0 if xi_{i_d} <= 1/2, else 1; k = sum_d b_d 2^d, F_k that child of K;
+ *      v_i = sum_j prod_d J1[i_d][j_d] [ C_p(fine_mask_{F_k}) gather_{F_k}(src) ]_j,   J1[i][j] = phi_j(2 xi_i - b(i)),
+ *    phi the Lagrange basis of FE_Q(p) on its Gauss-Lobatto nodes.  interpolation_1d [(p+1)^2] row-major replaces J1;
+ *    NULL: this default.  At p = 1, 2 every row of J1 is a unit vector: the call is an injection, bit for bit.
+ *  - dst[coarse(K, i)] = v_i for owned entries that are not coarse Dirichlet dofs; coarse Dirichlet dofs and dofs that
+ *    no coarse cell owns become 0.
+ * Stores are plain, no atomics: the same input gives the same bits on two calls and in a replayed graph.  The call only
+ * enqueues, reads nothing back and allocates nothing; double and float.  interpolate(prolongate(x)) = x on owned
+ * non-Dirichlet dofs up to rounding; an unchanged cell without a fine mask passes its values through bit for bit.
+ * The creators refuse (MFGPU_EINVAL) what mfgpu_transfer_create_h_hn refuses, and a pair in which a coarse cell is not
+ * exactly one fine cell with child = 0 or all 2^dim children, each once.                                              */
+int mfgpu_transfer_create_h_hn_interp(int dim, int degree, int number_type, uint32_t n_coarse_cells, uint32_t n_fine_cells,
+                                      const uint32_t *coarse_cell_dofs, const uint32_t *fine_cell_dofs,
+                                      const uint32_t *parent, const uint32_t *child, uint32_t n_coarse_dofs,
+                                      uint32_t n_fine_dofs, const uint32_t *coarse_dirichlet, uint32_t n_coarse_dirichlet,
+                                      const double *prolongation_1d, const uint32_t *coarse_mask, const uint32_t *fine_mask,
+                                      const double *constraint_weights,
+                                      const double *interpolation_1d /* [(p+1)^2] or NULL */, mfgpu_transfer **out);
+int mfgpu_transfer_create_h_hn_interp_from_meshes(const mfgpu_mesh *coarse, const mfgpu_mesh *fine, mfgpu_transfer **out);
+int mfgpu_transfer_interpolate(mfgpu_transfer *t, void *dst_coarse_dev, const void *src_fine_dev, void *stream);
 void mfgpu_mesh_destroy(mfgpu_mesh *m);
 /* fills *desc with pointers into the mesh (valid until mfgpu_mesh_destroy) */
 int mfgpu_mesh_desc(const mfgpu_mesh *m, mfgpu_desc *desc);
