@@ -135,6 +135,9 @@ SYMBOLS = [
     "mfgpu_integrator_recovery_indicator", "mfgpu_mesh_refine_leaves",
     "mfgpu_mesh_adapt_leaves", "mfgpu_transfer_create_h_hn_interp", "mfgpu_transfer_create_h_hn_interp_from_meshes",
     "mfgpu_transfer_interpolate",
+    "mfgpu_locate_points", "mfgpu_points_create", "mfgpu_points_create_in_cells", "mfgpu_points_cells",
+    "mfgpu_points_n_not_found", "mfgpu_points_evaluate", "mfgpu_points_integrate", "mfgpu_points_memory_consumption",
+    "mfgpu_points_destroy",
 ]
 
 _lib = None
@@ -323,6 +326,19 @@ def lib():
                                                         vp, C.POINTER(vp)]
         L.mfgpu_transfer_create_h_hn_interp_from_meshes.argtypes = [vp, vp, C.POINTER(vp)]
         L.mfgpu_transfer_interpolate.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_locate_points.argtypes = [C.POINTER(Desc), vp, u32, vp, vp, C.POINTER(u32)]
+        L.mfgpu_points_create.argtypes = [vp, C.POINTER(Desc), vp, u32, C.POINTER(vp)]
+        L.mfgpu_points_create_in_cells.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
+        L.mfgpu_points_cells.argtypes = [vp, C.POINTER(vp)]
+        L.mfgpu_points_cells.restype = C.c_int64
+        L.mfgpu_points_n_not_found.argtypes = [vp]
+        L.mfgpu_points_n_not_found.restype = u32
+        L.mfgpu_points_evaluate.argtypes = [vp, vp, vp, vp, vp]
+        L.mfgpu_points_integrate.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_points_memory_consumption.argtypes = [vp]
+        L.mfgpu_points_memory_consumption.restype = C.c_size_t
+        L.mfgpu_points_destroy.argtypes = [vp]
+        L.mfgpu_points_destroy.restype = None
         _lib = L
     return _lib
 
@@ -1002,6 +1018,77 @@ class Integrator:
         v = DeviceVector(self.n_cells * self.n_error_points * self.dim)
         _check(lib().mfgpu_integrator_error_points(self._h, v.ptr, None))
         return v.to_host().reshape(self.n_cells, self.n_error_points, self.dim)
+
+
+POINT_NOT_FOUND = 0xffffffff  # MFGPU_POINT_NOT_FOUND
+
+
+def locate_points(desc: Desc, x):
+    """mfgpu_locate_points (host): (cell [n] uint32, xi [n, dim], n_not_found) of the points x [n, dim]; a point no cell
+    holds has cell POINT_NOT_FOUND and xi 0"""
+    dim = int(desc.dim)
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, dim)
+    cell, xi, missing = np.empty(len(x), np.uint32), np.empty((len(x), dim), np.float64), C.c_uint32()
+    _check(lib().mfgpu_locate_points(C.byref(desc), x.ctypes.data, len(x), cell.ctypes.data, xi.ctypes.data,
+                                     C.byref(missing)))
+    return cell, xi, int(missing.value)
+
+
+class Points:
+    """A set of points in the cells of an integrator's mesh (mfgpu_points_*): the field and its gradient at them
+    (evaluate) and the transpose of the value part, point sources (integrate).  Double only.  The integrator is kept
+    alive by the object."""
+
+    def __init__(self, integrator: "Integrator", desc: Desc = None, x=None, _in_cells=None):
+        self._it = integrator
+        self.dim = integrator.dim
+        h = C.c_void_p()
+        if _in_cells is None:
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.dim)
+            self.n = len(x)
+            _check(lib().mfgpu_points_create(integrator._h, C.byref(desc), x.ctypes.data, self.n, C.byref(h)))
+        else:
+            cell, xi = _in_cells
+            self.n = len(cell)
+            _check(lib().mfgpu_points_create_in_cells(integrator._h, cell.ctypes.data, xi.ctypes.data, self.n, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def in_cells(cls, integrator: "Integrator", cell, xi):
+        """points given as (cell [n], xi [n, dim] in [0, 1]); POINT_NOT_FOUND is allowed as a cell"""
+        cell = np.ascontiguousarray(cell, dtype=np.uint32).reshape(-1)
+        xi = np.ascontiguousarray(xi, dtype=np.float64).reshape(-1, integrator.dim)
+        if len(xi) != len(cell):
+            raise ValueError("cell and xi disagree on the number of points")
+        return cls(integrator, _in_cells=(cell, xi))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_points_destroy(self._h)
+            self._h = None
+
+    @property
+    def cells(self):
+        """the cell of every point, in the caller's order (a copy)"""
+        p = C.c_void_p()
+        n = lib().mfgpu_points_cells(self._h, C.byref(p))
+        return _view(p.value, n, np.uint32).copy()
+
+    @property
+    def n_not_found(self):
+        return int(lib().mfgpu_points_n_not_found(self._h))
+
+    def evaluate(self, u, values=None, gradients=None, stream=None):
+        """u_h at the points into `values` [n] and / or its real-space gradient into `gradients` [n * dim] (device
+        arrays, caller's point order); points without a cell get 0"""
+        _check(lib().mfgpu_points_evaluate(self._h, _ptr(u), _optr(values), _optr(gradients), stream))
+
+    def integrate(self, rhs, weights=None, stream=None):
+        """rhs [n_dofs] = sum_k weights_k phi_i(x_k) (weights None: all 1), distributed like a cell result"""
+        _check(lib().mfgpu_points_integrate(self._h, _ptr(rhs), _optr(weights), stream))
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_points_memory_consumption(self._h))
 
 
 class MgHierarchy:

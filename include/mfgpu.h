@@ -818,6 +818,61 @@ int mfgpu_integrator_recovery_indicator(mfgpu_integrator *it, const void *u, con
                                         void *stream);
 void mfgpu_integrator_destroy(mfgpu_integrator *it);
 
+/* ---- fields and point sources at arbitrary points (no reference counterpart; deal.II: VectorTools::point_value /
+ * point_gradient, FEPointEvaluation::evaluate / integrate, create_point_source_vector) --------
+ * MFGPU_F64 only (MFGPU_F32 description or integrator: MFGPU_EUNSUPPORTED), dim 2 and 3, degree 1..6, uniform-J0 and
+ * general geometry, with and without hanging nodes.  One definition throughout, with N = p+1, x_q the description's
+ * quadrature_points of a cell (QGauss(N), x fastest) and L_q the tensor Lagrange basis on the 1D Gauss abscissae:
+ *   mapping   x(xi) = sum_q L_q(xi) x_q -- exact for affine cells and MappingQ1 (every mesh stand-in below), not for
+ *             mappings of a higher degree (the restriction of the integrator's error points);
+ *   field     U_q = the cell's nodal values at the Gauss points, by the steps of mfgpu_integrator_evaluate (gather
+ *             through loc2glob, hanging-node resolution, S x S (x S)); u_h(xi) = sum_q L_q(xi) U_q, the same polynomial;
+ *   gradient  grad_x u_h = J(xi)^-T grad_xi u_h with J(xi) = sum_q grad L_q(xi) x_q (inv_jac is not needed on the
+ *             device, so every integrator serves; with MFGPU_UNIFORM_J0 J is one scalar per cell).
+ *
+ * mfgpu_locate_points (host only): for each of the n points x [n * dim] the cell that holds it and its reference
+ * coordinates xi [n * dim] in [0, 1]^dim.  It reads dim, degree, n_cells, quadrature_points and number_type of the
+ * description.  Conditions of the interface (stated, not measured):
+ *   - a cell is a candidate when the point lies in the bounding box of the cell's 2^dim corners (the mapping at xi in
+ *     {0, 1}^dim) inflated by 1e-10 of the box's diagonal; candidates are found through a uniform bin grid;
+ *   - per candidate, Newton on x(xi) = x from the cell's centre, at most 30 steps, converged when |delta xi|_inf <= 1e-14;
+ *     an iteration that diverges or does not converge means "not in this cell";
+ *   - a converged candidate is accepted when every xi_d lies in [-1e-10, 1 + 1e-10]; xi is then clamped to [0, 1];
+ *   - among the accepting cells the one with the lowest index wins, whatever the bin grid;
+ *   - a point no cell accepts gets cell = MFGPU_POINT_NOT_FOUND and xi = 0 and is counted in *n_not_found (may be NULL):
+ *     not an error.                                                                                                 */
+#define MFGPU_POINT_NOT_FOUND 0xffffffffu
+int mfgpu_locate_points(const mfgpu_desc *desc, const double *x, uint32_t n, uint32_t *cell, double *xi,
+                        uint32_t *n_not_found);
+/* The points object: n points, each in a cell of the integrator's description (or in none), ready for the two calls
+ * below.  It BORROWS the integrator's device geometry (loc2glob, constraint mask, tables, quadrature points): the
+ * integrator must outlive it.  mfgpu_points_create = mfgpu_locate_points on `desc` (the description the integrator was
+ * created from), then mfgpu_points_create_in_cells, which takes (cell [n], xi [n * dim]) as given: MFGPU_POINT_NOT_FOUND is
+ * allowed as a cell; any other cell >= n_cells, or a xi outside [0, 1], is MFGPU_EINVAL.  n = 0 is allowed.  The points
+ * are sorted by cell and each cell's points are cut into work items of at most 512; everything either call needs is
+ * allocated here (the local vectors of integrate and its dof -> slot CSR included), so both calls only enqueue and can
+ * be captured in a graph.                                                                                           */
+typedef struct mfgpu_points mfgpu_points;
+int mfgpu_points_create(mfgpu_integrator *it, const mfgpu_desc *desc, const double *x, uint32_t n, mfgpu_points **out);
+int mfgpu_points_create_in_cells(mfgpu_integrator *it, const uint32_t *cell, const double *xi, uint32_t n,
+                                 mfgpu_points **out);
+/* the cell of every point in the caller's order (host array owned by the object); returns n */
+int64_t mfgpu_points_cells(const mfgpu_points *p, const uint32_t **cell);
+uint32_t mfgpu_points_n_not_found(const mfgpu_points *p);
+/* values [n] = u_h(x_k), gradients [n * dim] = grad_x u_h(x_k) (x, y, z per point), in the caller's point order; device
+ * doubles.  Either output may be NULL (both: MFGPU_EINVAL).  u [n_dofs] is read on every dof a cell lists, constrained
+ * dofs included, hanging dofs never, as mfgpu_integrator_evaluate does.  Points without a cell get 0.  Every output
+ * entry is written by exactly one thread; two calls give bitwise-equal results.  One wave per work item.  Asynchronous. */
+int mfgpu_points_evaluate(mfgpu_points *p, const void *u, void *values, void *gradients, void *stream);
+/* rhs_i = sum_k w_k phi_i(x_k), the transpose of the value part of mfgpu_points_evaluate, distributed like a cell
+ * result: hanging-node resolution transposed, constrained rows 0, every entry of rhs [n_dofs] written.  weights [n] in
+ * the caller's point order, NULL = all 1; points without a cell contribute nothing.  No floating-point atomics: the
+ * work items' local vectors are summed per dof in ascending (work item, local index) order, so two calls give
+ * bitwise-equal results.  Asynchronous; two calls on one object may not overlap (they share the local vectors).      */
+int mfgpu_points_integrate(mfgpu_points *p, void *rhs, const void *weights, void *stream);
+size_t mfgpu_points_memory_consumption(const mfgpu_points *p); /* device bytes the object owns */
+void mfgpu_points_destroy(mfgpu_points *p);
+
 /* ---- deal.II stand-in for the setup side (host only) --------------------------------------
  * Produces what Triangulation + DoFHandler + ConstraintMatrix + FEValues + ShapeInfo hand to
  * MatrixFreeGpu::reinit, for the meshes bmop uses (bmop_common.h:108-120).                    */
