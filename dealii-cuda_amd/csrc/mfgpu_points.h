@@ -21,6 +21,34 @@ std::vector<double> point_table(int n);
 // l[j] = L_j(t), dl[j] = L_j'(t) from a point_table (the formula of the kernels)
 void point_basis(int n, const double *table, double t, double *l, double *dl);
 
+// The constants of point location (include/mfgpu.h, "mfgpu_locate_points"), read by the host search and by
+// locate_kernel (mfgpu_locate.hip) alike.
+constexpr int kNewtonSteps = 30;
+constexpr double kNewtonTol = 1e-14, kAcceptTol = 1e-10, kBoxInflation = 1e-10;
+constexpr double kHintMargin = 1e-8;  // a hinted cell is taken only when every xi_d lies in [kHintMargin, 1 - kHintMargin]
+
+// The candidate grid of point location, one for host and device: the boxes of the cells' 2^dim corners inflated by
+// kBoxInflation of their diagonal, the box of all of them, and a uniform grid of nb bins per direction over it with the
+// cells whose box meets a bin, in ascending order (CSR).
+struct LocatorGrid {
+  std::vector<double> lo, hi;  // [n_cells * dim]
+  double glo[3] = {0, 0, 0}, ghi[3] = {0, 0, 0};
+  uint32_t nb = 1;
+  double inv_w[3] = {0, 0, 0};  // bins per unit length; 0 in a direction without extent
+  std::vector<uint32_t> boff, bidx;  // [nb^dim + 1]; [boff.back()]
+  // the bin of coordinate v in direction e, clamped to the grid (the formula of the kernel)
+  uint32_t bin_of(double v, int e) const {
+    const double t = (v - glo[e]) * inv_w[e];
+    return t <= 0 ? 0u : t >= nb ? nb - 1 : (uint32_t)t;
+  }
+};
+// xq: the description's quadrature_points [n_cells * n^dim * dim], n = degree + 1
+void build_locator_grid(int dim, int n, size_t n_cells, const double *xq, LocatorGrid &grid);
+// Newton on x(xi) = x in one cell (xq: its n^dim Gauss points) from the cell's centre; true when it converged to an
+// accepted xi (then clamped to [0, 1]).  y: [n^dim * dim] scratch.
+bool newton_in_cell(int dim, int n, const double *table, const double *xq, size_t nd, const double *x, double *y,
+                    double *xi);
+
 // Host half of mfgpu_points_create_in_cells: the points sorted by cell (stable, the points without a cell last), cut
 // into work items, and the dof -> slot CSR of integrate (slot = item * N^dim + local index, ascending; constrained dofs
 // and dofs no item touches stay empty).

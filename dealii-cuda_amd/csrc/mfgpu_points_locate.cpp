@@ -87,8 +87,7 @@ bool newton_step(int dim, const double *J, const double *F, double *delta) {
   return true;
 }
 
-constexpr int kNewtonSteps = 30;
-constexpr double kNewtonTol = 1e-14, kAcceptTol = 1e-10, kBoxInflation = 1e-10;
+}  // namespace
 
 // Newton on x(xi) = x in one cell from its centre; true when it converged to an accepted xi (then clamped to [0, 1])
 bool newton_in_cell(int dim, int n, const double *table, const double *xq, size_t nd, const double *x, double *y,
@@ -115,7 +114,66 @@ bool newton_in_cell(int dim, int n, const double *table, const double *xq, size_
   return true;
 }
 
-}  // namespace
+void build_locator_grid(int dim, int N, size_t nc, const double *xq, LocatorGrid &g) {
+  g = LocatorGrid();
+  const size_t nd = (size_t)ipow(N, dim);
+  const std::vector<double> table = point_table(N);
+  // boxes of the cells' corners (the mapping at xi in {0, 1}^dim), inflated
+  std::vector<double> &lo = g.lo, &hi = g.hi;
+  lo.resize(nc * dim);
+  hi.resize(nc * dim);
+  double *glo = g.glo, *ghi = g.ghi;
+  for (size_t c = 0; c < nc; ++c) {
+    double *l = &lo[c * dim], *h = &hi[c * dim];
+    for (int v = 0; v < (1 << dim); ++v) {
+      double corner[3], F[3], J[9];
+      for (int e = 0; e < dim; ++e) corner[e] = (v >> e) & 1;
+      map_eval(dim, N, table.data(), xq + c * nd * dim, corner, F, J);
+      for (int e = 0; e < dim; ++e) {
+        l[e] = v == 0 ? F[e] : std::min(l[e], F[e]);
+        h[e] = v == 0 ? F[e] : std::max(h[e], F[e]);
+      }
+    }
+    double diag = 0;
+    for (int e = 0; e < dim; ++e) diag += (h[e] - l[e]) * (h[e] - l[e]);
+    diag = std::sqrt(diag);
+    for (int e = 0; e < dim; ++e) {
+      l[e] -= kBoxInflation * diag;
+      h[e] += kBoxInflation * diag;
+      glo[e] = c == 0 ? l[e] : std::min(glo[e], l[e]);
+      ghi[e] = c == 0 ? h[e] : std::max(ghi[e], h[e]);
+    }
+  }
+  // uniform bin grid over the boxes: bin -> cells whose box meets it, ascending
+  uint32_t nb = (uint32_t)std::floor(std::pow((double)nc, 1.0 / dim) + 1e-9);
+  nb = std::max(1u, std::min(nb, 256u));
+  g.nb = nb;
+  for (int e = 0; e < dim; ++e) g.inv_w[e] = ghi[e] > glo[e] ? nb / (ghi[e] - glo[e]) : 0.0;
+  const size_t n_bins = (size_t)ipow((int)nb, dim);
+  std::vector<uint32_t> &boff = g.boff, &bidx = g.bidx;
+  boff.assign(n_bins + 1, 0);
+  for (int pass = 0; pass < 2; ++pass) {
+    std::vector<uint32_t> pos(boff.begin(), boff.end() - 1);
+    for (size_t c = 0; c < nc; ++c) {
+      uint32_t b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
+      for (int e = 0; e < dim; ++e) {
+        b0[e] = g.bin_of(lo[c * dim + e], e);
+        b1[e] = g.bin_of(hi[c * dim + e], e);
+      }
+      for (uint32_t bz = b0[2]; bz <= b1[2]; ++bz)
+        for (uint32_t by = b0[1]; by <= b1[1]; ++by)
+          for (uint32_t bx = b0[0]; bx <= b1[0]; ++bx) {
+            const size_t b = bx + (size_t)nb * (by + (size_t)nb * bz);
+            if (pass == 0) ++boff[b + 1];
+            else bidx[pos[b]++] = (uint32_t)c;
+          }
+    }
+    if (pass == 0) {
+      for (size_t b = 0; b < n_bins; ++b) boff[b + 1] += boff[b];
+      bidx.resize(boff[n_bins]);
+    }
+  }
+}
 
 std::vector<double> point_table(int n) {
   std::vector<double> t((size_t)n + (size_t)n * n, 0.0);
@@ -231,62 +289,10 @@ int mfgpu_locate_points(const mfgpu_desc *desc, const double *x, uint32_t n, uin
   const size_t nd = (size_t)ipow(N, dim), nc = d.n_cells;
   const double *xq = (const double *)d.quadrature_points;
   const std::vector<double> table = point_table(N);
-  // boxes of the cells' corners (the mapping at xi in {0, 1}^dim), inflated
-  std::vector<double> lo(nc * dim), hi(nc * dim);
-  double glo[3] = {0, 0, 0}, ghi[3] = {0, 0, 0};
-  for (size_t c = 0; c < nc; ++c) {
-    double *l = &lo[c * dim], *h = &hi[c * dim];
-    for (int v = 0; v < (1 << dim); ++v) {
-      double corner[3], F[3], J[9];
-      for (int e = 0; e < dim; ++e) corner[e] = (v >> e) & 1;
-      map_eval(dim, N, table.data(), xq + c * nd * dim, corner, F, J);
-      for (int e = 0; e < dim; ++e) {
-        l[e] = v == 0 ? F[e] : std::min(l[e], F[e]);
-        h[e] = v == 0 ? F[e] : std::max(h[e], F[e]);
-      }
-    }
-    double diag = 0;
-    for (int e = 0; e < dim; ++e) diag += (h[e] - l[e]) * (h[e] - l[e]);
-    diag = std::sqrt(diag);
-    for (int e = 0; e < dim; ++e) {
-      l[e] -= kBoxInflation * diag;
-      h[e] += kBoxInflation * diag;
-      glo[e] = c == 0 ? l[e] : std::min(glo[e], l[e]);
-      ghi[e] = c == 0 ? h[e] : std::max(ghi[e], h[e]);
-    }
-  }
-  // uniform bin grid over the boxes: bin -> cells whose box meets it, ascending
-  uint32_t nb = (uint32_t)std::floor(std::pow((double)nc, 1.0 / dim) + 1e-9);
-  nb = std::max(1u, std::min(nb, 256u));
-  double inv_w[3];
-  for (int e = 0; e < dim; ++e) inv_w[e] = ghi[e] > glo[e] ? nb / (ghi[e] - glo[e]) : 0.0;
-  auto bin_of = [&](double v, int e) {
-    const double t = (v - glo[e]) * inv_w[e];
-    return t <= 0 ? 0u : t >= nb ? nb - 1 : (uint32_t)t;
-  };
-  const size_t n_bins = (size_t)ipow((int)nb, dim);
-  std::vector<uint32_t> boff(n_bins + 1, 0), bidx;
-  for (int pass = 0; pass < 2; ++pass) {
-    std::vector<uint32_t> pos(boff.begin(), boff.end() - 1);
-    for (size_t c = 0; c < nc; ++c) {
-      uint32_t b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
-      for (int e = 0; e < dim; ++e) {
-        b0[e] = bin_of(lo[c * dim + e], e);
-        b1[e] = bin_of(hi[c * dim + e], e);
-      }
-      for (uint32_t bz = b0[2]; bz <= b1[2]; ++bz)
-        for (uint32_t by = b0[1]; by <= b1[1]; ++by)
-          for (uint32_t bx = b0[0]; bx <= b1[0]; ++bx) {
-            const size_t b = bx + (size_t)nb * (by + (size_t)nb * bz);
-            if (pass == 0) ++boff[b + 1];
-            else bidx[pos[b]++] = (uint32_t)c;
-          }
-    }
-    if (pass == 0) {
-      for (size_t b = 0; b < n_bins; ++b) boff[b + 1] += boff[b];
-      bidx.resize(boff[n_bins]);
-    }
-  }
+  LocatorGrid g;
+  build_locator_grid(dim, N, nc, xq, g);
+  const std::vector<double> &lo = g.lo, &hi = g.hi;
+  const std::vector<uint32_t> &boff = g.boff, &bidx = g.bidx;
   std::vector<double> y(nd * dim);
   uint32_t missing = 0;
   for (uint32_t k = 0; k < n; ++k) {
@@ -294,10 +300,10 @@ int mfgpu_locate_points(const mfgpu_desc *desc, const double *x, uint32_t n, uin
     cell[k] = MFGPU_POINT_NOT_FOUND;
     for (int e = 0; e < dim; ++e) xi[(size_t)k * dim + e] = 0.0;
     bool inside = true;
-    for (int e = 0; e < dim; ++e) inside = inside && xk[e] >= glo[e] && xk[e] <= ghi[e];  // false for NaN
+    for (int e = 0; e < dim; ++e) inside = inside && xk[e] >= g.glo[e] && xk[e] <= g.ghi[e];  // false for NaN
     if (inside) {
       size_t b = 0;
-      for (int e = dim - 1; e >= 0; --e) b = b * nb + bin_of(xk[e], e);
+      for (int e = dim - 1; e >= 0; --e) b = b * g.nb + g.bin_of(xk[e], e);
       for (uint32_t j = boff[b]; j < boff[b + 1]; ++j) {  // ascending: the lowest accepting cell wins
         const size_t c = bidx[j];
         bool in_box = true;

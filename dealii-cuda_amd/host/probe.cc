@@ -89,9 +89,41 @@ void run(int n_ref, unsigned int n_points) {
     v = -extent + 2 * extent * (state / 4294967296.0);
   }
   mfgpu_points *points = nullptr;
+#ifdef PROBE_DEVICE_LOCATE
+  // the points uploaded, located by the locator's kernel, and the object built from the device arrays
+  mfgpu_locator *locator = nullptr;
+  check(mfgpu_locator_create(integrator.it, &dof_handler.desc, &locator), "mfgpu_locator_create");
+  VectorType x_dev(x.empty() ? std::vector<double>(1, 0.0) : x), xi_dev((size_t)n_points * dim + 1);
+  GpuVector<float> cell_dev(n_points + 1);  // 4-byte device memory: holds the uint32 cells
+  const auto t1 = std::chrono::steady_clock::now();
+  check(mfgpu_locator_locate(locator, x_dev.getDataRO(), n_points, nullptr, (uint32_t *)cell_dev.getData(),
+                             xi_dev.getData(), nullptr, nullptr), "mfgpu_locator_locate");
+  check(mfgpu_points_create_located(integrator.it, (const uint32_t *)cell_dev.getDataRO(), xi_dev.getDataRO(), n_points,
+                                    nullptr, &points), "mfgpu_points_create_located");
+  const double t_create = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+  {  // against the host location of the same points
+    std::vector<uint32_t> cell_host(n_points);
+    std::vector<double> xi_host((size_t)n_points * dim);
+    check(mfgpu_locate_points(&dof_handler.desc, x.data(), n_points, cell_host.data(), xi_host.data(), nullptr),
+          "mfgpu_locate_points");
+    const std::vector<number> xi_got = xi_dev.toVector();
+    const uint32_t *cell_got = nullptr;
+    mfgpu_points_cells(points, &cell_got);
+    unsigned int differing = 0;
+    double worst_xi = 0;
+    for (unsigned int k = 0; k < n_points; ++k) {
+      differing += cell_got[k] != cell_host[k];
+      for (int d = 0; d < dim; ++d)
+        worst_xi = std::max(worst_xi, std::fabs(xi_got[(size_t)k * dim + d] - xi_host[(size_t)k * dim + d]));
+    }
+    std::printf("device location: %u cells differ from the host's, max |xi_dev - xi_host| %.3e\n", differing, worst_xi);
+  }
+  mfgpu_locator_destroy(locator);
+#else
   const auto t1 = std::chrono::steady_clock::now();
   check(mfgpu_points_create(integrator.it, &dof_handler.desc, x.data(), n_points, &points), "mfgpu_points_create");
   const double t_create = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+#endif
   VectorType values(n_points ? n_points : 1);
   check(mfgpu_points_evaluate(points, solution.getDataRO(), values.getData(), nullptr, nullptr), "mfgpu_points_evaluate");
   mfgpu_device_synchronize();

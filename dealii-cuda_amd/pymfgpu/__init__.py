@@ -138,6 +138,8 @@ SYMBOLS = [
     "mfgpu_locate_points", "mfgpu_points_create", "mfgpu_points_create_in_cells", "mfgpu_points_cells",
     "mfgpu_points_n_not_found", "mfgpu_points_evaluate", "mfgpu_points_integrate", "mfgpu_points_memory_consumption",
     "mfgpu_points_destroy",
+    "mfgpu_locator_create", "mfgpu_locator_locate", "mfgpu_locator_memory_consumption", "mfgpu_locator_destroy",
+    "mfgpu_points_create_located",
 ]
 
 _lib = None
@@ -339,6 +341,13 @@ def lib():
         L.mfgpu_points_memory_consumption.restype = C.c_size_t
         L.mfgpu_points_destroy.argtypes = [vp]
         L.mfgpu_points_destroy.restype = None
+        L.mfgpu_locator_create.argtypes = [vp, C.POINTER(Desc), C.POINTER(vp)]
+        L.mfgpu_locator_locate.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
+        L.mfgpu_locator_memory_consumption.argtypes = [vp]
+        L.mfgpu_locator_memory_consumption.restype = C.c_size_t
+        L.mfgpu_locator_destroy.argtypes = [vp]
+        L.mfgpu_locator_destroy.restype = None
+        L.mfgpu_points_create_located.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp)]
         _lib = L
     return _lib
 
@@ -1039,11 +1048,14 @@ class Points:
     (evaluate) and the transpose of the value part, point sources (integrate).  Double only.  The integrator is kept
     alive by the object."""
 
-    def __init__(self, integrator: "Integrator", desc: Desc = None, x=None, _in_cells=None):
+    def __init__(self, integrator: "Integrator", desc: Desc = None, x=None, _in_cells=None, _located=None):
         self._it = integrator
         self.dim = integrator.dim
         h = C.c_void_p()
-        if _in_cells is None:
+        if _located is not None:
+            cell, xi, self.n, stream = _located
+            _check(lib().mfgpu_points_create_located(integrator._h, _optr(cell), _optr(xi), self.n, stream, C.byref(h)))
+        elif _in_cells is None:
             x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.dim)
             self.n = len(x)
             _check(lib().mfgpu_points_create(integrator._h, C.byref(desc), x.ctypes.data, self.n, C.byref(h)))
@@ -1061,6 +1073,12 @@ class Points:
         if len(xi) != len(cell):
             raise ValueError("cell and xi disagree on the number of points")
         return cls(integrator, _in_cells=(cell, xi))
+
+    @classmethod
+    def located(cls, integrator: "Integrator", cell, xi, n, stream=None):
+        """points given as device buffers (cell [n] uint32, xi [n * dim]) as Locator.locate leaves them
+        (mfgpu_points_create_located): synchronises `stream`, downloads both and builds the object of in_cells"""
+        return cls(integrator, _located=(cell, xi, int(n), stream))
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -1089,6 +1107,44 @@ class Points:
 
     def memory_consumption(self):
         return int(lib().mfgpu_points_memory_consumption(self._h))
+
+
+class Locator:
+    """Point location on the device (mfgpu_locator_*): mfgpu_locate_points for points that move.  Created from an
+    integrator and the description it was created from; the integrator is kept alive by the object.  Double only.
+
+    The `cell`, `hint` and `n_not_found` buffers are 4-byte device memory holding uint32: allocate them as
+    DeviceVector(n, F32) and read them back with `.to_host().view(np.uint32)` (cells_to_host does that); a torch int32
+    tensor on the GPU is accepted as well."""
+
+    def __init__(self, integrator: "Integrator", desc: Desc):
+        self._it = integrator
+        self.dim = integrator.dim
+        h = C.c_void_p()
+        _check(lib().mfgpu_locator_create(integrator._h, C.byref(desc), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_locator_destroy(self._h)
+            self._h = None
+
+    def locate(self, x, cell, xi, hint=None, n_not_found=None, stream=None, n=None):
+        """the cell [n] (POINT_NOT_FOUND: none) and xi [n * dim] of the points x [n * dim], all device buffers; hint [n]
+        (may be `cell` itself) names a cell to try first; n_not_found: one uint32, overwritten.  n defaults to the
+        length of `cell`.  Asynchronous."""
+        if n is None:
+            n = cell.n if isinstance(cell, DeviceVector) else cell.numel()
+        _check(lib().mfgpu_locator_locate(self._h, _optr(x), int(n), _optr(hint), _optr(cell), _optr(xi),
+                                          _optr(n_not_found), stream))
+
+    @staticmethod
+    def cells_to_host(cell):
+        """a DeviceVector(n, F32) that holds cells, on the host as uint32"""
+        return cell.to_host().view(np.uint32)
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_locator_memory_consumption(self._h))
 
 
 class MgHierarchy:

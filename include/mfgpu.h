@@ -832,7 +832,8 @@ void mfgpu_integrator_destroy(mfgpu_integrator *it);
  *
  * mfgpu_locate_points (host only): for each of the n points x [n * dim] the cell that holds it and its reference
  * coordinates xi [n * dim] in [0, 1]^dim.  It reads dim, degree, n_cells, quadrature_points and number_type of the
- * description.  Conditions of the interface (stated, not measured):
+ * description.  Conditions of the interface (stated, not measured), shared word for word by mfgpu_locator_locate below
+ * (the same candidate grid, the same constants: csrc/mfgpu_points.h):
  *   - a cell is a candidate when the point lies in the bounding box of the cell's 2^dim corners (the mapping at xi in
  *     {0, 1}^dim) inflated by 1e-10 of the box's diagonal; candidates are found through a uniform bin grid;
  *   - per candidate, Newton on x(xi) = x from the cell's centre, at most 30 steps, converged when |delta xi|_inf <= 1e-14;
@@ -872,6 +873,41 @@ int mfgpu_points_evaluate(mfgpu_points *p, const void *u, void *values, void *gr
 int mfgpu_points_integrate(mfgpu_points *p, void *rhs, const void *weights, void *stream);
 size_t mfgpu_points_memory_consumption(const mfgpu_points *p); /* device bytes the object owns */
 void mfgpu_points_destroy(mfgpu_points *p);
+
+/* ---- point location on the device: mfgpu_locate_points for points that move ---------------
+ * The locator is created once per mesh from the integrator and the description it was created from (MFGPU_EINVAL when
+ * dim, degree or n_cells disagree or quadrature_points is missing; MFGPU_F32: MFGPU_EUNSUPPORTED).  It builds the
+ * candidate grid of mfgpu_locate_points on the host and keeps it on the device; the cells' Gauss points are BORROWED from
+ * the integrator, which must outlive the locator.
+ *
+ * mfgpu_locator_locate: x [n * dim], hint [n] (or NULL), cell [n], xi [n * dim] and n_not_found (one uint32_t, or NULL)
+ * are DEVICE pointers.  The call only enqueues on `stream`, allocates nothing and can be captured in a graph; n = 0 is
+ * allowed.  The result is defined exactly as for mfgpu_locate_points -- candidates in ascending order through the same
+ * bin grid, Newton on F(xi) = sum_q L_q(xi) (x_q - x) from the cell's centre with the same limits and tolerances, the
+ * first accepting cell wins, xi clamped to [0, 1], a point no cell accepts (outside the global box and NaN included)
+ * gets MFGPU_POINT_NOT_FOUND and xi = 0 -- evaluated in the device's arithmetic: the cells agree with the host's, xi to
+ * rounding.  *n_not_found is overwritten by every call (zeroed on the stream, then whole numbers added per wave): it does
+ * not accumulate and is deterministic.  One lane per point, every output entry written by its own lane, no
+ * floating-point atomics: two calls give bitwise-equal cell and xi.
+ * Hints: with hint[k] < n_cells the hinted cell is tried first, Newton from its centre, and taken only if the iteration
+ * converges with every xi_d in [1e-8, 1 - 1e-8]; otherwise (also for MFGPU_POINT_NOT_FOUND and any other value >=
+ * n_cells) the lane runs the ordinary search from the beginning.  Condition of the interface: the cells do not overlap
+ * and neighbouring cells differ in size by less than a factor of 100.  Then a point that far inside a cell is at least
+ * 1e-8 h from its boundary while any other cell accepts at most 1e-10 h' beyond its own, so no other cell accepts it and
+ * the hinted result equals the unhinted one bit for bit.  Every mesh stand-in below meets the condition.
+ * `hint` may be the same pointer as `cell` (a lane reads its hint before it writes its cell); no other pair of
+ * arguments may alias.  MFGPU_EINVAL: NULL x, cell or xi with n > 0.                                                    */
+typedef struct mfgpu_locator mfgpu_locator;
+int mfgpu_locator_create(mfgpu_integrator *it, const mfgpu_desc *desc, mfgpu_locator **out);
+int mfgpu_locator_locate(mfgpu_locator *l, const double *x, uint32_t n, const uint32_t *hint, uint32_t *cell, double *xi,
+                         uint32_t *n_not_found, void *stream);
+size_t mfgpu_locator_memory_consumption(const mfgpu_locator *l); /* device bytes the object owns */
+void mfgpu_locator_destroy(mfgpu_locator *l);
+/* The points object of (cell [n], xi [n * dim]) in DEVICE memory, as mfgpu_locator_locate leaves them: synchronises
+ * `stream`, downloads both (4 + 8 dim bytes per point) and calls mfgpu_points_create_in_cells.  This is the one
+ * synchronising step between locating on the device and evaluating; the object is the one described above.            */
+int mfgpu_points_create_located(mfgpu_integrator *it, const uint32_t *cell_dev, const double *xi_dev, uint32_t n,
+                                void *stream, mfgpu_points **out);
 
 /* ---- deal.II stand-in for the setup side (host only) --------------------------------------
  * Produces what Triangulation + DoFHandler + ConstraintMatrix + FEValues + ShapeInfo hand to
