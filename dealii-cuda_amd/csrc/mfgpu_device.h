@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -33,6 +34,15 @@ inline int einval(const char *msg) {
 inline size_t esize(int number_type) { return number_type == MFGPU_F32 ? 4 : 8; }
 inline bool valid_number_type(int number_type) { return number_type == MFGPU_F64 || number_type == MFGPU_F32; }
 
+// Guard mode (mfgpu_debug_guard_*, mfgpu_guard.hip; off unless a caller switches it on): an allocation becomes
+// [front guard | payload | back guard] with both guards and every unfilled floating-point payload set to 0xFF bytes
+// (a NaN as double and as float), and is registered until it is freed.  The payload begins 256-byte aligned, as a bare
+// hipMalloc's does.
+extern std::atomic<size_t> g_guard_bytes;  // 0: the mode is off
+// the padded allocation of `bytes` payload bytes: *payload and its distance *front (> 0) from the hipMalloc'ed base
+int guard_alloc(void **payload, size_t *front, size_t bytes, size_t guard, bool zero, bool poison);
+void guard_free(void *payload, size_t front);
+
 // One device allocation of n elements of T.  DeviceArray<void> counts in bytes and is read through as<Number>(): the
 // arrays whose element is the operator's number type.  A DeviceArray<T> moves into a DeviceArray<void>.
 template <typename T>
@@ -43,21 +53,53 @@ class DeviceArray {
 
  public:
   DeviceArray() = default;
-  DeviceArray(DeviceArray &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+  DeviceArray(DeviceArray &&o) noexcept : p_(o.p_), bytes_(o.bytes_), front_(o.front_) {
+    o.p_ = nullptr, o.bytes_ = 0, o.front_ = 0;
+  }
   template <typename U>
-  DeviceArray(DeviceArray<U> &&o) noexcept : p_(o.p_), bytes_(o.bytes_) {
-    o.p_ = nullptr, o.bytes_ = 0;
+  DeviceArray(DeviceArray<U> &&o) noexcept : p_(o.p_), bytes_(o.bytes_), front_(o.front_) {
+    o.p_ = nullptr, o.bytes_ = 0, o.front_ = 0;
   }
   DeviceArray &operator=(DeviceArray &&o) noexcept {
     std::swap(p_, o.p_);
     std::swap(bytes_, o.bytes_);
+    std::swap(front_, o.front_);
     return *this;
   }
-  ~DeviceArray() { hipFree(p_); }
+  ~DeviceArray() {
+    if (front_)
+      guard_free(p_, front_);
+    else
+      hipFree(p_);
+  }
 
-  int alloc(size_t n, bool zero = false) {
+  // without `zero` the payload is unspecified (guard mode: 0xFF bytes where T is a floating-point type or void, the
+  // Number arrays; integer arrays are left alone, an all-ones index would be a wild address)
+  int alloc(size_t n, bool zero = false) { return alloc_(n, zero, floating); }
+  int upload(const void *host, size_t n) {  // n = 0 leaves the array empty
+    if (const int rc = alloc_(n, false, false)) return rc;
+    if (n) HIP_TRY(hipMemcpy(p_, host, bytes_, hipMemcpyHostToDevice));
+    return 0;
+  }
+  T *get() const { return p_; }
+  template <typename Number>
+  Number *as() const {
+    static_assert(std::is_void<T>::value, "typed arrays are read through get()");
+    return static_cast<Number *>(p_);
+  }
+  size_t bytes() const { return bytes_; }  // of the payload
+
+ private:
+  static constexpr bool floating = std::is_void<T>::value || std::is_floating_point<T>::value;
+
+  int alloc_(size_t n, bool zero, bool poison) {
     *this = DeviceArray();
     if (n == 0) return 0;
+    if (const size_t guard = g_guard_bytes.load(std::memory_order_relaxed)) {
+      if (const int rc = guard_alloc((void **)&p_, &front_, n * elem, guard, zero, poison)) return rc;
+      bytes_ = n * elem;
+      return 0;
+    }
     HIP_TRY(hipMalloc((void **)&p_, n * elem));
     bytes_ = n * elem;
     if (zero) {
@@ -69,22 +111,10 @@ class DeviceArray {
     }
     return 0;
   }
-  int upload(const void *host, size_t n) {  // n = 0 leaves the array empty
-    if (const int rc = alloc(n)) return rc;
-    if (n) HIP_TRY(hipMemcpy(p_, host, bytes_, hipMemcpyHostToDevice));
-    return 0;
-  }
-  T *get() const { return p_; }
-  template <typename Number>
-  Number *as() const {
-    static_assert(std::is_void<T>::value, "typed arrays are read through get()");
-    return static_cast<Number *>(p_);
-  }
-  size_t bytes() const { return bytes_; }
 
- private:
   T *p_ = nullptr;
   size_t bytes_ = 0;
+  size_t front_ = 0;  // guard mode: bytes between the hipMalloc'ed base and p_
 };
 
 class Stream {

@@ -6,6 +6,7 @@ it has NO fallback: if the library is missing or a call fails it raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -140,6 +141,8 @@ SYMBOLS = [
     "mfgpu_points_destroy",
     "mfgpu_locator_create", "mfgpu_locator_locate", "mfgpu_locator_memory_consumption", "mfgpu_locator_destroy",
     "mfgpu_points_create_located",
+    "mfgpu_debug_guard_begin", "mfgpu_debug_guard_end", "mfgpu_debug_guard_layout", "mfgpu_debug_guard_check",
+    "mfgpu_debug_guard_selftest",
 ]
 
 _lib = None
@@ -348,6 +351,12 @@ def lib():
         L.mfgpu_locator_destroy.argtypes = [vp]
         L.mfgpu_locator_destroy.restype = None
         L.mfgpu_points_create_located.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp)]
+        u64p = C.POINTER(C.c_uint64)
+        L.mfgpu_debug_guard_begin.argtypes = [z]
+        L.mfgpu_debug_guard_end.argtypes = []
+        L.mfgpu_debug_guard_layout.argtypes = [z, z, C.POINTER(z), C.POINTER(z)]
+        L.mfgpu_debug_guard_check.argtypes = [u64p, u64p, C.c_char_p, z]
+        L.mfgpu_debug_guard_selftest.argtypes = [u64p, C.c_char_p, z, C.POINTER(i), C.POINTER(i)]
         _lib = L
     return _lib
 
@@ -1798,6 +1807,45 @@ def device_memory_info():
     f, t = C.c_size_t(), C.c_size_t()
     _check(lib().mfgpu_device_memory_info(C.byref(f), C.byref(t)))
     return f.value, t.value
+
+
+def guard_layout(n_bytes, guard_bytes):
+    """(total bytes, payload offset) of a guard-mode allocation (mfgpu_debug_guard_layout; needs no device)"""
+    total, off = C.c_size_t(), C.c_size_t()
+    _check(lib().mfgpu_debug_guard_layout(int(n_bytes), int(guard_bytes), C.byref(total), C.byref(off)))
+    return total.value, off.value
+
+
+@contextlib.contextmanager
+def guards(guard_bytes):
+    """guard mode of the library's own device arrays (include/mfgpu.h) for the handles created inside the block"""
+    _check(lib().mfgpu_debug_guard_begin(int(guard_bytes)))
+    try:
+        yield
+    finally:
+        _check(lib().mfgpu_debug_guard_end())
+
+
+def guard_check_raw():
+    """(n_live, n_damaged, report) of mfgpu_debug_guard_check"""
+    live, damaged, report = C.c_uint64(), C.c_uint64(), C.create_string_buffer(2048)
+    _check(lib().mfgpu_debug_guard_check(C.byref(live), C.byref(damaged), report, len(report)))
+    return int(live.value), int(damaged.value), report.value.decode()
+
+
+def guard_check():
+    """the number of registered arrays; raises with the report when a guard is damaged"""
+    live, damaged, report = guard_check_raw()
+    if damaged:
+        raise MfgpuError(f"{damaged} damaged guard(s) among {live} live arrays:\n{report}")
+    return live
+
+
+def guard_selftest():
+    """(n_damaged, report, poisoned_ok, zeroed_ok) of mfgpu_debug_guard_selftest"""
+    damaged, report, p_ok, z_ok = C.c_uint64(), C.create_string_buffer(2048), C.c_int(), C.c_int()
+    _check(lib().mfgpu_debug_guard_selftest(C.byref(damaged), report, len(report), C.byref(p_ok), C.byref(z_ok)))
+    return int(damaged.value), report.value.decode(), bool(p_ok.value), bool(z_ok.value)
 
 
 def dist_unique_id() -> bytes:

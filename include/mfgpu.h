@@ -330,6 +330,38 @@ int mfgpu_device_synchronize(void);
  * mfgpu_destroy / mfgpu_vec_free return everything mfgpu_create / mfgpu_vec_alloc took              */
 int mfgpu_device_memory_info(size_t *free_bytes, size_t *total_bytes); /* bmop.cu:148 */
 
+/* ---- guard mode: a debugging aid for the library's OWN device arrays (no reference counterpart) ---------------
+ * Off by default and switched by these calls only; the library reads no environment variable.  While the mode is on,
+ * every device array a handle allocates (halo, batch arrays, workspaces, the solvers' vectors; not mfgpu_vec_alloc's
+ * caller vectors and not the static buffer of the blocking reductions) is one allocation
+ *     [front guard | payload | back guard]
+ * whose payload begins at a multiple of 256 bytes, at least guard_bytes in, and whose back guard of guard_bytes bytes
+ * begins at the payload's last byte + 1.  Both guards hold 0xFF bytes (a NaN as double and as float).  A payload of
+ * floating-point numbers that the library allocates WITHOUT filling it holds the same bytes, so a kernel that uses a
+ * slot nothing wrote returns NaN; zero-filled and uploaded payloads are what they always are, and arrays of integers
+ * are never poisoned.  The fills are complete when the allocating call returns.  mfgpu_*_memory_consumption keeps
+ * counting payload bytes only.  Arrays allocated before _begin are neither padded nor registered; arrays allocated
+ * during the mode stay registered, and checked, until they are freed, also after _end.  Set-up calls only: do not
+ * switch the mode while another thread creates or destroys handles.
+ *   _begin   guard_bytes in [1, 2^30], else MFGPU_EINVAL; a second _begin changes the size for later allocations
+ *   _layout  the padding arithmetic alone (needs no device): total bytes of the allocation and the payload's offset
+ *   _check   synchronises the device, copies both guards of every registered array to the host and compares them byte
+ *            for byte.  n_live: registered arrays; n_damaged: damaged guards (an array has two).  report (len bytes,
+ *            may be NULL with len 0) gets one line for each of the first 8 damaged guards:
+ *              "array #<ordinal> (<payload bytes> payload bytes): back guard, offset +<k>: 0x<byte>"
+ *              "array #<ordinal> (<payload bytes> payload bytes): front guard, offset -<k>: 0x<byte>"
+ *            with the damaged byte nearest the payload: +0 is the first byte behind it, -1 the last in front of it.
+ *            Ordinals count the mode's allocations from 0 in allocation order.
+ *   _selftest  (guard mode only, else MFGPU_EINVAL) allocates one unfilled and one zero-filled array of doubles and
+ *            reads both back: *poisoned_ok = the first is all 0xFF, *zeroed_ok = the second all zero.  It then copies
+ *            8 bytes of 0x5a over the first bytes behind the unfilled array's payload and 8 over the last bytes in front
+ *            of it -- both inside that array's own allocation --, returns what _check then reports, and frees both.   */
+int mfgpu_debug_guard_begin(size_t guard_bytes);
+int mfgpu_debug_guard_end(void);
+int mfgpu_debug_guard_layout(size_t bytes, size_t guard_bytes, size_t *total, size_t *payload_offset);
+int mfgpu_debug_guard_check(uint64_t *n_live, uint64_t *n_damaged, char *report, size_t len);
+int mfgpu_debug_guard_selftest(uint64_t *n_damaged, char *report, size_t len, int *poisoned_ok, int *zeroed_ok);
+
 /* ---- single-node multi-GPU mode (no reference counterpart: the reference is single-GPU) --------
  * One process per GPU; the mesh is cut into z-slabs (mfgpu_mesh_create_uniform's slab arguments), each rank owns the
  * vector entries of its slab including both interface planes.  After the slab's cell loop an interface plane holds

@@ -14,7 +14,9 @@ pattern in its payload (Zoned(n, nt)); a vector the call reads or adds to gets i
 
 ZONE = 4096 elements on each side is a condition, not a measurement: it exceeds the longest per-batch dof list any kernel
 walks (p_kgu(7) * 64 = 2624 slots at p = 6, csrc/mfgpu_internal.h), so an access displaced by up to one whole batch list
-still lands in a zone.  The zones prove nothing about wild indices or about the library's own buffers."""
+still lands in a zone.  The zones prove nothing about indices that are wrong by more than a zone, about reads whose value
+is discarded, or about the library's own buffers: those sit between guards in tests/test_gpu_guards.py (the guard mode of
+include/mfgpu.h), all but g_red_buf, the static scratch of the blocking reductions."""
 import numpy as np
 
 import pymfgpu as mf
