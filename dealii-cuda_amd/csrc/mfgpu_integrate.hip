@@ -588,6 +588,7 @@ struct mfgpu_integrator {
   bool general = false;
   uint32_t n_cells = 0, n_dofs = 0;
   DeviceArray<uint32_t> d_l2g, d_cmask, d_off, d_idx;
+  DeviceArray<uint8_t> d_con;  // [n_dofs] 1 on a constrained dof (mfgpu_qop.hip: src mask and identity rows)
   DeviceArray<double> d_tab, d_qpts, d_jxw, d_metric, d_mass;
   DeviceArray<double> d_local, d_err, d_ones;
   // MFGPU_UPDATABLE_COEFFICIENTS: inv_jac and the (identity) cell order of the folds stay on the device -- what
@@ -615,6 +616,12 @@ IntegratorView mfgpu::integrator_view(const mfgpu_integrator *it) {
   v.rhs_off = it->d_off.get();
   v.tab = it->d_tab.get();
   v.qpts = it->d_qpts.get();
+  v.updatable = it->updatable;
+  v.rhs_idx = it->d_idx.get();
+  v.con = it->d_con.get();
+  v.jxw = it->d_jxw.get();
+  v.jinv = it->updatable ? it->geo.jinv.as<const double>() : nullptr;
+  v.local = it->d_local.get();
   return v;
 }
 
@@ -669,6 +676,7 @@ static int integrator_setup(mfgpu_integrator *it, const mfgpu_desc &d) {
     if (!con[d.loc2glob[j]]) idx[pos[d.loc2glob[j]]++] = (uint32_t)j;
   if ((rc = it->d_off.upload(off.data(), off.size()))) return rc;
   if ((rc = it->d_idx.upload(idx.data(), idx.size()))) return rc;
+  if ((rc = it->d_con.upload(con.data(), con.size()))) return rc;
   if ((rc = it->d_local.alloc(nc * nd))) return rc;
   if ((rc = it->d_err.alloc(nc))) return rc;
   std::vector<double> ones(nc, 1.0);

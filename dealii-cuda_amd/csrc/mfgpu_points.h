@@ -65,15 +65,21 @@ struct PointsPlan {
 int build_points_plan(int dim, uint32_t nd, uint32_t n_cells, uint32_t n_dofs, const uint32_t *loc2glob,
                       const uint8_t *constrained, const uint32_t *cell, const double *xi, uint32_t n, PointsPlan &plan);
 
-// What a points object borrows from its integrator (mfgpu_integrate.hip): device pointers, valid while it lives.
+// What a points object or a quadrature-point operator (mfgpu_qop.hip) borrows from its integrator
+// (mfgpu_integrate.hip): device pointers, valid while it lives.
 struct IntegratorView {
   int dim, n;
-  bool general;
+  bool general, updatable;
   uint32_t n_cells, n_dofs;
   const uint32_t *loc2glob, *cmask;  // [n_cells * n^dim]; [n_cells] or nullptr
   const uint32_t *rhs_off;           // [n_dofs + 1] CSR offsets of mfgpu_integrator_rhs: an empty range marks a
                                      // constrained (or unreferenced) dof
+  const uint32_t *rhs_idx;           // its index list: cell-major local indices, ascending per dof
+  const uint8_t *con;                // [n_dofs] 1 on a constrained dof
   const double *tab, *qpts;          // Tab<n>; [n_cells * n^dim * dim]
+  const double *jxw;                 // [n_cells * n^dim]
+  const double *jinv;                // updatable only: [n_cells] J0^-1, or with `general` J^-1 per point, row-major
+  double *local;                     // [n_cells * n^dim] the per-cell local vectors of mfgpu_integrator_rhs (scratch)
 };
 IntegratorView integrator_view(const mfgpu_integrator *it);
 

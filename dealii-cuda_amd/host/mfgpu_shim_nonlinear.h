@@ -111,6 +111,13 @@ void point_gradients(PoissonIntegrator<dim> &integrator, const GpuVector<double>
   check(mfgpu_integrator_evaluate(integrator.it, u.getDataRO(), nullptr, gradients_qp.getData(), nullptr),
         "point_gradients");
 }
+// both in one pass over the cells
+template <int dim>
+void point_values_and_gradients(PoissonIntegrator<dim> &integrator, const GpuVector<double> &u, GpuVector<double> &values_qp,
+                                GpuVector<double> &gradients_qp) {
+  check(mfgpu_integrator_evaluate(integrator.it, u.getDataRO(), values_qp.getData(), gradients_qp.getData(), nullptr),
+        "point_values_and_gradients");
+}
 }  // namespace VectorTools
 
 }  // namespace mfgpu_shim

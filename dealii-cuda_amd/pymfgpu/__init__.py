@@ -89,6 +89,16 @@ class VCycleDesc(C.Structure):
                 ("coarse_tolerance", C.c_double), ("coarse_max_iterations", C.c_uint32)]
 
 
+# terms of a QpOperator (MFGPU_QOP_*) and the flag of its vmult
+QOP_DIFFUSION_SCALAR, QOP_DIFFUSION_TENSOR, QOP_CONVECTION, QOP_FLUX, QOP_REACTION = 1, 2, 4, 8, 16
+QOP_TRANSPOSE = 1
+
+
+class QopCoefficients(C.Structure):
+    """mirror of struct mfgpu_qop_coefficients (device pointers)"""
+    _fields_ = [("diffusion", C.c_void_p), ("convection", C.c_void_p), ("flux", C.c_void_p), ("reaction", C.c_void_p)]
+
+
 # int fn(void *ctx, void *z_dev, const void *r_dev, void *stream)
 CG_CALLBACK_TYPE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
@@ -143,6 +153,8 @@ SYMBOLS = [
     "mfgpu_points_create_located",
     "mfgpu_debug_guard_begin", "mfgpu_debug_guard_end", "mfgpu_debug_guard_layout", "mfgpu_debug_guard_check",
     "mfgpu_debug_guard_selftest",
+    "mfgpu_integrator_integrate", "mfgpu_qop_create", "mfgpu_qop_set_coefficients", "mfgpu_qop_vmult",
+    "mfgpu_qop_compute_inverse_diagonal", "mfgpu_qop_memory_consumption", "mfgpu_qop_destroy",
 ]
 
 _lib = None
@@ -357,6 +369,15 @@ def lib():
         L.mfgpu_debug_guard_layout.argtypes = [z, z, C.POINTER(z), C.POINTER(z)]
         L.mfgpu_debug_guard_check.argtypes = [u64p, u64p, C.c_char_p, z]
         L.mfgpu_debug_guard_selftest.argtypes = [u64p, C.c_char_p, z, C.POINTER(i), C.POINTER(i)]
+        L.mfgpu_integrator_integrate.argtypes = [vp, vp, vp, vp, vp]
+        L.mfgpu_qop_create.argtypes = [vp, u32, C.POINTER(vp)]
+        L.mfgpu_qop_set_coefficients.argtypes = [vp, C.POINTER(QopCoefficients), vp]
+        L.mfgpu_qop_vmult.argtypes = [vp, vp, vp, u32, vp]
+        L.mfgpu_qop_compute_inverse_diagonal.argtypes = [vp, vp, vp]
+        L.mfgpu_qop_memory_consumption.argtypes = [vp]
+        L.mfgpu_qop_memory_consumption.restype = C.c_size_t
+        L.mfgpu_qop_destroy.argtypes = [vp]
+        L.mfgpu_qop_destroy.restype = None
         _lib = L
     return _lib
 
@@ -1036,6 +1057,42 @@ class Integrator:
         v = DeviceVector(self.n_cells * self.n_error_points * self.dim)
         _check(lib().mfgpu_integrator_error_points(self._h, v.ptr, None))
         return v.to_host().reshape(self.n_cells, self.n_error_points, self.dim)
+
+    def integrate(self, dst, values=None, gradients=None, stream=None):
+        """the transpose of evaluate: dst_i = sum_q JxW_q (phi_i v_q + grad phi_i . g_q), constrained rows 0; values
+        [n_cells * (p+1)^dim], gradients [n_cells * (p+1)^dim * dim] real-space (need UPDATABLE_COEFFICIENTS)"""
+        _check(lib().mfgpu_integrator_integrate(self._h, _ptr(dst), _optr(values), _optr(gradients), stream))
+
+
+class QpOperator:
+    """mfgpu_qop_*: (A u)_i = sum_q JxW_q [grad phi_i . (D grad u + gamma u) + phi_i (beta . grad u + c u)] with the
+    coefficients given at the quadrature points (device arrays in the layout of Integrator.evaluate).  terms: QOP_* bits.
+    Borrows the integrator, which it keeps alive."""
+
+    def __init__(self, integrator: "Integrator", terms):
+        self._it = integrator
+        h = C.c_void_p()
+        _check(lib().mfgpu_qop_create(integrator._h, int(terms), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_qop_destroy(self._h)
+            self._h = None
+
+    def set_coefficients(self, diffusion=None, convection=None, flux=None, reaction=None, stream=None):
+        """folds the given real-space arrays; None keeps a term's last values"""
+        c = QopCoefficients(_optr(diffusion), _optr(convection), _optr(flux), _optr(reaction))
+        _check(lib().mfgpu_qop_set_coefficients(self._h, C.byref(c), stream))
+
+    def vmult(self, dst, src, transpose=False, stream=None):
+        _check(lib().mfgpu_qop_vmult(self._h, _ptr(dst), _ptr(src), QOP_TRANSPOSE if transpose else 0, stream))
+
+    def inverse_diagonal(self, inv_diag, stream=None):
+        _check(lib().mfgpu_qop_compute_inverse_diagonal(self._h, _ptr(inv_diag), stream))
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_qop_memory_consumption(self._h))
 
 
 POINT_NOT_FOUND = 0xffffffff  # MFGPU_POINT_NOT_FOUND

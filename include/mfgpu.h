@@ -848,7 +848,74 @@ int mfgpu_integrator_evaluate(mfgpu_integrator *it, const void *u, void *values_
  * bitwise-equal results.  Asynchronous: enqueues on `stream` and reads nothing back.                                 */
 int mfgpu_integrator_recovery_indicator(mfgpu_integrator *it, const void *u, const void *weight_qp, void *per_cell,
                                         void *stream);
+/* The transpose of mfgpu_integrator_evaluate -- the submit_value / submit_gradient / integrate /
+ * distribute_local_to_global half of FEEvaluationGpu (fee_gpu.cuh) for point data the caller formed:
+ *   dst_i = sum_cells sum_q JxW_q [ phi_i(x_q) v_q + grad_x phi_i(x_q) . g_q ]
+ * values_qp: v [n_cells * (p+1)^dim]; gradients_qp: g [n_cells * (p+1)^dim * dim], real-space vectors (x, y, z per
+ * point; the kernel applies J^-1 per point, or J0^-1, before the reference-gradient contraction); both in the layout
+ * mfgpu_integrator_evaluate writes.  Either may be NULL (both: MFGPU_EINVAL).  gradients_qp != NULL on an integrator
+ * created without MFGPU_UPDATABLE_COEFFICIENTS is MFGPU_EINVAL (inv_jac is needed on the device), as for evaluate.
+ * Distributed like a cell result (transposed hanging-node resolution) through the CSR gather of mfgpu_integrator_rhs:
+ * constrained rows 0, every entry of dst written, no atomics (two calls give bitwise-equal results).  It uses the
+ * integrator's per-cell scratch, as mfgpu_integrator_rhs and every mfgpu_qop of the integrator do: calls that share
+ * an integrator must be ordered (one stream, or events).  Asynchronous.                                            */
+int mfgpu_integrator_integrate(mfgpu_integrator *it, void *dst, const void *values_qp, const void *gradients_qp,
+                               void *stream);
 void mfgpu_integrator_destroy(mfgpu_integrator *it);
+
+/* ---- the general linear second-order operator on quadrature-point coefficients (no reference counterpart; deal.II: a
+ * user LocOp over FEEvaluation) -------------------------------------------------------------
+ * Free rows:
+ *   (A u)_i = sum_cells sum_q JxW_q [ grad phi_i . (D_q grad u_q + gamma_q u_q) + phi_i (beta_q . grad u_q + c_q u_q) ]
+ * constrained rows are identity rows (dst_c = src_c) and constrained entries of src are read as 0, both as mfgpu_vmult,
+ * so mfgpu_vec_* solvers written for the operator work unchanged; a dof no cell references gets 0.  One cell kernel
+ * (one wave per cell, evaluate -> point-wise terms -> integrate in LDS) plus the integrator's per-dof gather; no
+ * atomics, bitwise repeatable, enqueue only.  MFGPU_F64 only, as the integrator.
+ *
+ * The object is created from an integrator, BORROWS its geometry, gather lists and per-cell scratch, and must be
+ * destroyed before it; calls on one integrator and its operators must be ordered (see mfgpu_integrator_integrate).
+ * terms: a non-empty set of the bits below; both diffusion bits, or an unknown bit: MFGPU_EINVAL.  Every term but
+ * MFGPU_QOP_REACTION needs an integrator created with MFGPU_UPDATABLE_COEFFICIENTS (else MFGPU_EINVAL).
+ *
+ * mfgpu_qop_set_coefficients FOLDS the caller's real-space device arrays (doubles, cell-major in the description's cell
+ * order, points x fastest, vectors (x, y, z) and matrices row-major per point) into reference form:
+ *   JxW J^-1 D J^-T (dim^2 values per point; scalar D = a I on MFGPU_UNIFORM_J0: the one value a J0^2 JxW),
+ *   JxW J^-1 gamma, JxW J^-1 beta (dim values each), JxW c (one value),
+ * so mfgpu_qop_vmult reads neither inv_jac nor JxW.  A pointer for a term in `terms` replaces that term, NULL keeps its
+ * last values; a pointer for a term not in `terms`, or NULL everywhere, is MFGPU_EINVAL.  It only enqueues (the arrays
+ * may be reused after the stream passes the call), reads nothing back and allocates nothing.  mfgpu_qop_vmult and
+ * mfgpu_qop_compute_inverse_diagonal before every term has been set once: MFGPU_EINVAL.
+ *
+ * Only the terms in `terms` get storage; mfgpu_qop_memory_consumption returns exactly the folded bytes.  Per point:
+ *   MFGPU_QOP_DIFFUSION_SCALAR  8 (MFGPU_UNIFORM_J0)  or 8 dim^2 (general geometry)
+ *   MFGPU_QOP_DIFFUSION_TENSOR  8 dim^2
+ *   MFGPU_QOP_CONVECTION        8 dim
+ *   MFGPU_QOP_FLUX              8 dim
+ *   MFGPU_QOP_REACTION          8
+ * e.g. all five terms in 3D: 8 (9 + 3 + 3 + 1) = 128; scalar diffusion + reaction on a uniform-J0 mesh: 16.
+ *
+ * mfgpu_qop_vmult flags: 0, or MFGPU_QOP_TRANSPOSE for A^T (D -> D^T, beta <-> gamma on the folded arrays).  src is
+ * never written; dst may be src (in place: the cell kernel has read src into the per-cell scratch before the gather
+ * writes dst, and an identity row reads its entry before it writes it).
+ * mfgpu_qop_compute_inverse_diagonal: inv_diag_i = 1 / A_ii of the operator above with the hanging-node constraints
+ * applied (the cell operator on local unit vectors, both resolutions); 1 on constrained and unreferenced dofs.  Set-up
+ * work: (p+1)^dim cell applies per cell.                                                                             */
+typedef struct mfgpu_qop mfgpu_qop;
+#define MFGPU_QOP_DIFFUSION_SCALAR (1u << 0) /* D = a I,   a [n_cells*ND]                    */
+#define MFGPU_QOP_DIFFUSION_TENSOR (1u << 1) /* D [n_cells*ND*dim*dim] row-major, any matrix */
+#define MFGPU_QOP_CONVECTION       (1u << 2) /* beta  [n_cells*ND*dim]                       */
+#define MFGPU_QOP_FLUX             (1u << 3) /* gamma [n_cells*ND*dim]                       */
+#define MFGPU_QOP_REACTION         (1u << 4) /* c [n_cells*ND]                               */
+#define MFGPU_QOP_TRANSPOSE        (1u << 0) /* vmult flag: apply A^T (D -> D^T, beta <-> gamma) */
+typedef struct mfgpu_qop_coefficients {
+  const void *diffusion, *convection, *flux, *reaction; /* device arrays */
+} mfgpu_qop_coefficients;
+int mfgpu_qop_create(mfgpu_integrator *it, uint32_t terms, mfgpu_qop **out);
+int mfgpu_qop_set_coefficients(mfgpu_qop *q, const mfgpu_qop_coefficients *c, void *stream);
+int mfgpu_qop_vmult(mfgpu_qop *q, void *dst, const void *src, uint32_t flags, void *stream);
+int mfgpu_qop_compute_inverse_diagonal(mfgpu_qop *q, void *inv_diag, void *stream);
+size_t mfgpu_qop_memory_consumption(const mfgpu_qop *q);
+void mfgpu_qop_destroy(mfgpu_qop *q);
 
 /* ---- fields and point sources at arbitrary points (no reference counterpart; deal.II: VectorTools::point_value /
  * point_gradient, FEPointEvaluation::evaluate / integrate, create_point_source_vector) --------
