@@ -262,6 +262,8 @@ int handle_pass2_group(mfgpu_handle *h, int group, void *dst, const void *src, v
 // what mfgpu_vcycle (mfgpu_vcycle.hip) checks of the pieces it borrows, and mfgpu_cg_set_vcycle of the V-cycle
 void transfer_sizes(const mfgpu_transfer *t, uint32_t *n_coarse_dofs, uint32_t *n_fine_dofs, int *number_type);
 void vcycle_active(const mfgpu_vcycle *v, int *active_type, uint32_t *n_active);
+// what mfgpu_bicgstab_set_operator_qop checks of the operator it borrows
+uint32_t qop_n_dofs(const mfgpu_qop *q);
 
 }  // namespace mfgpu
 

@@ -492,3 +492,7 @@ size_t mfgpu_qop_memory_consumption(const mfgpu_qop *q) {
 }
 
 void mfgpu_qop_destroy(mfgpu_qop *q) { delete q; }
+
+namespace mfgpu {
+uint32_t qop_n_dofs(const mfgpu_qop *q) { return q->iv.n_dofs; }
+}  // namespace mfgpu

@@ -77,6 +77,7 @@ public:
     return inverse_diagonal_matrix;
   }
   std::size_t memory_consumption() const { return mfgpu_qop_memory_consumption(qop); }
+  mfgpu_qop *get_qop() const { return qop; }  // SolverBicgstabDevice
 
 private:
   mfgpu_qop *qop = nullptr;
@@ -163,6 +164,98 @@ public:
 
 private:
   SolverControl &control;
+};
+
+// The same solver with its loop on the device (mfgpu_bicgstab, include/mfgpu.h), as SolverCGDevice is to SolverCG: the
+// scalars stay in a device state block, the host reads them once every check_every iterations.  A matrix with get_qop()
+// (QpOperatorGpu) is applied inside the library, any other through its vmult; DiagonalMatrix maps to MFGPU_CG_JACOBI,
+// MultigridPreconditionerDevice to mfgpu_bicgstab_set_vcycle, anything else with a vmult(z, r) is called back twice per
+// iteration.
+template <typename VectorType>
+class SolverBicgstabDevice {
+public:
+  typedef typename VectorType::value_type Number;
+  explicit SolverBicgstabDevice(SolverControl &control, unsigned int check_every = 10)
+      : control(control), check_every(check_every) {}
+  template <typename MatrixType>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b, const DiagonalMatrix<Number> &prec) {
+    Run run(b.size(), MFGPU_CG_JACOBI, prec.get_vector().getDataRO());
+    Callback<MatrixType> op{&A, b.size(), &run.error};
+    set_operator(run, A, op, 0);
+    finish(run, x, b);
+  }
+  template <typename MatrixType, int dim, typename LevelMatrixType, typename LevelNumber, typename CoarseSolver>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b,
+             const MultigridPreconditionerDevice<dim, LevelMatrixType, LevelNumber, CoarseSolver, Number> &prec) {
+    Run run(b.size(), MFGPU_CG_CALLBACK, nullptr);
+    Callback<MatrixType> op{&A, b.size(), &run.error};
+    set_operator(run, A, op, 0);
+    check(mfgpu_bicgstab_set_vcycle(run.s, prec.get_vcycle()), "SolverBicgstabDevice");
+    finish(run, x, b);
+  }
+  template <typename MatrixType, typename PreconditionerType>
+  void solve(const MatrixType &A, VectorType &x, const VectorType &b, const PreconditionerType &prec) {
+    Run run(b.size(), MFGPU_CG_CALLBACK, nullptr);
+    Callback<MatrixType> op{&A, b.size(), &run.error};
+    Callback<PreconditionerType> pc{&prec, b.size(), &run.error};
+    set_operator(run, A, op, 0);
+    check(mfgpu_bicgstab_set_callback(run.s, &Callback<PreconditionerType>::call, &pc), "SolverBicgstabDevice");
+    finish(run, x, b);
+  }
+
+private:
+  // the solver object of one solve, destroyed with it
+  struct Run {
+    mfgpu_bicgstab *s = nullptr;
+    std::string error;  // of a callback: no exception crosses the C-ABI
+    Run(unsigned int n, int preconditioner, const void *inv_diag) {
+      check(mfgpu_bicgstab_create(n, number_type<Number>(), preconditioner, inv_diag, &s), "SolverBicgstabDevice");
+    }
+    ~Run() { mfgpu_bicgstab_destroy(s); }
+    Run(const Run &) = delete;
+    Run &operator=(const Run &) = delete;
+  };
+  // dst = object.vmult(src) on the solver's vectors: the operator, or z = prec^-1 r
+  template <typename ObjectType>
+  struct Callback {
+    const ObjectType *object;
+    unsigned int n;
+    std::string *error;
+    static int call(void *ctx, void *dst_dev, const void *src_dev, void *) {
+      Callback *self = static_cast<Callback *>(ctx);
+      try {
+        VectorType dst(dst_dev, self->n, typename VectorType::borrowed_t()),
+            src(const_cast<void *>(src_dev), self->n, typename VectorType::borrowed_t());
+        self->object->vmult(dst, src);
+        return 0;
+      } catch (std::exception &e) {
+        *self->error = e.what();
+        return MFGPU_EHIP;
+      }
+    }
+  };
+  template <typename MatrixType>
+  static auto set_operator(Run &run, const MatrixType &A, Callback<MatrixType> &, int) -> decltype(A.get_qop(), void()) {
+    check(mfgpu_bicgstab_set_operator_qop(run.s, A.get_qop(), 0), "SolverBicgstabDevice");
+  }
+  template <typename MatrixType>
+  static void set_operator(Run &run, const MatrixType &, Callback<MatrixType> &op, long) {
+    check(mfgpu_bicgstab_set_operator(run.s, &Callback<MatrixType>::call, &op), "SolverBicgstabDevice");
+  }
+  void finish(Run &run, VectorType &x, const VectorType &b) {
+    if (x.size() != b.size()) x.reinit(b.size());
+    mfgpu_cg_info info{};
+    const int rc = mfgpu_bicgstab_solve(run.s, x.getData(), b.getDataRO(), control.tolerance, control.max_steps,
+                                        check_every, nullptr, &info);
+    if (rc != 0 && !run.error.empty()) throw std::runtime_error("SolverBicgstabDevice: " + run.error);
+    check(rc, "SolverBicgstabDevice");
+    control.steps = info.iterations;
+    if (info.status == 2)
+      throw std::runtime_error("SolverBicgstab: no convergence in " + std::to_string(control.max_steps) + " steps");
+    if (info.status == 3) throw std::runtime_error("SolverBicgstab: breakdown, r0.v, t.t or rho is zero or not finite");
+  }
+  SolverControl &control;
+  unsigned int check_every;
 };
 
 }  // namespace mfgpu_shim

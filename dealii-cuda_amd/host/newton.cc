@@ -9,6 +9,8 @@
 //             and flux gamma = 2 u grad u, both formed on the device from the same two arrays
 //   solve     J d = -R by BiCGStab preconditioned with the inverse diagonal, to 1e-12 |R|; u += d (d is zero on every
 //             constrained dof).  Only norms and dot products return to the host.
+//             -DNEWTON_DEVICE_BICGSTAB (the -devbicg binaries): the same solver with its loop on the device,
+//             SolverBicgstabDevice; same arguments and output lines
 //   error     L2 error of the last iterate on QGauss(p+2)
 // usage: newton-<dim>d-p<k> [-q] [min_cycle] [max_cycle]     (default max_cycle 6 - dim)
 // -q prints one line per cycle:
@@ -95,7 +97,11 @@ void run_cycle(unsigned int cycle) {
     jacobian.compute_diagonal();
     residual *= -1.0;
     SolverControl solver_control(10000, 1e-12 * residual.l2_norm());
+#ifdef NEWTON_DEVICE_BICGSTAB
+    SolverBicgstabDevice<VectorType> bicgstab(solver_control);  // the loop on the device (mfgpu_bicgstab): -devbicg
+#else
     SolverBicgstab<VectorType> bicgstab(solver_control);
+#endif
     bicgstab.solve(jacobian, update, residual, *jacobian.get_diagonal_inverse());
     inner += solver_control.last_step();
     ++newton;

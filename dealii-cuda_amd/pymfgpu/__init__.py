@@ -46,6 +46,7 @@ class Desc(C.Structure):
 
 CG_NONE, CG_JACOBI, CG_CHEBYSHEV, CG_CALLBACK = 0, 1, 2, 3  # preconditioner of CG (MFGPU_CG_*)
 CG_STATE_BYTES, CG_PARTIAL_BYTES = 128, 3 * 2048 * 8  # the fixed device blocks of a CG (mfgpu_cg_create)
+BICGSTAB_STATE_BYTES, BICGSTAB_PARTIAL_BYTES = 128, 6 * 2048 * 8  # ... and of a BiCGStab (mfgpu_bicgstab_create)
 
 
 class CGInfo(C.Structure):
@@ -155,6 +156,10 @@ SYMBOLS = [
     "mfgpu_debug_guard_selftest",
     "mfgpu_integrator_integrate", "mfgpu_qop_create", "mfgpu_qop_set_coefficients", "mfgpu_qop_vmult",
     "mfgpu_qop_compute_inverse_diagonal", "mfgpu_qop_memory_consumption", "mfgpu_qop_destroy",
+    "mfgpu_bicgstab_create", "mfgpu_bicgstab_set_operator", "mfgpu_bicgstab_set_operator_handle",
+    "mfgpu_bicgstab_set_operator_qop", "mfgpu_bicgstab_set_callback", "mfgpu_bicgstab_set_vcycle", "mfgpu_bicgstab_begin",
+    "mfgpu_bicgstab_begin_relative", "mfgpu_bicgstab_iterate", "mfgpu_bicgstab_status", "mfgpu_bicgstab_solve",
+    "mfgpu_bicgstab_memory_consumption", "mfgpu_bicgstab_destroy",
 ]
 
 _lib = None
@@ -299,6 +304,21 @@ def lib():
         L.mfgpu_cg_chebyshev_scalars.argtypes = [u32, d, d, C.POINTER(d)]
         L.mfgpu_cg_begin_relative.argtypes = [vp, vp, vp, d, u32, vp]
         L.mfgpu_cg_set_vcycle.argtypes = [vp, vp]
+        L.mfgpu_bicgstab_create.argtypes = [C.c_size_t, i, i, vp, C.POINTER(vp)]
+        L.mfgpu_bicgstab_set_operator.argtypes = [vp, CG_CALLBACK_TYPE, vp]
+        L.mfgpu_bicgstab_set_operator_handle.argtypes = [vp, vp]
+        L.mfgpu_bicgstab_set_operator_qop.argtypes = [vp, vp, u32]
+        L.mfgpu_bicgstab_set_callback.argtypes = [vp, CG_CALLBACK_TYPE, vp]
+        L.mfgpu_bicgstab_set_vcycle.argtypes = [vp, vp]
+        L.mfgpu_bicgstab_begin.argtypes = [vp, vp, vp, d, u32, vp]
+        L.mfgpu_bicgstab_begin_relative.argtypes = [vp, vp, vp, d, u32, vp]
+        L.mfgpu_bicgstab_iterate.argtypes = [vp, u32, vp]
+        L.mfgpu_bicgstab_status.argtypes = [vp, vp, C.POINTER(CGInfo)]
+        L.mfgpu_bicgstab_solve.argtypes = [vp, vp, vp, d, u32, u32, vp, C.POINTER(CGInfo)]
+        L.mfgpu_bicgstab_memory_consumption.argtypes = [vp]
+        L.mfgpu_bicgstab_memory_consumption.restype = C.c_size_t
+        L.mfgpu_bicgstab_destroy.argtypes = [vp]
+        L.mfgpu_bicgstab_destroy.restype = None
         L.mfgpu_transfer_prolongate_add.argtypes = [vp, vp, vp, vp]
         L.mfgpu_vec_residual.argtypes = [vp, vp, vp, z, i, vp]
         L.mfgpu_vcycle_create.argtypes = [C.POINTER(VCycleDesc), C.POINTER(vp)]
@@ -1007,6 +1027,7 @@ class Integrator:
     def __init__(self, desc: Desc, keep=None):
         self._keep = keep
         self.dim, self.degree, self.n_cells = int(desc.dim), int(desc.degree), int(desc.n_cells)
+        self.n_dofs = int(desc.n_dofs)
         h = C.c_void_p()
         _check(lib().mfgpu_integrator_create(C.byref(desc), C.byref(h)))
         self._h = h
@@ -1093,6 +1114,109 @@ class QpOperator:
 
     def memory_consumption(self):
         return int(lib().mfgpu_qop_memory_consumption(self._h))
+
+    def n(self):
+        return self._it.n_dofs
+
+    m = n
+
+
+class BiCGStab:
+    """Device-resident BiCGStab (mfgpu_bicgstab_*) for the non-symmetric operators, in the shape of CG: begin and iterate
+    only enqueue work, status is the only blocking call.  operator: an Operator, a QpOperator (transpose=True solves with
+    A^T) or a callable apply(dst, src, stream) -> 0 / None or an error code that enqueues dst = A src on `stream`, with
+    dst and src DeviceVector views of the solver's vectors; a callable needs n (and number_type).  preconditioner:
+    CG_NONE, CG_JACOBI (inv_diag) or CG_CALLBACK with callback(z, r, stream) as for CG, or set_vcycle.  The operator,
+    inv_diag, x and b must outlive the solve.  The methods return the raw code with check=False."""
+
+    def __init__(self, operator, preconditioner=CG_NONE, inv_diag=None, callback=None, transpose=False, n=None,
+                 number_type=None):
+        self._op, self._inv_diag = operator, inv_diag
+        self._cb = self._apply = self._cb_error = None
+        if isinstance(operator, (Operator, QpOperator)):
+            self.n = operator.n()
+            self.number_type = operator.number_type if isinstance(operator, Operator) else F64
+        elif callable(operator):
+            if n is None:
+                raise ValueError("BiCGStab on a callable needs n")
+            self.n, self.number_type = int(n), F64 if number_type is None else number_type
+        else:
+            raise TypeError("BiCGStab: operator must be an Operator, a QpOperator or a callable")
+        h = C.c_void_p()
+        _check(lib().mfgpu_bicgstab_create(self.n, int(self.number_type), int(preconditioner), _optr(inv_diag), C.byref(h)))
+        self._h = h
+        if isinstance(operator, Operator):
+            _check(lib().mfgpu_bicgstab_set_operator_handle(h, operator._h))
+        elif isinstance(operator, QpOperator):
+            _check(lib().mfgpu_bicgstab_set_operator_qop(h, operator._h, QOP_TRANSPOSE if transpose else 0))
+        else:
+            self._apply = CG_CALLBACK_TYPE(self._trampoline(operator))
+            _check(lib().mfgpu_bicgstab_set_operator(h, self._apply, None))
+        if callback is not None:
+            self.set_callback(callback)
+
+    def _trampoline(self, f):
+        def trampoline(_ctx, dst, src, stream):
+            try:
+                rc = f(DeviceVector.view(dst, self.n, self.number_type), DeviceVector.view(src, self.n, self.number_type),
+                       stream)
+                return 0 if rc is None else int(rc)
+            except Exception as e:  # no exception crosses the C-ABI: kept for _done
+                self._cb_error = e
+                return EINVAL
+
+        return trampoline
+
+    def set_callback(self, callback):
+        cb = CG_CALLBACK_TYPE(self._trampoline(callback))
+        _check(lib().mfgpu_bicgstab_set_callback(self._h, cb, None))
+        self._cb = cb  # the library keeps the function pointer: keep the ctypes object alive
+
+    def set_vcycle(self, vcycle: "VCycle", check=True):
+        """the library's own callback of a CG_CALLBACK solver: z = vcycle.apply(r) without a trip through Python"""
+        rc = lib().mfgpu_bicgstab_set_vcycle(self._h, vcycle._h)
+        if rc == 0:
+            self._vcycle = vcycle  # borrowed by the library
+        return _check(rc) if check else rc
+
+    def _done(self, rc, check):
+        e, self._cb_error = self._cb_error, None
+        if e is not None:
+            raise e
+        return _check(rc) if check else rc
+
+    def destroy(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_bicgstab_destroy(self._h)
+            self._h = None
+
+    __del__ = destroy
+
+    def begin(self, x, b, tolerance, max_iterations, stream=None, check=True):
+        return self._done(lib().mfgpu_bicgstab_begin(self._h, _optr(x), _optr(b), float(tolerance), int(max_iterations),
+                                                     stream), check)
+
+    def begin_relative(self, x, b, relative_tolerance, max_iterations, stream=None, check=True):
+        """begin with tolerance = relative_tolerance * |b|, formed on the device (mfgpu_bicgstab_begin_relative)"""
+        return self._done(lib().mfgpu_bicgstab_begin_relative(self._h, _optr(x), _optr(b), float(relative_tolerance),
+                                                              int(max_iterations), stream), check)
+
+    def iterate(self, n_iterations=1, stream=None, check=True):
+        return self._done(lib().mfgpu_bicgstab_iterate(self._h, int(n_iterations), stream), check)
+
+    def status(self, stream=None):
+        info = CGInfo()
+        _check(lib().mfgpu_bicgstab_status(self._h, stream, C.byref(info)))
+        return info
+
+    def solve(self, x, b, tolerance, max_iterations, check_every=10, stream=None, check=True):
+        info = CGInfo()
+        rc = self._done(lib().mfgpu_bicgstab_solve(self._h, _optr(x), _optr(b), float(tolerance), int(max_iterations),
+                                                   int(check_every), stream, C.byref(info)), check)
+        return info if check else rc
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_bicgstab_memory_consumption(self._h))
 
 
 POINT_NOT_FOUND = 0xffffffff  # MFGPU_POINT_NOT_FOUND

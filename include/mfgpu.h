@@ -917,6 +917,69 @@ int mfgpu_qop_compute_inverse_diagonal(mfgpu_qop *q, void *inv_diag, void *strea
 size_t mfgpu_qop_memory_consumption(const mfgpu_qop *q);
 void mfgpu_qop_destroy(mfgpu_qop *q);
 
+/* ---- device-resident BiCGStab (no reference counterpart): the solver for the non-symmetric
+ * operators above, in the style of mfgpu_cg.  The algorithm is SolverBicgstab::solve of host/mfgpu_shim_qop.h:
+ * right-preconditioned, zero start (x = 0, r = r0 = b), per iteration p = r + beta (p - omega v), y = M^-1 p, v = A y,
+ * alpha = rho / (r0.v), x += alpha y, s = r - alpha v (kept in r), exit when |s| <= tolerance; else z = M^-1 s, t = A z,
+ * omega = (t.s) / (t.t), x += omega z, r = s - omega t, exit when |r| <= tolerance.  Every scalar (rho, alpha, omega,
+ * beta, the norms, the tolerance, the iteration count, the status) lives in a 128-byte device state block; the sums
+ * accumulate in double over a fixed grid in a fixed order; the scalars are formed in double and rounded to the number
+ * type before any element-wise use.  mfgpu_bicgstab_begin and _iterate only enqueue work on `stream` (no allocation, no
+ * synchronisation, no host read-back: they can be captured in a graph); mfgpu_bicgstab_status is the only blocking call.
+ * The operator is a callback, so that a handle, a mfgpu_qop (or its transpose) or the caller's own code serves.
+ * Status (mfgpu_cg_info): 0 running, 1 converged, 2 max iterations, 3 breakdown (r0.v, t.t or rho zero or not finite; x
+ * is then at the last complete update).  iterations counts as SolverControl::steps does: an exit after the half step of
+ * iteration k reports k, with residual = |s|.  That exit takes effect on the device: the operator apply and the sums
+ * that were enqueued behind it run and write t and partial sums only.
+ * Freeze rule: once the status has left 0 every solver kernel returns without writing a vector (the operator and the
+ * preconditioner still run, on unchanged inputs), so x, the count and the residual do not depend on how many iterations
+ * were enqueued past the end, nor on check_every.
+ * One object is used on one stream at a time; x, b and inv_diag must stay valid and unchanged (x: untouched by others)
+ * from begin until the solve is over; the operator, V-cycle and callbacks are borrowed and must outlive the solves.   */
+typedef struct mfgpu_bicgstab mfgpu_bicgstab;
+/* All allocation happens here: the work vectors r, r0, p, v, t (5 vectors of n_dofs numbers; MFGPU_CG_JACOBI and
+ * MFGPU_CG_CALLBACK: + y and z = 7; with MFGPU_CG_NONE y is p and z is r), 6 * 2048 doubles of partial sums, the 128-byte
+ * state block -- mfgpu_bicgstab_memory_consumption is exactly their sum -- and a pinned host mirror of the state block.
+ * preconditioner: MFGPU_CG_NONE, MFGPU_CG_JACOBI (inv_diag_dev of the number type, read, not copied) or
+ * MFGPU_CG_CALLBACK.  MFGPU_EINVAL, nothing created: null out, n_dofs == 0, an unknown number type, an unknown
+ * preconditioner or MFGPU_CG_CHEBYSHEV (not offered), JACOBI without inv_diag_dev.                                     */
+int mfgpu_bicgstab_create(size_t n_dofs, int number_type, int preconditioner, const void *inv_diag_dev,
+                          mfgpu_bicgstab **out);
+/* the operator, one of three: apply enqueues dst = A src on `stream` (a non-zero return ends begin / iterate with that
+ * code); a handle (mfgpu_vmult; MFGPU_EINVAL unless its number type and length are the solver's); a mfgpu_qop
+ * (mfgpu_qop_vmult with flags 0 or MFGPU_QOP_TRANSPOSE; MFGPU_EINVAL unless the solver is MFGPU_F64 and of its length) */
+int mfgpu_bicgstab_set_operator(mfgpu_bicgstab *s, int (*apply)(void *ctx, void *dst_dev, const void *src_dev, void *stream),
+                                void *ctx);
+int mfgpu_bicgstab_set_operator_handle(mfgpu_bicgstab *s, mfgpu_handle *A);
+int mfgpu_bicgstab_set_operator_qop(mfgpu_bicgstab *s, mfgpu_qop *q, uint32_t flags);
+/* MFGPU_CG_CALLBACK: fn enqueues z = M^-1 r on `stream`, twice per iteration (y from p, z from s); the library's own
+ * callback for a V-cycle, z = mfgpu_vcycle_apply(v, z, r, stream) (MFGPU_EINVAL unless the V-cycle's active type and
+ * length are the solver's).  Both: MFGPU_EINVAL for a solver that is not a CALLBACK solver.                          */
+int mfgpu_bicgstab_set_callback(mfgpu_bicgstab *s, int (*fn)(void *ctx, void *z_dev, const void *r_dev, void *stream),
+                                void *ctx);
+int mfgpu_bicgstab_set_vcycle(mfgpu_bicgstab *s, mfgpu_vcycle *v);
+/* x = 0, r = r0 = b, p = r, y = M^-1 p; status 1 with 0 iterations if |b| <= tolerance.  MFGPU_EINVAL, nothing written:
+ * null pointers, no operator set, CALLBACK without a callback, x overlapping b.  _begin_relative: tolerance =
+ * relative_tolerance * |b| formed on the device; MFGPU_EINVAL also for a negative or non-finite relative tolerance.
+ * 16-byte accesses when x, b and inv_diag are 16-byte aligned.                                                       */
+int mfgpu_bicgstab_begin(mfgpu_bicgstab *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations,
+                         void *stream);
+int mfgpu_bicgstab_begin_relative(mfgpu_bicgstab *s, void *x_dev, const void *b_dev, double relative_tolerance,
+                                  uint32_t max_iterations, void *stream);
+/* n_iterations more iterations (MFGPU_EINVAL before begin): per iteration two operator applies and five solver launches
+ * -- the sums of r0.v; alpha, x += alpha y, r -= alpha v, the sums of s.s; the sums of t.s and t.t in one pass; omega,
+ * x += omega z, r -= omega t, the sums of r.r and r0.r; count, status, beta and the new p -- plus two preconditioner
+ * calls for CALLBACK                                                                                                 */
+int mfgpu_bicgstab_iterate(mfgpu_bicgstab *s, uint32_t n_iterations, void *stream);
+/* one asynchronous copy of the state block into the pinned mirror and a stream synchronisation (MFGPU_EINVAL before
+ * begin) */
+int mfgpu_bicgstab_status(mfgpu_bicgstab *s, void *stream, mfgpu_cg_info *info);
+/* begin; { iterate(check_every); status } until the status leaves 0.  check_every == 0: MFGPU_EINVAL */
+int mfgpu_bicgstab_solve(mfgpu_bicgstab *s, void *x_dev, const void *b_dev, double tolerance, uint32_t max_iterations,
+                         uint32_t check_every, void *stream, mfgpu_cg_info *info);
+size_t mfgpu_bicgstab_memory_consumption(const mfgpu_bicgstab *s);
+void mfgpu_bicgstab_destroy(mfgpu_bicgstab *s);
+
 /* ---- fields and point sources at arbitrary points (no reference counterpart; deal.II: VectorTools::point_value /
  * point_gradient, FEPointEvaluation::evaluate / integrate, create_point_source_vector) --------
  * MFGPU_F64 only (MFGPU_F32 description or integrator: MFGPU_EUNSUPPORTED), dim 2 and 3, degree 1..6, uniform-J0 and
