@@ -384,13 +384,16 @@ int qop_apply(void *ctx, void *dst, const void *src, void *stream) {
   mfgpu_bicgstab *s = static_cast<mfgpu_bicgstab *>(ctx);
   return mfgpu_qop_vmult(s->qop, dst, src, s->qop_flags, stream);
 }
+int vqop_apply(void *ctx, void *dst, const void *src, void *stream) {
+  return mfgpu_vqop_vmult(static_cast<mfgpu_vqop *>(ctx), dst, src, stream);
+}
 int vcycle_callback(void *ctx, void *z_dev, const void *r_dev, void *stream) {
   return mfgpu_vcycle_apply(static_cast<mfgpu_vcycle *>(ctx), z_dev, r_dev, stream);
 }
 
 int apply_operator(mfgpu_bicgstab *s, void *dst, const void *src, hipStream_t st) {
   const int rc = s->apply(s->apply_ctx, dst, src, (void *)st);
-  if (rc && s->apply != handle_apply && s->apply != qop_apply) mfgpu::set_error("mfgpu_bicgstab: the operator callback failed");
+  if (rc && s->apply != handle_apply && s->apply != qop_apply && s->apply != vqop_apply) mfgpu::set_error("mfgpu_bicgstab: the operator callback failed");
   return rc;
 }
 int precondition(mfgpu_bicgstab *s, void *dst, const void *src, hipStream_t st) {
@@ -536,6 +539,15 @@ int mfgpu_bicgstab_set_operator_qop(mfgpu_bicgstab *s, mfgpu_qop *q, uint32_t fl
   s->qop_flags = flags;
   s->apply = qop_apply;
   s->apply_ctx = s;
+  return MFGPU_OK;
+}
+
+int mfgpu_bicgstab_set_operator_vqop(mfgpu_bicgstab *s, mfgpu_vqop *q) {
+  if (!s || !q) return einval("mfgpu_bicgstab_set_operator_vqop: null argument");
+  if (s->number_type != MFGPU_F64 || mfgpu::vqop_length(q) != s->n)
+    return einval("mfgpu_bicgstab_set_operator_vqop: needs an MFGPU_F64 solver of the operator's length dim * n_dofs");
+  s->apply = vqop_apply;
+  s->apply_ctx = q;
   return MFGPU_OK;
 }
 

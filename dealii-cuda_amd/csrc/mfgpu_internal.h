@@ -264,6 +264,8 @@ void transfer_sizes(const mfgpu_transfer *t, uint32_t *n_coarse_dofs, uint32_t *
 void vcycle_active(const mfgpu_vcycle *v, int *active_type, uint32_t *n_active);
 // what mfgpu_bicgstab_set_operator_qop checks of the operator it borrows
 uint32_t qop_n_dofs(const mfgpu_qop *q);
+// and mfgpu_bicgstab_set_operator_vqop: dim * n_dofs
+size_t vqop_length(const mfgpu_vqop *q);
 
 }  // namespace mfgpu
 

@@ -100,6 +100,15 @@ class QopCoefficients(C.Structure):
     _fields_ = [("diffusion", C.c_void_p), ("convection", C.c_void_p), ("flux", C.c_void_p), ("reaction", C.c_void_p)]
 
 
+# terms of a VectorQpOperator (MFGPU_VQOP_*)
+VQOP_ISOTROPIC, VQOP_TENSOR4, VQOP_MASS = 1, 2, 4
+
+
+class VqopCoefficients(C.Structure):
+    """mirror of struct mfgpu_vqop_coefficients (device pointers)"""
+    _fields_ = [("lam", C.c_void_p), ("mu", C.c_void_p), ("tensor", C.c_void_p), ("mass", C.c_void_p)]
+
+
 # int fn(void *ctx, void *z_dev, const void *r_dev, void *stream)
 CG_CALLBACK_TYPE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
@@ -160,6 +169,9 @@ SYMBOLS = [
     "mfgpu_bicgstab_set_operator_qop", "mfgpu_bicgstab_set_callback", "mfgpu_bicgstab_set_vcycle", "mfgpu_bicgstab_begin",
     "mfgpu_bicgstab_begin_relative", "mfgpu_bicgstab_iterate", "mfgpu_bicgstab_status", "mfgpu_bicgstab_solve",
     "mfgpu_bicgstab_memory_consumption", "mfgpu_bicgstab_destroy",
+    "mfgpu_vqop_create", "mfgpu_vqop_set_coefficients", "mfgpu_vqop_vmult", "mfgpu_vqop_compute_inverse_diagonal",
+    "mfgpu_vqop_set_constrained_values", "mfgpu_vqop_memory_consumption", "mfgpu_vqop_destroy",
+    "mfgpu_bicgstab_set_operator_vqop",
 ]
 
 _lib = None
@@ -398,6 +410,16 @@ def lib():
         L.mfgpu_qop_memory_consumption.restype = C.c_size_t
         L.mfgpu_qop_destroy.argtypes = [vp]
         L.mfgpu_qop_destroy.restype = None
+        L.mfgpu_vqop_create.argtypes = [vp, u32, vp, C.c_size_t, C.POINTER(vp)]
+        L.mfgpu_vqop_set_coefficients.argtypes = [vp, C.POINTER(VqopCoefficients), vp]
+        L.mfgpu_vqop_vmult.argtypes = [vp, vp, vp, vp]
+        L.mfgpu_vqop_compute_inverse_diagonal.argtypes = [vp, vp, vp]
+        L.mfgpu_vqop_set_constrained_values.argtypes = [vp, vp, C.c_double, vp]
+        L.mfgpu_vqop_memory_consumption.argtypes = [vp]
+        L.mfgpu_vqop_memory_consumption.restype = C.c_size_t
+        L.mfgpu_vqop_destroy.argtypes = [vp]
+        L.mfgpu_vqop_destroy.restype = None
+        L.mfgpu_bicgstab_set_operator_vqop.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -1121,10 +1143,60 @@ class QpOperator:
     m = n
 
 
+class VectorQpOperator:
+    """mfgpu_vqop_*: the elasticity operator on fields of dim components in blocks (u[a * n_dofs + i]),
+    (A u)_(a,i) = sum_q JxW_q [sum_k d_k phi_i sigma_ak + phi_i rho u_a] with sigma = lam (div u) I + mu (grad u + grad u^T)
+    (VQOP_ISOTROPIC) or sigma_ak = sum_bl C[a][k][b][l] d_l u_b (VQOP_TENSOR4), and VQOP_MASS for the rho term.
+    constrained: ascending block indices in [0, dim * n_dofs) (None: the description's list in every component; a list
+    of one's own must hold every dof of the description's list, the hanging dofs among them, in every component).
+    Borrows the integrator, which it keeps alive."""
+
+    def __init__(self, integrator: "Integrator", terms, constrained=None):
+        self._it = integrator
+        h = C.c_void_p()
+        if constrained is None:
+            ptr, cnt = None, 0
+        else:
+            c = np.asarray(constrained)
+            if c.size and (c.min() < 0 or c.max() > 0xffffffff):
+                raise MfgpuError("mfgpu error -1 (MFGPU_EINVAL): constrained index out of range")
+            c = np.ascontiguousarray(c, dtype=np.uint32).reshape(-1)
+            ptr, cnt = c.ctypes.data if c.size else np.zeros(1, np.uint32).ctypes.data, c.size
+        _check(lib().mfgpu_vqop_create(integrator._h, int(terms), ptr, cnt, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mfgpu_vqop_destroy(self._h)
+            self._h = None
+
+    def set_coefficients(self, lam=None, mu=None, tensor=None, mass=None, stream=None):
+        """folds the given real-space arrays; None keeps a term's last values; lam and mu go together"""
+        c = VqopCoefficients(_optr(lam), _optr(mu), _optr(tensor), _optr(mass))
+        _check(lib().mfgpu_vqop_set_coefficients(self._h, C.byref(c), stream))
+
+    def vmult(self, dst, src, stream=None):
+        _check(lib().mfgpu_vqop_vmult(self._h, _ptr(dst), _ptr(src), stream))
+
+    def inverse_diagonal(self, inv_diag, stream=None):
+        _check(lib().mfgpu_vqop_compute_inverse_diagonal(self._h, _ptr(inv_diag), stream))
+
+    def set_constrained_values(self, vec, value, stream=None):
+        _check(lib().mfgpu_vqop_set_constrained_values(self._h, _ptr(vec), float(value), stream))
+
+    def memory_consumption(self):
+        return int(lib().mfgpu_vqop_memory_consumption(self._h))
+
+    def n(self):
+        return self._it.dim * self._it.n_dofs
+
+    m = n
+
+
 class BiCGStab:
     """Device-resident BiCGStab (mfgpu_bicgstab_*) for the non-symmetric operators, in the shape of CG: begin and iterate
     only enqueue work, status is the only blocking call.  operator: an Operator, a QpOperator (transpose=True solves with
-    A^T) or a callable apply(dst, src, stream) -> 0 / None or an error code that enqueues dst = A src on `stream`, with
+    A^T), a VectorQpOperator or a callable apply(dst, src, stream) -> 0 / None or an error code that enqueues dst = A src on `stream`, with
     dst and src DeviceVector views of the solver's vectors; a callable needs n (and number_type).  preconditioner:
     CG_NONE, CG_JACOBI (inv_diag) or CG_CALLBACK with callback(z, r, stream) as for CG, or set_vcycle.  The operator,
     inv_diag, x and b must outlive the solve.  The methods return the raw code with check=False."""
@@ -1133,7 +1205,7 @@ class BiCGStab:
                  number_type=None):
         self._op, self._inv_diag = operator, inv_diag
         self._cb = self._apply = self._cb_error = None
-        if isinstance(operator, (Operator, QpOperator)):
+        if isinstance(operator, (Operator, QpOperator, VectorQpOperator)):
             self.n = operator.n()
             self.number_type = operator.number_type if isinstance(operator, Operator) else F64
         elif callable(operator):
@@ -1149,6 +1221,8 @@ class BiCGStab:
             _check(lib().mfgpu_bicgstab_set_operator_handle(h, operator._h))
         elif isinstance(operator, QpOperator):
             _check(lib().mfgpu_bicgstab_set_operator_qop(h, operator._h, QOP_TRANSPOSE if transpose else 0))
+        elif isinstance(operator, VectorQpOperator):
+            _check(lib().mfgpu_bicgstab_set_operator_vqop(h, operator._h))
         else:
             self._apply = CG_CALLBACK_TYPE(self._trampoline(operator))
             _check(lib().mfgpu_bicgstab_set_operator(h, self._apply, None))

@@ -917,6 +917,68 @@ int mfgpu_qop_compute_inverse_diagonal(mfgpu_qop *q, void *inv_diag, void *strea
 size_t mfgpu_qop_memory_consumption(const mfgpu_qop *q);
 void mfgpu_qop_destroy(mfgpu_qop *q);
 
+/* ---- the vector-valued quadrature-point operator: linear elasticity (no reference counterpart; deal.II: a user LocOp
+ * over FEEvaluation<dim, p, p+1, dim>) ---------------------------------------------------------
+ * A field has dim components on the description's scalar FE_Q(p) space, stored in BLOCKS: u[a * n_dofs + i] is component
+ * a at scalar dof i, length dim * n_dofs.  Every component uses the integrator's loc2glob, constraint masks and gather
+ * lists; a component is a plain scalar vector for mfgpu_integrator_evaluate / _integrate, mfgpu_points_* and the
+ * transfers, and the whole vector one for mfgpu_vec_* and mfgpu_bicgstab.  Free rows, with sigma the point-wise stress:
+ *   (A u)_(a,i) = sum_cells sum_q JxW_q [ sum_k d_k phi_i(x_q) sigma_ak(x_q) + phi_i(x_q) rho_q u_a(x_q) ]
+ *   MFGPU_VQOP_ISOTROPIC  sigma = lambda_q (div u) I + mu_q (grad u + grad u^T)
+ *   MFGPU_VQOP_TENSOR4    sigma_ak = sum_bl C_q[a][k][b][l] d_l u_b   (any tensor: no symmetry is assumed)
+ *   MFGPU_VQOP_MASS       the rho term
+ * Constrained rows are identity rows, constrained entries of src are read as 0 (the rules of mfgpu_vmult and
+ * mfgpu_qop_vmult); a dof no cell references gets 0.  MFGPU_F64 only, dim 2 and 3, degree 1..6, uniform-J0 and general
+ * geometry; with hanging nodes the cell's mask applies to every component.
+ *
+ * mfgpu_vqop_create BORROWS the integrator as mfgpu_qop_create does (destroy the operator first; calls that share an
+ * integrator must be ordered).  terms: a non-empty set of the three bits; both stress bits, or an unknown bit:
+ * MFGPU_EINVAL.  ISOTROPIC and TENSOR4 need an integrator created with MFGPU_UPDATABLE_COEFFICIENTS (else MFGPU_EINVAL);
+ * a MASS-only operator works on any integrator.
+ * constrained: an ascending list of n_constrained indices in the block numbering [0, dim * n_dofs), copied; NULL: the
+ * description's constrained_dofs in every component.  Not strictly ascending, or an index out of range: MFGPU_EINVAL.
+ * A caller's own list fixes single components on a face (sliding and symmetry boundaries).  It must contain, in every
+ * component, each hanging dof and every other dof of the description's constrained_dofs (MFGPU_EINVAL otherwise): the
+ * integrator's gather lists leave those rows empty.  For boundary dofs that are free in some component, create the
+ * integrator from a description whose constrained_dofs holds the hanging dofs alone.
+ *
+ * mfgpu_vqop_set_coefficients folds the caller's real-space device arrays once per update (enqueue only, no allocation,
+ * no read-back), cell-major, points x fastest; per point lambda, mu, mass: one double; tensor: dim^4 doubles row-major
+ * (a, k, b, l).  NULL keeps a term's last values.  lambda without mu or mu without lambda, a pointer for a term not in
+ * `terms`, or NULL everywhere: MFGPU_EINVAL.  vmult / the diagonal before every term has been set once: MFGPU_EINVAL.
+ * Folded forms ([cell][component][q]) and bytes per point -- mfgpu_vqop_memory_consumption returns exactly their sum
+ * over the points plus the dim * n_dofs bytes of the operator's own constraint flags:
+ *   MFGPU_VQOP_TENSOR4    JxW sum_kl J^-1[e][k] C[a][k][b][l] J^-1[f][l]        8 dim^4  (128 in 2D, 648 in 3D)
+ *   MFGPU_VQOP_ISOTROPIC  uniform-J0: lambda J0^2 JxW, mu J0^2 JxW              16
+ *                         general: lambda JxW, mu JxW; the apply reads the      16  (+ the integrator's 8 dim^2 inv_jac,
+ *                         integrator's inv_jac: grad_x u_b = J^-T grad_xi u_b,       read, not stored again)
+ *                         sigma, then the reference flux J^-1 sigma_a
+ *   MFGPU_VQOP_MASS       JxW rho                                               8
+ *
+ * mfgpu_vqop_vmult: one cell kernel (one wave per cell: gather dim components, hanging-node resolution, dim^2 reference
+ * gradients, the law in place, integration per component, transposed resolution, dim local vectors -- the integrator's
+ * scratch plus dim - 1 copies of its size that the operator owns) and one gather launch for all components, which
+ * writes the identity rows.  No atomics, bitwise repeatable, every entry of dst written, src never written, dst may be
+ * src.  mfgpu_vqop_compute_inverse_diagonal: 1 / A_jj with the hanging-node constraints applied (cell applies on local
+ * unit vectors), 1 on constrained and unreferenced entries.  mfgpu_vqop_set_constrained_values: vec[j] = value on the
+ * operator's constrained list (makes a right-hand side built per component by mfgpu_integrator_integrate consistent
+ * with a per-component list).  All three only enqueue.                                                              */
+typedef struct mfgpu_vqop mfgpu_vqop;
+#define MFGPU_VQOP_ISOTROPIC (1u << 0) /* lambda, mu [n_cells*ND] each                          */
+#define MFGPU_VQOP_TENSOR4   (1u << 1) /* C [n_cells*ND*dim^4], row-major (a,k,b,l), any tensor */
+#define MFGPU_VQOP_MASS      (1u << 2) /* rho [n_cells*ND]                                      */
+typedef struct mfgpu_vqop_coefficients {
+  const void *lambda, *mu, *tensor, *mass; /* device arrays */
+} mfgpu_vqop_coefficients;
+int mfgpu_vqop_create(mfgpu_integrator *it, uint32_t terms, const uint32_t *constrained, size_t n_constrained,
+                      mfgpu_vqop **out);
+int mfgpu_vqop_set_coefficients(mfgpu_vqop *q, const mfgpu_vqop_coefficients *c, void *stream);
+int mfgpu_vqop_vmult(mfgpu_vqop *q, void *dst, const void *src, void *stream);
+int mfgpu_vqop_compute_inverse_diagonal(mfgpu_vqop *q, void *inv_diag, void *stream);
+int mfgpu_vqop_set_constrained_values(mfgpu_vqop *q, void *vec, double value, void *stream);
+size_t mfgpu_vqop_memory_consumption(const mfgpu_vqop *q);
+void mfgpu_vqop_destroy(mfgpu_vqop *q);
+
 /* ---- device-resident BiCGStab (no reference counterpart): the solver for the non-symmetric
  * operators above, in the style of mfgpu_cg.  The algorithm is SolverBicgstab::solve of host/mfgpu_shim_qop.h:
  * right-preconditioned, zero start (x = 0, r = r0 = b), per iteration p = r + beta (p - omega v), y = M^-1 p, v = A y,
@@ -952,6 +1014,8 @@ int mfgpu_bicgstab_set_operator(mfgpu_bicgstab *s, int (*apply)(void *ctx, void 
                                 void *ctx);
 int mfgpu_bicgstab_set_operator_handle(mfgpu_bicgstab *s, mfgpu_handle *A);
 int mfgpu_bicgstab_set_operator_qop(mfgpu_bicgstab *s, mfgpu_qop *q, uint32_t flags);
+/* a mfgpu_vqop (mfgpu_vqop_vmult; MFGPU_EINVAL unless the solver is MFGPU_F64 and of length dim * n_dofs) */
+int mfgpu_bicgstab_set_operator_vqop(mfgpu_bicgstab *s, mfgpu_vqop *q);
 /* MFGPU_CG_CALLBACK: fn enqueues z = M^-1 r on `stream`, twice per iteration (y from p, z from s); the library's own
  * callback for a V-cycle, z = mfgpu_vcycle_apply(v, z, r, stream) (MFGPU_EINVAL unless the V-cycle's active type and
  * length are the solver's).  Both: MFGPU_EINVAL for a solver that is not a CALLBACK solver.                          */
